@@ -22,7 +22,16 @@ last thing printed: the headline record, numbers only, under 4 KB (`headline()` 
 not parseable by the driver), closed by a short `digest` of the secondary entries.  `--full-secondary` adds the CPU / GPU-eager baselines of those entries and the evaluation loop without
 the producer overlap (minutes of host time); `--no-secondary` skips them all.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+Everything above beyond the timed steps -- the per-kernel split and `roofline`, `cpu_baseline`, `gpu_eager_baseline`, the
+secondary configurations, `projected`, `digest` and the side file -- is measured only with `--full`.  A plain run sets up,
+warms up, times --steps frames and prints the headline (metric, value, unit, ms_per_step, ...) and nothing else; the side
+file is written only where --details names one.  `--dump-outputs DIR` writes what the last timed frame rendered, the
+arrays a caller of ufr_render_rays receives (depth, depth_z: H x W; rgb: H x W x 3; float32, gathered over the ranks), as
+DIR/<name>.npy.  The sampler uniforms of the timed frames come from a generator seeded at setup, so the same arguments
+render the same frames in every run and two builds can be compared output for output.
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -51,6 +60,8 @@ PEAK_F16_MFMA_TFLOPS = 2516.6  # dense fp16 / bf16 MFMA peak: 256 CU x 4 SIMD x 
 # operands, fp32 accumulate: ufr_layout_f16.h), so their matrix-core bound in fp32-equivalent flop is peak/3
 PEAK_F32_VIA_F16X3_TFLOPS = PEAK_F16_MFMA_TFLOPS / 3.0
 SIDE_FILE = os.path.join(ROOT, "bench_secondary.json")
+UNIFORM_SEED = 0  # the timed frames' sampler uniforms: one seeded GPU generator per process (per rank)
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: 5 float32 per pixel; larger frames are written as a seeded pixel sample
 
 
 def parse(argv=None):
@@ -73,12 +84,21 @@ def parse(argv=None):
     p.add_argument("--fixed-uniforms", type=int, default=-1, metavar="SEED",
                    help=">= 0: sampler uniforms are one seeded draw for the whole frame, sliced per rank (so an N-rank run "
                         "renders exactly the frame a 1-rank run renders); default: fresh GPU draws every step")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what explains the headline: per-kernel split and roofline, the CPU and GPU-eager "
+                        "baselines, the secondary configurations (single GPU, configs[1]), the projection and the digest; "
+                        "the whole record goes to --details (default bench_secondary.json) and stderr")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes the last timed frame's depth, depth_z (H x W) and rgb (H x W x 3) as DIR/<name>.npy "
+                        "(float32)")
     p.add_argument("--dump-depth", default="", help="rank 0 writes the (gathered) H x W depth map of the last step here (.npy)")
     p.add_argument("--no-secondary", action="store_true", help="skip the configs[3] / configs[4] measurements attached as "
                                                                 "`secondary` to a single-GPU line")
     p.add_argument("--secondary-train-steps", type=int, default=10)
-    p.add_argument("--details", default=SIDE_FILE, help="where the whole record (per-kernel split, per-rank tables, secondary "
-                                                        "entries, projection, prose) is written; it is echoed on stderr too")
+    p.add_argument("--details", default=None, help="where the whole record (per-kernel split, per-rank tables, secondary "
+                                                   "entries, projection, prose) is written; it is echoed on stderr too "
+                                                   "(default: bench_secondary.json beside this file with --full or --config "
+                                                   "c3, none otherwise)")
     p.add_argument("--stub-secondary", action="store_true",
                    help="tests: attach worst-case-sized placeholder secondary entries instead of measuring them, so that the "
                         "real configs[1] command path (digest, projection, headline size guard) runs in seconds")
@@ -156,6 +176,28 @@ def gpu_eager_baseline(frame_cpu, weights_cpu, a, dev):
                        f"(= {HW / RN * med:.1f} s per {a.height}x{a.width} frame)")
 
 
+def dump_outputs(path, out, shard, rank):
+    """What ufr_render_rays handed back in the last timed frame, gathered over the ranks (a collective: every rank calls
+    this), written by rank 0 as path/<name>.npy in float32: depth and depth_z (H x W), rgb (H x W x 3).  A frame of more
+    than DUMP_MAX_BYTES is written as a fixed seeded sample of its pixels instead (depth, depth_z: (n,), rgb: (n, 3))."""
+    import numpy as np
+
+    from uforecon_amd.dist import all_gather_tiles
+
+    depth, rgb = all_gather_tiles(out["depth"], out["rgb"], shard)
+    depth_z, _ = all_gather_tiles(out["depth_z"], None, shard)
+    if rank != 0:
+        return
+    arrays = dict(depth=depth, depth_z=depth_z, rgb=rgb)
+    HW = depth.numel()
+    if HW * 5 * 4 > DUMP_MAX_BYTES:
+        pick = torch.randperm(HW, generator=torch.Generator().manual_seed(0))[:DUMP_MAX_BYTES // (5 * 4)].sort().values
+        arrays = {k: v.reshape(HW, -1)[pick.to(v.device)].squeeze(1) for k, v in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.detach().float().cpu().numpy())
+
+
 def config_name(a):
     if (a.views, a.height, a.width, a.coarse, a.fine) == (3, 512, 640, 64, 64):
         return "configs[1]"
@@ -187,6 +229,8 @@ def measure_frames(a, dev, world, rank):
     out = dict(depth=torch.empty(RN, device=dev), depth_z=torch.empty(RN, device=dev), rgb=torch.empty(RN, 3, device=dev))
     gathered = None
     fixed = None
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(UNIFORM_SEED)
     if a.fixed_uniforms >= 0:
         g = torch.Generator().manual_seed(a.fixed_uniforms)
         fixed = (torch.rand(a.coarse, HW, generator=g).to(dev)[:, ray_idx].contiguous(),
@@ -196,8 +240,8 @@ def measure_frames(a, dev, world, rank):
     def step():
         nonlocal gathered
         fh = ops.FrameHandle(frame.batch, frame.source_imgs_feat, frame.feature_volume, frame.match_feature)
-        U1 = fixed[0] if fixed else torch.rand(a.coarse, RN, device=dev)
-        U2 = fixed[1] if fixed else torch.rand(a.fine, RN, device=dev)
+        U1 = fixed[0] if fixed else torch.rand(a.coarse, RN, device=dev, generator=gen)
+        U2 = fixed[1] if fixed else torch.rand(a.fine, RN, device=dev, generator=gen)
         ops.render_rays(fh, W, ray_idx, U1, U2, workspace=ws, want_srdf=False, out=out)
         if world > 1:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -218,14 +262,18 @@ def measure_frames(a, dev, world, rank):
         step()
     fence()
     ag_events.clear()
-    ops.profile_enable(a.streams <= 1)
+    ops.profile_enable(a.full and a.streams <= 1)
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:           # the last timed frame, before any untimed frame below overwrites `out`
+        dump_outputs(a.dump_outputs, out, shard, rank)
     prof_steps = a.steps
-    if a.streams > 1:  # per-kernel durations: untimed single-stream frames (see the module docstring)
+    if not a.full:
+        prof = {}
+    elif a.streams > 1:  # per-kernel durations: untimed single-stream frames (see the module docstring)
         ws1 = ops.RenderWorkspace(dev, a.coarse, a.fine, a.views, chunk_rays=a.chunk, n_streams=1)
         ws, prof_steps = ws1, 1
         step()
@@ -288,20 +336,21 @@ def measure_frames(a, dev, world, rank):
         rt_achieved = rt_flop / (rt_ms * 1e-3) / 1e12 if rt_ms > 0 else 0.0
         traffic, traffic_src = None, None
         pmc_vt, pmc_rt, pmc_src = None, None, None
-        try:  # HBM bytes per view-transformer launch from the latest committed PMC pass OF THIS CONFIGURATION
-            # (profiles/rN_pmc.json: configs[1]; profiles/rN_c4_pmc.json: configs[3], the L = 6 instantiation)
-            import glob
-            pat = {"configs[1]": "r*[0-9]_pmc.json", "configs[3]": "r*_c4_pmc.json"}.get(cfg)
-            pj = sorted(glob.glob(os.path.join(ROOT, "profiles", pat)))[-1]
-            for k, v in json.load(open(pj)).items():
-                if f"view_transformer_kernel<{a.views + 1}," in k and v.get("hbm_bytes_per_launch"):
-                    traffic, traffic_src = v["hbm_bytes_per_launch"], os.path.relpath(pj, ROOT)
-                if f"view_transformer_kernel<{a.views + 1}," in k and v.get("SQ_VALU_MFMA_BUSY_CYCLES"):
-                    pmc_vt, pmc_src = v, os.path.relpath(pj, ROOT)
-                if k.startswith("ray_transformer_kernel") and v.get("SQ_VALU_MFMA_BUSY_CYCLES"):
-                    pmc_rt = v
-        except Exception:  # noqa: BLE001
-            pass
+        if a.full:
+            try:  # HBM bytes per view-transformer launch from the latest committed PMC pass OF THIS CONFIGURATION
+                # (profiles/rN_pmc.json: configs[1]; profiles/rN_c4_pmc.json: configs[3], the L = 6 instantiation)
+                import glob
+                pat = {"configs[1]": "r*[0-9]_pmc.json", "configs[3]": "r*_c4_pmc.json"}.get(cfg)
+                pj = sorted(glob.glob(os.path.join(ROOT, "profiles", pat)))[-1]
+                for k, v in json.load(open(pj)).items():
+                    if f"view_transformer_kernel<{a.views + 1}," in k and v.get("hbm_bytes_per_launch"):
+                        traffic, traffic_src = v["hbm_bytes_per_launch"], os.path.relpath(pj, ROOT)
+                    if f"view_transformer_kernel<{a.views + 1}," in k and v.get("SQ_VALU_MFMA_BUSY_CYCLES"):
+                        pmc_vt, pmc_src = v, os.path.relpath(pj, ROOT)
+                    if k.startswith("ray_transformer_kernel") and v.get("SQ_VALU_MFMA_BUSY_CYCLES"):
+                        pmc_rt = v
+            except Exception:  # noqa: BLE001
+                pass
 
         def pmc_fracs(v, algo_flop_per_launch_in_that_run):
             """From the committed SQ counter pass: the fraction of the launch the matrix pipes were busy (busy cycles summed
@@ -356,23 +405,26 @@ def measure_frames(a, dev, world, rank):
                           # 840 v_mfma_f32_16x16x32_f16 (16 384 flop each) per 8 points at NV = 3, K / row padding included
                           issued_f16_tflops=achieved * (840 * 16384 / 8) / VIEWT_FLOP_PER_POINT[3] if a.views == 3 else None),
         )
-        # reproducible from profiles/ without trusting the peak basis: matrix-pipe busy fraction and issued / algorithmic work
-        # of the same kernels in the committed counter pass (which ran the same chunking: points per launch = vt_pts_per_launch)
-        busy, over, valu = pmc_fracs(pmc_vt, vt_flop)
-        line["roofline"].update(mfma_busy_frac=busy, valu_busy_frac=valu, issued_over_algorithmic=over, pmc_source=pmc_src)
-        rbusy, rover, rvalu = pmc_fracs(pmc_rt, rt_flop)
-        line["roofline"]["ray_transformer"].update(mfma_busy_frac=rbusy, valu_busy_frac=rvalu, issued_over_algorithmic=rover,
-                                                   traffic=(pmc_rt or {}).get("hbm_bytes_per_launch"))
-        if not a.no_gpu_eager_baseline and world == 1:
-            # the >= 20x target's denominator, measured in the same run on the same GPU (BASELINE.md has no published
-            # number: vs_baseline is relative to this leg, not to a figure from the reference's authors)
-            eager = gpu_eager_baseline(frame_cpu, weights_cpu, a, dev)
-            line["gpu_eager_baseline"] = eager
-            line["vs_baseline"] = rays_per_s / eager["value"]
-            line["config"]["vs_baseline_denominator"] = ("gpu_eager_baseline.value: eager PyTorch restatement of the reference "
-                                                         "path on this GPU, 800-ray chunks (BASELINE.md section 3)")
-        if not a.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(frame_cpu, weights_cpu, a)
+        if not a.full:           # no per-kernel split was measured: the headline fields alone
+            del line["roofline"], line["config"]["kernel_ms_per_frame_rank0"], line["config"]["kernel_ms_measured"]
+        else:
+            # reproducible from profiles/ without trusting the peak basis: matrix-pipe busy fraction and issued / algorithmic work
+            # of the same kernels in the committed counter pass (which ran the same chunking: points per launch = vt_pts_per_launch)
+            busy, over, valu = pmc_fracs(pmc_vt, vt_flop)
+            line["roofline"].update(mfma_busy_frac=busy, valu_busy_frac=valu, issued_over_algorithmic=over, pmc_source=pmc_src)
+            rbusy, rover, rvalu = pmc_fracs(pmc_rt, rt_flop)
+            line["roofline"]["ray_transformer"].update(mfma_busy_frac=rbusy, valu_busy_frac=rvalu, issued_over_algorithmic=rover,
+                                                       traffic=(pmc_rt or {}).get("hbm_bytes_per_launch"))
+            if not a.no_gpu_eager_baseline and world == 1:
+                # the >= 20x target's denominator, measured in the same run on the same GPU (BASELINE.md has no published
+                # number: vs_baseline is relative to this leg, not to a figure from the reference's authors)
+                eager = gpu_eager_baseline(frame_cpu, weights_cpu, a, dev)
+                line["gpu_eager_baseline"] = eager
+                line["vs_baseline"] = rays_per_s / eager["value"]
+                line["config"]["vs_baseline_denominator"] = ("gpu_eager_baseline.value: eager PyTorch restatement of the reference "
+                                                             "path on this GPU, 800-ray chunks (BASELINE.md section 3)")
+            if not a.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(frame_cpu, weights_cpu, a)
     del frame, out, ws, W, gathered, fixed
     torch.cuda.empty_cache()
     return line
@@ -500,6 +552,7 @@ def secondary_measurements(a, dev):
     torch.cuda.empty_cache()
     c3 = parse(["--views", "5", "--height", "600", "--width", "800", "--coarse", "128", "--fine", "128", "--steps", "2",
                 "--warmup", "1", "--streams", str(a.streams), "--cpu-rays", "64", "--cpu-calls", "2", "--eager-chunks", "2"])
+    c3.full = True               # its per-kernel split and roofline (the digest reads them)
     c3.no_cpu_baseline = a.no_cpu_baseline or not full
     c3.no_gpu_eager_baseline = a.no_gpu_eager_baseline or not full
     sec["configs[3]"] = measure_frames(c3, dev, 1, 0)
@@ -599,7 +652,7 @@ def _r(x, nd=8):
     return x
 
 
-def headline(full):
+def headline(full, details=os.path.basename(SIDE_FILE)):
     """The ONE stdout line: the contract's fields, `roofline` / `cpu_baseline` / `gpu_eager_baseline` as numbers plus a
     one-sentence sample description, a digest of the secondary entries -- and nothing else.  Everything that explains
     (peak basis, power note, arithmetic, per-kernel split, per-rank tables, projection) lives in bench_secondary.json
@@ -632,7 +685,8 @@ def headline(full):
             h[k] = {kk: _r(vv) for kk, vv in full[k].items()}
     if full.get("secondary_error"):
         h["secondary_error"] = str(full["secondary_error"])[:200]
-    h["details"] = os.path.basename(SIDE_FILE) + " (also on stderr)"
+    if details:
+        h["details"] = details + " (also on stderr)"
     if full.get("digest"):
         h["digest"] = full["digest"]
     for drop in ((), ("details",), ("config", "per_rank"), ("gpu_eager_baseline", "sample"), ("cpu_baseline", "sample"), ("digest",)):
@@ -648,17 +702,17 @@ def headline(full):
 
 
 def emit(full, path=None):
-    """Side file + stderr get the whole record; stdout gets the headline as its ONLY and LAST line."""
-    path = path or SIDE_FILE
-    doc = json.dumps(full, indent=1)
-    try:
-        with open(path, "w") as f:
-            f.write(doc + "\n")
-    except OSError as e:          # a read-only checkout must not cost the run its headline
-        print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
-    print(doc, file=sys.stderr, flush=True)
-    sys.stderr.flush()
-    print(headline(full), flush=True)
+    """Side file + stderr get the whole record (path None: neither); stdout gets the headline as its ONLY and LAST line."""
+    if path:
+        doc = json.dumps(full, indent=1)
+        try:
+            with open(path, "w") as f:
+                f.write(doc + "\n")
+        except OSError as e:          # a read-only checkout must not cost the run its headline
+            print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
+        print(doc, file=sys.stderr, flush=True)
+        sys.stderr.flush()
+    print(headline(full, os.path.basename(path) if path else None), flush=True)
 
 
 def main():
@@ -684,13 +738,15 @@ def main():
     if a.config == "c3":
         line = measure_evalset(a, dev, world, rank)
         if rank == 0:
-            emit(line, a.details)
+            emit(line, a.details or SIDE_FILE)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
         return
     line = measure_frames(a, dev, world, rank)
-    if rank == 0:
+    if rank == 0 and not a.full:
+        emit(line, a.details)
+    elif rank == 0:
         if world == 1 and not a.no_secondary and config_name(a) == "configs[1]":
             if a.stub_secondary:
                 line["secondary"] = stub_secondary()
@@ -704,7 +760,7 @@ def main():
         if world == 1 and config_name(a) == "configs[1]":
             line["projected"] = projection(line)
         line["digest"] = digest(line)
-        emit(line, a.details)
+        emit(line, a.details or SIDE_FILE)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

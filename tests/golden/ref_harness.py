@@ -1,8 +1,8 @@
 """Import the upstream UFORecon per-ray path on CPU (THIS container only).
 
-Used only by ``make_golden.py`` and by ``tests/test_oracle_vs_reference.py`` (which is
-skipped wherever /root/reference is absent, e.g. on the GPU box).  Nothing of the
-reference travels: only the numeric vectors this produces are committed.
+Used only by the generators beside it (``make_golden*.py``, ``make_bf16_anchor.py``); no
+test imports it.  Nothing of the reference travels: only the numeric vectors this produces
+are committed.
 
 The reference needs pytorch_lightning / torchvision / kornia / cv2 / piq / mcubes /
 easydict at *import* time only; none of them is touched by the per-ray path, so empty

@@ -77,7 +77,7 @@ def test_headline_sheds_optional_blocks_before_failing():
 def test_bench_headline_size(tmp_path):
     """The command the driver runs (configs[1], full 512x640 frame), with stub secondary entries of worst-case size."""
     side = str(tmp_path / "details.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--stub-secondary", "--details", side,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--stub-secondary", "--details", side,
                         "--eager-chunks", "1", "--cpu-calls", "1", "--cpu-rays", "64"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -94,3 +94,35 @@ def test_bench_headline_size(tmp_path):
     full = json.load(open(side))                                     # the whole record went to the side file (and stderr)
     assert "secondary" in full and "projected" in full and full["value"] == pytest.approx(d["value"], rel=1e-8)
     assert '"projected"' in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_the_last_timed_frame(tmp_path):
+    """bench.py without --full: the headline fields of the timed steps and nothing measured beside them; --dump-outputs
+    writes the arrays the last timed frame rendered, the same ones in every run with the same arguments (the uniforms come
+    from a seeded generator) -- and, with the same number of frames drawn before it, whatever the warm-up / timed split."""
+    import numpy as np
+
+    names = dict(depth=(64, 96), depth_z=(64, 96), rgb=(64, 96, 3))
+    dumps = []
+    for k, (steps, warmup) in enumerate(((3, 1), (3, 1), (2, 2))):
+        d_out = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--height", "64", "--width", "96",
+                            "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(d_out)],
+                           capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = r.stdout.strip().splitlines()
+        assert len(out) == 1, out[:3]
+        d = json.loads(out[0])
+        assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "rays/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["metric"].startswith("rays/s") and d["ms_per_step"] > 0
+        assert abs(d["value"] - 64 * 96 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for k_ in ("roofline", "cpu_baseline", "gpu_eager_baseline", "digest", "details"):
+            assert k_ not in d, k_
+        arrays = {n: np.load(d_out / f"{n}.npy") for n in names}
+        for n, shape in names.items():
+            assert arrays[n].shape == shape and arrays[n].dtype == np.float32 and np.isfinite(arrays[n]).all(), n
+        dumps.append(arrays)
+    assert float(dumps[0]["depth"].std()) > 0
+    for n in names:
+        assert np.array_equal(dumps[0][n], dumps[1][n]) and np.array_equal(dumps[0][n], dumps[2][n]), n

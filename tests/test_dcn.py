@@ -48,26 +48,30 @@ def test_oracle_out_of_image_samples_contribute_zero():
 
 def test_mirror_keys_and_plain_convolutions_match_the_reference():
     """The reference FeatureNet constructs without torchvision (only its forward needs deform_conv2d): same state_dict
-    keys, and the plain-convolution trunk (conv0/conv1/conv2, inner1/inner2) gives the reference's numbers."""
-    ref_dir = "/root/reference"
-    if not os.path.isdir(os.path.join(ref_dir, "code1")):
-        pytest.skip("reference tree not present (GPU box)")
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    from ref_harness import import_reference
-    import_reference()
-    from code1.encoder_utils.fmt.module import FeatureNet as Ref
+    keys, and the plain-convolution trunk (conv0/conv1/conv2, inner1/inner2) gives the reference's numbers.  The reference's
+    side is tests/golden/vs_reference.npz (tests/golden/make_golden_vs_reference.py): its keys, the trunk's module tree
+    (the same modules in the same order compute the same bits) and the trunk's outputs, which another host's convolution
+    library may round differently, hence the one-ulp-scale bound on the values."""
+    import numpy as np
+
     from uforecon_amd import featurenet as FN
 
-    r, m = fill_state_dict(Ref(base_channels=8), 11).eval(), fill_state_dict(FN.FeatureNet(8), 11).eval()
-    assert set(r.state_dict()) == set(m.state_dict())
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vs_reference.npz"))
+    m = fill_state_dict(FN.FeatureNet(8), 11).eval()
+    assert set(z["fnet/keys"].tolist()) == set(m.state_dict())
+    for name in ("conv0", "conv1", "conv2", "inner2"):
+        assert str(z[f"fnet/repr/{name}"]) == repr(getattr(m, name)), name
+
+    def close(got, want):
+        want = torch.from_numpy(want)
+        return float((got - want).abs().max()) <= 1e-6 * float(want.abs().max())
+
     x = torch.rand(2, 3, 32, 48, generator=torch.Generator().manual_seed(1))
     with torch.no_grad():
         for name in ("conv0", "conv1", "conv2"):
-            x_r = getattr(r, name)(x)
-            assert torch.equal(x_r, getattr(m, name)(x)), name
-            x = x_r
-        assert torch.equal(r.inner2(r.conv0(torch.ones(1, 3, 8, 8))), m.inner2(m.conv0(torch.ones(1, 3, 8, 8))))
+            assert close(getattr(m, name)(x), z[f"fnet/{name}"]), name
+            x = torch.from_numpy(z[f"fnet/{name}"])
+        assert close(m.inner2(m.conv0(torch.ones(1, 3, 8, 8))), z["fnet/inner2_conv0_ones"])
 
 
 @pytest.mark.gpu

@@ -162,8 +162,8 @@ def test_two_rank_bench_renders_the_one_rank_frame(tmp_path):
     import numpy as np
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--height", "64", "--width", "96", "--steps", "1", "--warmup", "1", "--fixed-uniforms", "7", "--no-cpu-baseline",
-              "--no-gpu-eager-baseline", "--chunk", "2048"]
+    common = ["--height", "64", "--width", "96", "--steps", "1", "--warmup", "1", "--fixed-uniforms", "7", "--full",
+              "--no-cpu-baseline", "--no-gpu-eager-baseline", "--chunk", "2048"]
     backend, env = _two_rank_backend()
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--details", str(tmp_path / "one.json"), "--dump-depth", str(tmp_path / "d1.npy"),
                           *common], capture_output=True, text=True, env=env, timeout=600)
@@ -287,7 +287,7 @@ def test_bench_line_contract(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--height", "64", "--width", "96", "--steps", "2", "--warmup", "1",
-                        "--eager-chunks", "1"], capture_output=True, text=True, timeout=900,
+                        "--full", "--eager-chunks", "1"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

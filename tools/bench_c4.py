@@ -12,5 +12,6 @@ import bench  # noqa: E402
 if __name__ == "__main__":
     pinned = ["--views", "5", "--height", "600", "--width", "800", "--coarse", "128", "--fine", "128"]
     defaults = [] if any(a.startswith("--steps") for a in sys.argv[1:]) else ["--steps", "2", "--warmup", "1"]
-    sys.argv = [sys.argv[0], *pinned, *defaults, "--cpu-rays", "64", "--cpu-calls", "2", "--eager-chunks", "2", *sys.argv[1:]]
+    sys.argv = [sys.argv[0], *pinned, *defaults, "--full", "--cpu-rays", "64", "--cpu-calls", "2", "--eager-chunks", "2",
+                *sys.argv[1:]]
     bench.main()

@@ -12,7 +12,7 @@ bash tools/dev/ab_kernels.sh 4 "$@"
 echo "== frame (configs[1], 3 side streams)"
 for r in 1 2; do for v in "$@"; do
   if [ "$v" = default ]; then L=$PWD/uforecon_amd/lib/libufr.so; else L=$PWD/uforecon_amd/lib/libufr_$v.so; fi
-  UFR_LIB=$L python bench.py --steps 8 --warmup 2 --no-secondary --no-cpu-baseline --no-gpu-eager-baseline --details /tmp/ab_$v.json 2>/dev/null | python -c "
+  UFR_LIB=$L python bench.py --steps 8 --warmup 2 --full --no-secondary --no-cpu-baseline --no-gpu-eager-baseline --details /tmp/ab_$v.json 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v frame_ms', round(d['ms_per_step'],2), 'view_t_ms', d['roofline']['avg_launch_ms'], 'ray_t_ms', d['roofline']['ray_transformer']['avg_launch_ms'])"
 done; done
