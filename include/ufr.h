@@ -32,7 +32,7 @@ enum ufr_status {
 
 /* Version of this header's ABI (argument lists, struct layouts, packed-blob layout).  ufr_version() returns the value
  * the library was built with: a binding must refuse a library whose version differs (uforecon_amd/_lib.py does). */
-#define UFR_ABI_VERSION 503
+#define UFR_ABI_VERSION 504
 
 #define UFR_MAX_VIEWS 7
 #define UFR_NUM_STAGES 3
@@ -535,6 +535,33 @@ int ufr_tsdf_integrate(float* tsdf, float* weight, float* color, const int32_t* 
                        float voxel_size, float trunc_margin, const float* cam_intr, const float* cam_pose,
                        const float* depth_im, const float* color_im, int32_t im_h, int32_t im_w, float obs_weight,
                        int32_t integrate_color, ufr_stream stream);
+
+/* ---- marching cubes over a fused TSDF volume (ABI 504) ----------------------------------------------------
+ * Replaces skimage.measure.marching_cubes_lewiner(tsdf_vol, level=0) in TSDFVolume.get_mesh / get_point_cloud
+ * (tsdf_fusion.py:319-357) on the device: vol (X,Y,Z) fp32, z fastest (device), dim host int32[3], each >= 2, fewer than
+ * 2^31 voxels.  Output: an indexed triangle mesh with shared vertices, in voxel-index coordinates:
+ *   a corner is below iff v < level; the edge p -> p + e_a (values a, b) carries a vertex iff exactly one end is below,
+ *   at p with p[a] + t, t = (level - a) / (b - a); vertex order = (owner voxel p linear index, axis x < y < z);
+ *   normal = +grad f (central differences, one-sided at the border) interpolated with t, normalised ((0,0,0) if zero);
+ *   faces in (cube linear index, case-table order) order, wound so that the right-hand normal points towards increasing
+ *   f.  Ambiguous cube faces are split around their below corners (tools/gen_mcubes_table.py): closed surfaces come out
+ *   closed and consistently oriented.  No atomics: the output is deterministic.
+ * Two calls with the same vol, dim, level and workspace (>= ufr_marching_cubes_workspace_bytes(dim), 4 B per voxel + a
+ * little, device):
+ *   ufr_marching_cubes_count: counts_host[0] = V, counts_host[1] = F.  SYNCHRONISES the stream (the host needs the two
+ *     counts to size the outputs); V or F >= 2^31 is an error.
+ *   ufr_marching_cubes_emit: verts (V,3) fp32, normals (V,3) fp32, faces (F,3) int32 (device; nullable when their count
+ *     is 0).  n_verts / n_faces: the capacities of those arrays (the counts the first call returned); nothing beyond
+ *     them is written.  Does not synchronise.
+ * ufr_marching_cubes_table: host copy of the 256-case table, UFR_MC_TABLE_ROW int8 per case (edge triples, -1 padded;
+ *   numbering in tools/gen_mcubes_table.py).  out_len >= 256 * UFR_MC_TABLE_ROW; returns UFR_MC_TABLE_ROW.        */
+#define UFR_MC_TABLE_ROW 16
+size_t ufr_marching_cubes_workspace_bytes(const int32_t* dim);
+int ufr_marching_cubes_count(const float* vol, const int32_t* dim, float level, void* workspace, size_t workspace_bytes,
+                             int32_t* counts_host, ufr_stream stream);
+int ufr_marching_cubes_emit(const float* vol, const int32_t* dim, float level, void* workspace, size_t workspace_bytes,
+                            float* verts, float* normals, int32_t* faces, int32_t n_verts, int32_t n_faces, ufr_stream stream);
+int ufr_marching_cubes_table(int8_t* out, int32_t out_len);
 
 /* Pixel-wise view weights of the first cascade stage and the weighted aggregate (DepthNet.forward,
  * code1/encoder_utils/fmt/TransMVSNet.py:80-97 with PixelwiseNet :23-41), one pass over the similarity volume:

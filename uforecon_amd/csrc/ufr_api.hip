@@ -13,6 +13,7 @@
 
 #include "bwd_common.h"
 #include "bwd_tape.h"
+#include "mcubes_table.h"
 #include "ufr_internal.h"
 #include "ufr_layout_f16.h"
 
@@ -1252,6 +1253,96 @@ int ufr_tsdf_integrate(float* tsdf, float* weight, float* color, const int32_t* 
   UFR_HIP(launch_tsdf_integrate(tsdf, weight, color, dim, origin, voxel_size, trunc_margin, cam_intr, cam_pose, depth_im,
                                 color_im, im_h, im_w, obs_weight, integrate_color, s));
   return UFR_OK;
+}
+
+// ------------------------------------------------------------------ marching cubes
+namespace {
+struct McWorkspace {   // [tile sums int32 x2 | tile offsets int64 x2 | totals int64 x2 | index volume int32 per voxel]
+  int* tile_counts;
+  long long *tile_off, *totals;
+  int* index;
+  size_t bytes;
+  McWorkspace(void* base, const int32_t* dim) {
+    const size_t tiles = (size_t)mcubes_tiles(dim), n = (size_t)dim[0] * dim[1] * dim[2];
+    char* b = static_cast<char*>(base);
+    size_t off = 0;
+    tile_counts = reinterpret_cast<int*>(b + off);
+    off += align_up(tiles * 2 * sizeof(int));
+    tile_off = reinterpret_cast<long long*>(b + off);
+    off += align_up(tiles * 2 * sizeof(long long));
+    totals = reinterpret_cast<long long*>(b + off);
+    off += align_up(2 * sizeof(long long));
+    index = reinterpret_cast<int*>(b + off);
+    off += align_up(n * sizeof(int));
+    bytes = off;
+  }
+};
+
+int mc_check(const char* who, const float* vol, const int32_t* dim, void* ws, size_t ws_bytes) {
+  UFR_REQUIRE(vol && dim && ws, "%s: null argument", who);
+  UFR_REQUIRE(dim[0] >= 2 && dim[1] >= 2 && dim[2] >= 2, "%s: volume %dx%dx%d (every dim must be >= 2)", who, dim[0], dim[1], dim[2]);
+  UFR_REQUIRE((long long)dim[0] * dim[1] * dim[2] < (1ll << 31), "%s: volume %dx%dx%d has 2^31 voxels or more", who, dim[0], dim[1],
+              dim[2]);
+  const size_t need = McWorkspace(nullptr, dim).bytes;
+  if (ws_bytes < need) return fail(UFR_ERR_WORKSPACE, "%s: workspace %zu bytes, needs %zu", who, ws_bytes, need);
+  return UFR_OK;
+}
+}  // namespace
+
+size_t ufr_marching_cubes_workspace_bytes(const int32_t* dim) {
+  if (!dim || dim[0] < 2 || dim[1] < 2 || dim[2] < 2 || (long long)dim[0] * dim[1] * dim[2] >= (1ll << 31)) return 0;
+  return McWorkspace(nullptr, dim).bytes;
+}
+
+int ufr_marching_cubes_count(const float* vol, const int32_t* dim, float level, void* workspace, size_t workspace_bytes,
+                             int32_t* counts_host, ufr_stream stream) {
+  if (int rc = mc_check("ufr_marching_cubes_count", vol, dim, workspace, workspace_bytes)) return rc;
+  UFR_REQUIRE(counts_host, "ufr_marching_cubes_count: null argument (counts_host)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  McWorkspace w(workspace, dim);
+  {
+    ProfScope p("mcubes_count", s);
+    UFR_HIP(launch_mcubes_count(vol, dim, level, w.tile_counts, s));
+  }
+  {
+    ProfScope p("mcubes_scan", s);
+    UFR_HIP(launch_mcubes_scan(w.tile_counts, mcubes_tiles(dim), w.tile_off, w.totals, s));
+  }
+  long long tot[2] = {0, 0};
+  UFR_HIP(hipMemcpyAsync(tot, w.totals, sizeof(tot), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  UFR_REQUIRE(tot[0] < (1ll << 31) && tot[1] < (1ll << 31), "ufr_marching_cubes_count: %lld vertices, %lld faces: 2^31 or more",
+              tot[0], tot[1]);
+  counts_host[0] = (int32_t)tot[0];
+  counts_host[1] = (int32_t)tot[1];
+  return UFR_OK;
+}
+
+int ufr_marching_cubes_emit(const float* vol, const int32_t* dim, float level, void* workspace, size_t workspace_bytes,
+                            float* verts, float* normals, int32_t* faces, int32_t n_verts, int32_t n_faces, ufr_stream stream) {
+  if (int rc = mc_check("ufr_marching_cubes_emit", vol, dim, workspace, workspace_bytes)) return rc;
+  UFR_REQUIRE(n_verts >= 0 && n_faces >= 0, "ufr_marching_cubes_emit: n_verts %d, n_faces %d", n_verts, n_faces);
+  UFR_REQUIRE((n_verts == 0 || (verts && normals)) && (n_faces == 0 || faces), "ufr_marching_cubes_emit: null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  McWorkspace w(workspace, dim);
+  if (n_verts == 0 && n_faces == 0) return UFR_OK;
+  {
+    ProfScope p("mcubes_verts", s);   // also the index volume the faces need
+    UFR_HIP(launch_mcubes_verts(vol, dim, level, w.tile_off, w.index, verts, normals, n_verts, s));
+  }
+  if (n_faces > 0) {
+    ProfScope p("mcubes_faces", s);
+    UFR_HIP(launch_mcubes_faces(vol, dim, level, w.tile_off, w.index, faces, n_faces, s));
+  }
+  return UFR_OK;
+}
+
+int ufr_marching_cubes_table(int8_t* out, int32_t out_len) {
+  static_assert(sizeof(kMcTable[0]) == UFR_MC_TABLE_ROW, "mcubes_table.h and ufr.h disagree on the row length");
+  UFR_REQUIRE(out, "ufr_marching_cubes_table: null argument");
+  UFR_REQUIRE(out_len >= 256 * UFR_MC_TABLE_ROW, "ufr_marching_cubes_table: out_len %d < %d", out_len, 256 * UFR_MC_TABLE_ROW);
+  memcpy(out, kMcTable, sizeof(kMcTable));
+  return UFR_MC_TABLE_ROW;
 }
 
 int ufr_pixelwise_view_weights(const float* similarity, const float* params, float* view_weights, float* aggregated, int32_t NS,

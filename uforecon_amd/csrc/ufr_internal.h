@@ -133,6 +133,14 @@ hipError_t launch_tsdf_integrate(float* tsdf, float* weight, float* color, const
                                  float voxel_size, float trunc_margin, const float* K, const float* P,
                                  const float* depth_im, const float* color_im, int im_h, int im_w, float obs_weight,
                                  int integrate_color, hipStream_t s);
+// mcubes.hip: marching cubes (count -> scan -> verts -> faces; see the file header)
+int mcubes_tiles(const int* dim);
+hipError_t launch_mcubes_count(const float* vol, const int* dim, float level, int* tile_counts, hipStream_t s);
+hipError_t launch_mcubes_scan(const int* tile_counts, int n_tiles, long long* tile_off, long long* totals, hipStream_t s);
+hipError_t launch_mcubes_verts(const float* vol, const int* dim, float level, const long long* tile_off, int* index,
+                               float* verts, float* normals, long long n_verts, hipStream_t s);
+hipError_t launch_mcubes_faces(const float* vol, const int* dim, float level, const long long* tile_off, const int* index,
+                               int* faces, long long n_faces, hipStream_t s);
 // conv2d.hip: the plain 2-D convolutions of FeatureNet on channel-last tensors, epilogue fused (see the file header)
 struct Conv2dArgs {
   const float* in;      // [B][H][W][CIN] (the stem: planar [B][3][H][W])

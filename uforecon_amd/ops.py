@@ -722,6 +722,49 @@ def profile_read() -> dict:
     return {names[i].decode(): dict(ms=float(ms[i]), launches=int(launches[i])) for i in range(n)}
 
 
+def marching_cubes(vol: torch.Tensor, level: float = 0.0):
+    """Marching cubes on the device (ufr_marching_cubes_*): ``vol`` a CUDA fp32 contiguous (X,Y,Z) volume, z fastest (each
+    dim >= 2).  Returns device tensors on the current stream: ``verts`` (V,3) fp32 in voxel-index coordinates, ``faces``
+    (F,3) int32, ``normals`` (V,3) fp32 (+grad f, unit length), in the order include/ufr.h fixes.  One host
+    synchronisation (the counts size the outputs).  A volume without a crossing of ``level`` gives empty (0,3) tensors
+    (scikit-image raises there instead)."""
+    if vol.dim() != 3:
+        raise UfrError(f"marching_cubes: expected a 3-D volume, got shape {tuple(vol.shape)}")
+    lib = _lib.load()
+    dim = (C.c_int32 * 3)(*[int(d) for d in vol.shape])
+    nbytes = lib.ufr_marching_cubes_workspace_bytes(dim)
+    if nbytes == 0:
+        raise UfrError(f"marching_cubes: volume {tuple(vol.shape)} unsupported (every dim >= 2, fewer than 2^31 voxels)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+    counts = (C.c_int32 * 2)()
+    p = _dev(vol, "vol")
+    _lib.check(lib.ufr_marching_cubes_count(p, dim, float(level), ws.data_ptr(), nbytes, counts, _stream()),
+               "ufr_marching_cubes_count")
+    V, F = int(counts[0]), int(counts[1])
+    verts = torch.empty((V, 3), dtype=torch.float32, device=vol.device)
+    normals = torch.empty((V, 3), dtype=torch.float32, device=vol.device)
+    faces = torch.empty((F, 3), dtype=torch.int32, device=vol.device)
+    _lib.check(lib.ufr_marching_cubes_emit(p, dim, float(level), ws.data_ptr(), nbytes, verts.data_ptr() if V else None,
+                                           normals.data_ptr() if V else None, faces.data_ptr() if F else None, V, F,
+                                           _stream()), "ufr_marching_cubes_emit")
+    return verts, faces, normals
+
+
+def marching_cubes_table():
+    """The kernel's 256-case triangle table as a (256, UFR_MC_TABLE_ROW) int8 array (host only; no GPU needed)."""
+    import numpy as np
+
+    lib = _lib.load()
+    out = np.empty(256 * MC_TABLE_ROW, np.int8)
+    row = lib.ufr_marching_cubes_table(out.ctypes.data_as(C.POINTER(C.c_int8)), out.size)
+    if row != MC_TABLE_ROW:
+        _lib.check(row if row < 0 else -1, "ufr_marching_cubes_table")
+    return out.reshape(256, MC_TABLE_ROW)
+
+
+MC_TABLE_ROW = 16   # UFR_MC_TABLE_ROW of include/ufr.h
+
+
 CONV3D_S1, CONV3D_S2, CONV3D_T2 = 0, 1, 2
 
 
