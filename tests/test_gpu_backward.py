@@ -15,6 +15,7 @@ import os
 import pytest
 import torch
 
+import bwd_ref
 from helpers import CASES, VOLUME_KEYS, case_inputs, golden_volume_grad, grad_rel_err, load_weights, rel_err
 from oracle import ufo_oracle as O
 from uforecon_amd import model as M
@@ -118,7 +119,7 @@ def test_aggregate_bwd_matches_oracle_autograd(name):
     assert torch.equal(d_pv2, d_pv)
 
 
-def _aggregate_bwd_against_autograd(NV, SN, P, f64=False):
+def _aggregate_bwd_against_autograd(NV, SN, P, f64=False, envelope=None):
     from uforecon_amd.scene import make_frame
 
     W = ops.PackedWeights({k: v.to(DEV) for k, v in P.items()})
@@ -150,19 +151,28 @@ def _aggregate_bwd_against_autograd(NV, SN, P, f64=False):
             continue
         worst[k] = grad_rel_err(grads.grad(k), Pg[k].grad)
     worst["d_pv"] = grad_rel_err(d_pv, xr.grad[:, :, 32:72].sum(1))
+    if envelope is not None:    # the float64 yardstick with the ReLU-flip envelope (tests/bwd_ref.py): excess per tensor
+        e = bwd_ref.grad_envelope(P, x.cpu(), rgbm.cpu()[..., :3], rgbm.cpu()[..., 3], dirs.cpu()[..., :3], RN, SN, co_rad, co_srdf)
+        g = {k: grads.grad(k) for k in bwd_ref.VIEW_KEYS + bwd_ref.RAY_KEYS}
+        g["d_pv"] = d_pv
+        envelope.update(e.excesses(g))
+        envelope["beyond"] = e.beyond(g)
+        print(f"NV {NV} SN {SN}: |A| = {len(e.ambiguous)}, worst excess {max(v for k, v in envelope.items() if k != 'beyond'):.2e}")
     return worst
 
 
-@pytest.mark.parametrize("NV,SN", [(2, 48), (5, 96), (7, 32)])
+@pytest.mark.parametrize("NV,SN", [(2, 48), (5, 96), (6, 80), (7, 32)])
 def test_aggregate_bwd_other_view_counts_and_lengths(NV, SN):
     """The backward tiles hold 16 // (NV+1) points per 16 token columns and the ray kernel walks SN / 16 tiles per sweep:
     view counts with idle columns and sample totals that are not a power of two, against autograd through the oracle."""
-    worst = _aggregate_bwd_against_autograd(NV, SN, load_weights())
-    # a ReLU unit within rounding of zero may flip between two fp32 evaluations (DESIGN 3.6): allow it on a few tensors.
+    env = {}
+    worst = _aggregate_bwd_against_autograd(NV, SN, load_weights(), envelope=env)
     # The median sits at the arithmetic's own floor: since round 4 the data-gradient chain and the weight-gradient
     # contraction run as three bf16 plane products (16 significand bits per operand: ~1e-5 per tensor; GRAD_TOL is 1e-3)
     assert sorted(worst.values())[len(worst) // 2] < 5e-5, worst
-    assert max(worst.values()) < 2e-2, worst
+    # every tensor: within EPS of float64 autograd outside the envelope of the ReLU units within rounding of zero (a flip
+    # between two fp32 evaluations, DESIGN 3.6, is accounted for exactly instead of by a looser bound)
+    assert not env["beyond"], env
 
 
 def test_aggregate_bwd_with_checkpoint_like_weights():
@@ -179,10 +189,13 @@ def test_aggregate_bwd_with_checkpoint_like_weights():
             P[k] *= 8.0
         elif "norm" in k and k.endswith("weight"):
             P[k] = 0.5 + 9.5 * torch.rand(P[k].shape, generator=g)
-    worst = _aggregate_bwd_against_autograd(3, 64, P, f64=True)
+    env = {}
+    worst = _aggregate_bwd_against_autograd(3, 64, P, f64=True, envelope=env)
     print({k.split(".")[-3] + "." + k.split(".")[-2] if k.count(".") > 2 else k: f"{v:.1e}" for k, v in worst.items()})
     assert sorted(worst.values())[len(worst) // 2] < 1e-4, worst
     assert max(worst.values()) < 1e-3, worst
+    # outside the envelope of the ReLU units within rounding of zero (tests/bwd_ref.py): measured worst 8.2e-5
+    assert not env["beyond"], env
 
 
 def test_project_gather_bwd_matches_oracle_autograd():
