@@ -1,5 +1,5 @@
 """Is the view transformer power-limited?  Loops ufr_aggregate for ~10 s per setting while a thread samples rocm-smi
-(package power, sclk); prints kernel time next to the samples.  UFR_LIB / UFR_VT_PAD_LDS select the variant."""
+(package power, sclk); prints kernel time next to the samples.  UFR_LIB selects the variant."""
 import os, subprocess, sys, threading, time
 import numpy as np
 import torch
@@ -51,7 +51,7 @@ def loop(seconds, what):
     print(f"{what}: view {vt:.3f} ms ray {rt:.3f} ms over {n} launches; samples: {[(a[1], a[2]) for a in s[-6:]]}", flush=True)
 time.sleep(3)
 print("idle samples:", [(a[1], a[2]) for a in samples[-3:]], flush=True)
-loop(6, os.environ.get("UFR_LIB", "default").split("/")[-1] + " pad=" + os.environ.get("UFR_VT_PAD_LDS", "0"))
+loop(6, os.environ.get("UFR_LIB", "default").split("/")[-1])
 if os.environ.get("ZERO_TEST"):
     xs = x.clone()
     x.zero_()

@@ -23,32 +23,14 @@
 
 namespace ufr {
 
-#ifndef UFR_BWD_THREADS
-#define UFR_BWD_THREADS 256
-#endif
-constexpr int kBwdThreads = UFR_BWD_THREADS;
+constexpr int kBwdThreads = 256;
 constexpr int kBwdWaves = kBwdThreads / 64;
-#ifndef UFR_BWD_TT
-#define UFR_BWD_TT 32
-#endif
-constexpr int kTT = UFR_BWD_TT;   // tokens per tile
+constexpr int kTT = 32;           // tokens per tile
 constexpr int kCT = kTT / 16;     // MFMA column tiles per tile
 constexpr int kLD = kTT + 1;      // LDS row stride (floats)
 static_assert(kTT % 16 == 0 && kBwdThreads % kTT == 0, "tile shape");
 
 struct GradPtrs { float* p[P_COUNT]; };
-
-// development build (-DUFR_BWD_TIMING): cycles between consecutive barriers of workgroup 0, summed over its tiles
-#ifdef UFR_BWD_TIMING
-#define UFR_BWD_PHASE(arr, i)                                          \
-  if (blockIdx.x == 0 && threadIdx.x == 0) {                           \
-    const unsigned long long t_now = __builtin_readcyclecounter();     \
-    arr[i] += t_now - t_prev;                                          \
-    t_prev = t_now;                                                    \
-  }
-#else
-#define UFR_BWD_PHASE(arr, i)
-#endif
 
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
 

@@ -17,7 +17,7 @@
 
 namespace ufr {
 
-constexpr int kBlockCols = 2;                      // column tiles per block (= UFR_VT_C of the forward kernel)
+constexpr int kBlockCols = 2;                      // column tiles per block (= kVtC of the forward kernel)
 constexpr int kTileFloats = 256;                   // 64 lanes x float4
 
 // 16-bit mode (UFR_PRECISION_16BIT): the tiles that only feed the weight-gradient contraction -- which rounds its operands

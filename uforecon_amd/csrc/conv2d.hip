@@ -19,10 +19,6 @@
 #include "ufr_device.h"
 #include "ufr_internal.h"
 
-#ifndef UFR_C2_ROLLED
-#define UFR_C2_ROLLED 1     // the tap loop stays a loop: unrolled, the 32-channel 3x3 kernel held 302 registers (one wave per SIMD), 9 % slower
-#endif
-
 namespace ufr {
 
 namespace {
@@ -136,9 +132,8 @@ __global__ void __launch_bounds__(256) conv2d_mfma_kernel(Conv2dArgs a) {
     };
     TapVals<CPG> va[T], vb[T];
     load(0, va);
-#if UFR_C2_ROLLED
+    // the tap loop stays a loop: unrolled, the 32-channel 3x3 kernel held 302 registers (one wave per SIMD), 9 % slower
 #pragma unroll 1
-#endif
     for (int k = 0; k < KK; k += 2) {
       if (k + 1 < KK) load(k + 1, vb);
       contract(k, va);

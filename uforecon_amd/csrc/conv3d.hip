@@ -18,10 +18,6 @@
 #include "ufr_internal.h"
 #include "weight_stream.h"   // static_for
 
-#ifndef UFR_C3_FOLD
-#define UFR_C3_FOLD 1
-#endif
-
 namespace ufr {
 
 namespace {
@@ -388,7 +384,6 @@ hipError_t launch_conv3d(const float* in, const float* weight, const float* weig
   else if (mode == kConvS2) { a.Do = (D + 1) / 2; a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2; }   // k3 p1 s2: floor((n-1)/2)+1
   else { a.Do = 2 * D; a.Ho = 2 * H; a.Wo = 2 * W; }                                           // k3 p1 s2 output_padding 1
   const int ct = cout + cout2;
-#ifndef UFR_CONV3D_VALU_ONLY
   // whole 16-channel blocks on both sides, channel-last output, one head: the matrix-core kernel
   if (!ncdhw && cout2 == 0 && weight2 == nullptr && out_absmax == nullptr) {
 #define UFR_MFMA_CASE(CI, CO, MO) if (cin == CI && cout == CO && mode == MO) return launch_conv_mfma_t<CI, CO, MO>(a, s);
@@ -402,7 +397,6 @@ hipError_t launch_conv3d(const float* in, const float* weight, const float* weig
     UFR_MFMA_CASE(32, 16, kConvS2) UFR_MFMA_CASE(64, 32, kConvS2)      // = data gradients of conv9 / conv7
 #undef UFR_MFMA_CASE
   }
-#endif
 #define UFR_CONV_CASE(CI, CO, MO, RR) \
   if (cin == CI && ct <= CO && ct > CO - 4 && mode == MO) return launch_conv_t<CI, CO, MO, RR>(a, s);
   // the layers of CostRegNet / CostRegNetWeight with base_channels = 8 (module.py:469-543)
@@ -414,11 +408,9 @@ hipError_t launch_conv3d(const float* in, const float* weight, const float* weig
   UFR_CONV_CASE(32, 64, kConvS2, 1)     // conv5
   UFR_CONV_CASE(64, 64, kConvS1, 1)     // conv6
   UFR_CONV_CASE(64, 32, kDeconvS2, 2)   // conv7
-#if UFR_C3_FOLD
   // (transposed layers that write the two finest grids: the x parity folded into the channel axis, see conv3d_kernel)
   if (cin == 32 && ct == 16 && mode == kDeconvS2 && !a.ncdhw && a.Wo % 2 == 0) return launch_conv_t<32, 32, kDeconvS2F, 1>(a, s);
   if (cin == 16 && ct == 8 && mode == kDeconvS2 && !a.ncdhw && a.Wo % 2 == 0) return launch_conv_t<16, 16, kDeconvS2F, 2>(a, s);
-#endif
   UFR_CONV_CASE(32, 16, kDeconvS2, 2)   // conv9
   UFR_CONV_CASE(16, 8, kDeconvS2, 2)    // conv11
   UFR_CONV_CASE(8, 4, kConvS1, 2)       // prob (1 channel)
@@ -897,24 +889,11 @@ __global__ void __launch_bounds__(256) conv3d_wgrad_mfma8_kernel(WgradArgs a) {
   }
 }
 
-#ifndef UFR_CONV3D_WGRAD_MFMA
-#define UFR_CONV3D_WGRAD_MFMA 1
-#endif
-#ifndef UFR_WG_NT_SMALL
-#define UFR_WG_NT_SMALL 9
-#endif
-#ifndef UFR_WG_NT_MID
-#define UFR_WG_NT_MID 3
-#endif
-#ifndef UFR_WG_WAVES
-#define UFR_WG_WAVES 4096       // waves in flight per launch: 4 per SIMD
-#endif
-#ifndef UFR_WG_WAVES8
-#define UFR_WG_WAVES8 3072      // ... 3 per SIMD at the 8-channel kernel's ~150 registers
-#endif
+constexpr int kWgNtSmall = 9, kWgNtMid = 3;   // taps per pass of the matrix-core kernel (small / mid channel products)
+constexpr int kWgWaves = 4096;    // waves in flight per launch: 4 per SIMD
+constexpr int kWgWaves8 = 3072;   // ... 3 per SIMD at the 8-channel kernel's ~150 registers
 template <int CA, int CB, int S>
 hipError_t launch_wgrad_t(WgradArgs a, hipStream_t s) {
-#if UFR_CONV3D_WGRAD_MFMA
   // (the matrix-core kernels address both tensors with byte offsets below kWgOutRow)
   const bool small = a.n_p * CA * 4 < (1ll << 30) && (long long)a.B * a.Dq * a.Hq * a.Wq * CB * 4 < (1ll << 30);
   constexpr bool kPair = CA % 16 == 0 && CB % 16 == 0, kEight = CB == 8 && (CA == 8 || CA == 16);
@@ -926,24 +905,23 @@ hipError_t launch_wgrad_t(WgradArgs a, hipStream_t s) {
       // units: whole rows, halved until there are a few per wave slot (never below 32 voxels = 8 steps)
       const long long rows = (long long)a.B * a.Dp * a.Hp;
       a.seg = (a.Wp + 3) / 4 * 4;
-      while (rows * ((a.Wp + a.seg - 1) / a.seg) < 4 * UFR_WG_WAVES && a.seg > 32) a.seg = (a.seg / 2 + 3) / 4 * 4;
+      while (rows * ((a.Wp + a.seg - 1) / a.seg) < 4 * kWgWaves && a.seg > 32) a.seg = (a.seg / 2 + 3) / 4 * 4;
       a.nseg = (a.Wp + a.seg - 1) / a.seg;
       const long long units = rows * a.nseg;
       if constexpr (kPair) {
-        constexpr int NT = CA * CB <= 256 ? UFR_WG_NT_SMALL : CA * CB <= 1024 ? UFR_WG_NT_MID : 1;   // 4 NT (CA/16) (CB/16) accumulator registers
-        long long blocks = UFR_WG_WAVES / 4 * NT / 27;
+        constexpr int NT = CA * CB <= 256 ? kWgNtSmall : CA * CB <= 1024 ? kWgNtMid : 1;   // 4 NT (CA/16) (CB/16) accumulator registers
+        long long blocks = kWgWaves / 4 * NT / 27;
         if (blocks < 16) blocks = 16;
         if (blocks > (units + 3) / 4) blocks = (units + 3) / 4;
         hipLaunchKernelGGL((conv3d_wgrad_mfma_kernel<CA, CB, S, NT>), dim3((unsigned)blocks, 27 / NT), dim3(256), 0, s, a);
       } else {
-        long long blocks = UFR_WG_WAVES8 / 4;       // exactly the resident waves: the units are dealt round-robin
+        long long blocks = kWgWaves8 / 4;       // exactly the resident waves: the units are dealt round-robin
         if (blocks > (units + 3) / 4) blocks = (units + 3) / 4;
         hipLaunchKernelGGL((conv3d_wgrad_mfma8_kernel<CA, S>), dim3((unsigned)blocks), dim3(256), 0, s, a);
       }
       return hipGetLastError();
     }
   }
-#endif
   if constexpr (CB <= 8 && CA * CB <= 128) {
     // CAG coarse-side channels per thread (CAG CB <= 64), the groups on blockIdx.y; NT taps per pass (NT CAG CB <= 192), the
     // passes on blockIdx.z
@@ -990,36 +968,27 @@ hipError_t launch_conv3d_bwd_weight(const float* in, const float* d_out, float* 
   }
   a.n_p = (long long)B * a.Dp * a.Hp * a.Wp;
   if (a.n_p >= (1ll << 31) - 65536 || n_out >= (1ll << 40)) return hipErrorInvalidValue;     // the kernels index voxels with 32 bits
-  hipError_t e = hipErrorInvalidValue;
-#ifndef UFR_CONV3D_WGRAD_FP32_ONLY
   // round 6: the 16-bit matrix-core kernels (conv3d_wgrad_planes.hip) where they have the shape; they take the bias gradient
-  // along when TP is d_out (the convolutions)
-  {
-    const bool bias_rides = d_bias != nullptr && mode != kDeconvS2;
-    e = launch_conv3d_wgrad_planes(a.tp, a.tq, a.dw, bias_rides ? d_bias : nullptr, B, a.Dp, a.Hp, a.Wp, a.Dq, a.Hq, a.Wq, ca, cb, S, s);
-    if (e == hipSuccess) {
-      if (!d_bias || bias_rides) return hipSuccess;
-    } else if (e != hipErrorInvalidValue) {
-      return e;
-    }
-  }
-  if (e != hipSuccess) {
-#endif
-  e = hipErrorInvalidValue;
+  // along when TP is d_out (the convolutions).  The fp32 kernels take the shapes they do not have.
+  const bool bias_rides = d_bias != nullptr && mode != kDeconvS2;
+  hipError_t e = launch_conv3d_wgrad_planes(a.tp, a.tq, a.dw, bias_rides ? d_bias : nullptr, B, a.Dp, a.Hp, a.Wp, a.Dq, a.Hq, a.Wq, ca, cb, S, s);
+  if (e == hipSuccess) {
+    if (!d_bias || bias_rides) return hipSuccess;
+  } else if (e != hipErrorInvalidValue) {
+    return e;
+  } else {
 #define UFR_WG_CASE(A_, B_, S_) if (ca == A_ && cb == B_ && S == S_) e = launch_wgrad_t<A_, B_, S_>(a, s);
-  UFR_WG_CASE(8, 1, 1)     // conv0
-  UFR_WG_CASE(16, 8, 2)    // conv1, conv11
-  UFR_WG_CASE(16, 16, 1)   // conv2
-  UFR_WG_CASE(32, 16, 2)   // conv3, conv9
-  UFR_WG_CASE(32, 32, 1)   // conv4
-  UFR_WG_CASE(64, 32, 2)   // conv5, conv7
-  UFR_WG_CASE(64, 64, 1)   // conv6
-  UFR_WG_CASE(8, 8, 1)     // features head
-  UFR_WG_CASE(1, 8, 1)     // weights head
+    UFR_WG_CASE(8, 1, 1)     // conv0
+    UFR_WG_CASE(16, 8, 2)    // conv1, conv11
+    UFR_WG_CASE(16, 16, 1)   // conv2
+    UFR_WG_CASE(32, 16, 2)   // conv3, conv9
+    UFR_WG_CASE(32, 32, 1)   // conv4
+    UFR_WG_CASE(64, 32, 2)   // conv5, conv7
+    UFR_WG_CASE(64, 64, 1)   // conv6
+    UFR_WG_CASE(8, 8, 1)     // features head
+    UFR_WG_CASE(1, 8, 1)     // weights head
 #undef UFR_WG_CASE
-#ifndef UFR_CONV3D_WGRAD_FP32_ONLY
   }
-#endif
   if (e != hipSuccess) return e;
   if (d_bias) {
     const int rows = 16384;    // 64 rows per thread, four loads in flight; ~500 blocks: few same-address atomics

@@ -188,10 +188,6 @@ struct Brick {   // the brick of a workgroup -- output voxels (transposed: INPUT
   static constexpr int plane_bytes = halo * CIN * 2;       // one fp16 plane of the halo
 };
 
-#ifndef UFR_C3P_ABL
-#define UFR_C3P_ABL 0   // development ablations (timing only): 1 = one k-step, 2 = no halo loads, 3 = no stores
-#endif
-
 // Persistent workgroups (two per CU), each walking a contiguous run of bricks with the NEXT brick's halo loads in flight
 // while the current one computes: as one workgroup per brick the phases of a brick -- load round trip, split + LDS write,
 // MFMAs, stores -- ran one after the other and only two bricks per CU overlapped (ablations on the full-resolution 8 -> 8
@@ -257,7 +253,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_planes_kernel(PlanesArgs a) {
       const int hv = tid + 256 * r;
       const int hx = hv % Bk::HX, hy = (hv / Bk::HX) % Bk::HY, hz = hv / (Bk::HX * Bk::HY);
       const int ix = S * x0 + hx - O, iy = S * y0 + hy - O, iz = S * z0 + hz - O;
-      const bool ok = UFR_C3P_ABL != 2 && hv < Bk::halo && ix >= 0 && ix < a.W && iy >= 0 && iy < a.H && iz >= 0 && iz < a.D;
+      const bool ok = hv < Bk::halo && ix >= 0 && ix < a.W && iy >= 0 && iy < a.H && iz >= 0 && iz < a.D;
       const unsigned off = (unsigned)(((iz * a.H + iy) * a.W + ix) * (CIN * 4));
 #pragma unroll
       for (int c8 = 0; c8 < C8; ++c8) {
@@ -270,7 +266,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_planes_kernel(PlanesArgs a) {
 #pragma unroll
     for (int r = 0; r < HR; ++r) {
       const int hv = tid + 256 * r;
-      if (hv < Bk::halo && !(UFR_C3P_ABL == 4 && xv[r][0][0][0] != 12345.f)) {
+      if (hv < Bk::halo) {
 #pragma unroll
         for (int c8 = 0; c8 < C8; ++c8) {
           const f32x4 v0 = xv[r][c8][0], v1 = xv[r][c8][1];
@@ -390,7 +386,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_planes_kernel(PlanesArgs a) {
     // 3 NT MFMAs.  The operands of step s + 2 are requested before the MFMAs of step s are issued (scheduling fences keep
     // that order: left alone, the scheduler sinks every read to its use and the wave pays the LDS latency 56 times a brick
     // -- 0.31 ms for the full-resolution 8 -> 8 layer, a tenth of it in the matrix pipe).
-    constexpr int kSteps = (UFR_C3P_ABL == 1 ? 1 : KS) * VT;
+    constexpr int kSteps = KS * VT;
     f16x8 rb[3][2], ra[3][NTG][2];
     auto issue = [&](auto si) __attribute__((always_inline)) {
       constexpr int st = decltype(si)::value, ks = st / VT, v = st % VT;
@@ -451,7 +447,6 @@ __global__ void __launch_bounds__(256, 2) conv3d_planes_kernel(PlanesArgs a) {
         continue;
       }
       if (ox >= a.Wo || oy >= a.Ho || oz >= a.Do) continue;
-      if (UFR_C3P_ABL == 3 && acc[v][0][0] != 12345.f) continue;
       const size_t sp = ((size_t)oz * a.Ho + oy) * a.Wo + ox;
 #pragma unroll
       for (int t = 0; t < NTG; ++t) {

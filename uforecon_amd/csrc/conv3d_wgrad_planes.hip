@@ -109,9 +109,6 @@ struct WgCfg {
   static constexpr int lds = 2 * plane_bytes > red_bytes ? 2 * plane_bytes : red_bytes;
 };
 
-#ifndef UFR_WGP_ABL
-#define UFR_WGP_ABL 0   // development ablations (timing only): 1 = no slot loop, 2 = no halo staging, 3 = no flush
-#endif
 template <int CA, int CB, int S, int NA, int NTAP, bool HEADS = false>
 __global__ void __launch_bounds__(256, 2) conv3d_wgrad_planes_kernel(WgPlanesArgs a) {
   static_assert(!HEADS || (CA == 8 && NA == 1), "the two heads: 8 + 1 rows of one tile");
@@ -260,11 +257,10 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_planes_kernel(WgPlanesArg
     // ---- stage the TQ halo of this block's 16 (8) channels: (voxel, 4-channel group) per thread, two bf16 planes.  When a
     // halo is one round of eight loads per thread (the full-resolution 8-channel layers), the NEXT brick's loads are
     // in flight while this one computes (pre[]); else it is staged in place, round by round.
-    if constexpr (UFR_WGP_ABL == 2) { if (k == k_begin) stage_direct(k); }
-    else if constexpr (!kPre) stage_direct(k);
+    if constexpr (!kPre) stage_direct(k);
     else if (k == k_begin) { pre_load(k); pre_store(); }
     __syncthreads();
-    if constexpr (kPre && UFR_WGP_ABL != 2) {
+    if constexpr (kPre) {
       if (k + 1 < k_end) pre_load(k + 1);
     }
     int kk = k;
@@ -343,7 +339,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_planes_kernel(WgPlanesArg
       read_slot(std::integral_constant<int, 0>{});
       if constexpr (NSLOT > 1) read_slot(std::integral_constant<int, 1>{});
       trs[0] = frag_transpose(rd[0][0], rd[0][1], rd[0][2], rd[0][3], sel);
-      static_for<(UFR_WGP_ABL == 1 ? 1 : NSLOT)>([&](auto si) __attribute__((always_inline)) {
+      static_for<NSLOT>([&](auto si) __attribute__((always_inline)) {
         constexpr int s = decltype(si)::value;
         if constexpr (s + 2 < NSLOT) read_slot(std::integral_constant<int, s + 2>{});
         __builtin_amdgcn_sched_barrier(0);
@@ -357,7 +353,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_planes_kernel(WgPlanesArg
       });
     });
     __syncthreads();     // every wave is done with this brick's planes
-    if constexpr (kPre && UFR_WGP_ABL != 2) {
+    if constexpr (kPre) {
       if (k + 1 < k_end) pre_store();
     }
   }
@@ -391,7 +387,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_planes_kernel(WgPlanesArg
   __syncthreads();
   float* const stage = reinterpret_cast<float*>(smem);                  // [NA 16 rows][CBL][NTAP] (+ bias [NA 16])
   constexpr int kRowF = CBL * NTAP, kStageF = NA * 16 * kRowF;
-  if (wave == 0 && !(UFR_WGP_ABL == 3 && acc[0][0][0] != 12345.f)) {
+  if (wave == 0) {
 #pragma unroll
     for (int t = 0; t < NA; ++t) {
 #pragma unroll
@@ -411,7 +407,6 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_planes_kernel(WgPlanesArg
     }
   }
   __syncthreads();
-  if (UFR_WGP_ABL == 3 && acc[0][0][0] != 12345.f) return;
   for (int e = tid; e < kStageF; e += 256) {
     const int row = e / kRowF, rem = e - row * kRowF, bl = rem / NTAP, tl = rem - bl * NTAP;
     const int ach = a0 + row, bch = b0 + bl, tap = tap0 + tl;

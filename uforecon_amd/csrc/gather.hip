@@ -17,33 +17,9 @@
 
 namespace ufr {
 
-// out = fma(v_se,se, fma(v_sw,sw, fma(v_ne,ne, v_nw*nw))) per channel; masked corners read as zero
-__device__ __forceinline__ f32x4 lerp_tap4(const float* __restrict__ base, int stride, const Tap2& t, int c) {
-  f32x4 v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)   // texel index < 2^24, row stride < 2^24: one 24-bit multiply
-    v[k] = t.o[k] >= 0 ? ld4(base + (__umul24((unsigned)t.o[k], (unsigned)stride) + (unsigned)c)) : splat4(0.f);
-  f32x4 acc;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float a = mul_rn(v[0][e], t.w[0]);
-    a = fmaf(v[1][e], t.w[1], a);
-    a = fmaf(v[2][e], t.w[2], a);
-    acc[e] = fmaf(v[3][e], t.w[3], a);
-  }
-  return acc;
-}
-
-#ifndef UFR_GATHER_PAIR
-#define UFR_GATHER_PAIR 0       // 1: frustum lookups shared by lane pairs (volume_sample.h: sample_volume_pair) -- bit-identical, and
-                                // MEASURED SLOWER (gather 0.467 vs 0.458 ms per 524 288 points, frame 123.5 vs 121.5 ms): the DPP adds and the
-                                // doubled chain cost more than the halved line accesses save.  Kept as the A/B.
-#endif
-#ifndef UFR_GATHER_BUFFER
-#define UFR_GATHER_BUFFER 1     // taps through bounded buffer loads (ufr_device.h); 0 = the conditional global loads (A/B)
-#endif
-// the same through a bounded descriptor: texel t.o[k] of the map that starts at byte `base` of the descriptor, channels from
-// byte c4; masked corners (t.o[k] < 0) read zeros from kBufOut -- all four loads in flight at once
+// out = fma(v_se,se, fma(v_sw,sw, fma(v_ne,ne, v_nw*nw))) per channel through a bounded descriptor (ufr_device.h): texel
+// t.o[k] of the map that starts at byte `base` of the descriptor, channels from byte c4; masked corners (t.o[k] < 0) read
+// zeros from kBufOut -- all four loads in flight at once
 __device__ __forceinline__ f32x4 lerp_tap4_buf(__amdgpu_buffer_rsrc_t r, unsigned base, int stride_bytes, const Tap2& t, unsigned c4) {
   f32x4 v[4];
 #pragma unroll
@@ -190,12 +166,8 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
   // XCD-aware block -> point-group map: workgroups are dealt round-robin to the 8 XCDs (private L2 each), so
   // giving XCD x the x-th contiguous eighth of the launch keeps the texels that neighbouring rays share in ONE L2
   // instead of eight
-#ifndef UFR_GATHER_NO_XCD_MAP
   const int nb8 = (int)(gridDim.x / 8) * 8;
   const int blk = (int)blockIdx.x < nb8 ? (int)(blockIdx.x % 8) * (nb8 / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-#else
-  const int blk = blockIdx.x;
-#endif
   const int pidx = blk * 64 + p;
   const bool active = pidx < P;
   const int pc = active ? pidx : P - 1;
@@ -231,26 +203,16 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
     put_tap(sh_tapF + (v * 64 + p) * 8, taps_zeros(unnorm2d_nac(x, f.w), unnorm2d_nac(y, f.h), f.w, f.h));
     put_tap(sh_tapM + (v * 64 + p) * 8, taps_border(unnorm2d_ac(x, f.w), unnorm2d_ac(y, f.h), f.w, f.h));
     Tap2 tf = taps_zeros(unnorm2d_nac(x, f.W), unnorm2d_nac(y, f.H), f.W, f.H);
-#if UFR_GATHER_BUFFER
     const unsigned img_px = (unsigned)(f.H * f.W);
     f32x4 c4 = lerp_tap4_buf(buf_rsrc(f.rgb + (size_t)vu * img_px * 4, img_px * 16u), 0u, 16, tf, 0u);
-#else
-    f32x4 c4 = lerp_tap4(f.rgb + (size_t)v * f.H * f.W * 4, 4, tf, 0);
-#endif
     const float inb = (x <= 1.f && x >= -1.f && y <= 1.f && y >= -1.f) ? 1.f : 0.f;  // inclusive mask
     c4[3] = inb * mask_z;                                                             // ray_transformer.py:251-252
     if (active) st4(rgb_out + ((size_t)pidx * NV + v) * 4, c4);
     // MVS depth guide + positional encoding (ray_transformer.py:229-247, 29-73)
     float dv[4];
-#if UFR_GATHER_BUFFER
     const __amdgpu_buffer_rsrc_t rdepth = buf_rsrc(f.depth + (size_t)vu * img_px, img_px * 4u);
 #pragma unroll
     for (int k = 0; k < 4; ++k) dv[k] = buf_ld1(rdepth, tf.o[k] >= 0 ? (unsigned)tf.o[k] * 4u : kBufOut);
-#else
-    const float* dmap = f.depth + (size_t)v * f.H * f.W;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dv[k] = tf.o[k] >= 0 ? dmap[tf.o[k]] : 0.f;
-#endif
     const float dm = fmaf(dv[3], tf.w[3], fmaf(dv[2], tf.w[2], fmaf(dv[1], tf.w[1], mul_rn(dv[0], tf.w[0]))));
     const float* R = f.w2c_z[v];
     float zc = fmaf(R[2], pz, fmaf(R[1], py, mul_rn(R[0], px))) + R[3];
@@ -281,35 +243,22 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
   // ---- cooperative 32-channel gathers: lane group of 8 = one footprint, lane c8 = channels 4*c8..4*c8+3
   const int c8 = threadIdx.x & 7, grp = threadIdx.x >> 3;
   constexpr int n_grp = 64 * NV / 8;
-#if UFR_GATHER_BUFFER
   // one descriptor over all views' maps (the item's view differs per lane group): [NV][h][w][32] and [NV][h][w][match_ch]
   const unsigned map_px = (unsigned)(f.h * f.w);
   const __amdgpu_buffer_rsrc_t rfeat = buf_rsrc(f.feat, (unsigned)NV * map_px * 128u);
   const __amdgpu_buffer_rsrc_t rmatch = buf_rsrc(f.match, (unsigned)NV * map_px * (unsigned)f.match_ch * 4u);
-#endif
   // image features of (point, view) -> token columns 0..31 (ray_transformer.py:222-226)
-#ifdef UFR_GABL_NOCOOP  // ablation build: no 32-channel gathers (timing only)
-  if (false)
-#endif
   for (int item = grp; item < 64 * NV; item += n_grp) {
     const int ip = item / NV, iv = item - ip * NV;
     const int ipidx = blk * 64 + ip;
     if (ipidx < P) {
       const Tap2 t = get_tap(sh_tapF + (iv * 64 + ip) * 8);
-#if UFR_GATHER_BUFFER
       st4(x_tokens + ((size_t)ipidx * NV + iv) * row_cols + 4 * c8,
           lerp_tap4_buf(rfeat, (unsigned)iv * map_px * 128u, 128, t, 16u * c8));
-#else
-      st4(x_tokens + ((size_t)ipidx * NV + iv) * row_cols + 4 * c8,
-          lerp_tap4(f.feat + (size_t)iv * f.h * f.w * 32, 32, t, 4 * c8));
-#endif
     }
   }
   // pairwise similarity (model.py:271-283): pair q = (a, b), sides (view a, chunk b) / (view b+1, chunk a);
   // lane c8 = channel group gi of model.py:278-280
-#ifdef UFR_GABL_NOCOOP
-  if (false)
-#endif
   if (!sim8_in)
   for (int item = grp; item < 64 * npair; item += n_grp) {
     const int ip = item / npair, q = item - ip * npair;
@@ -318,16 +267,9 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
     const int b = a + rem;
     const int va = a, ca = b, vb = b + 1, cb = a;
     const Tap2 ta = get_tap(sh_tapM + (va * 64 + ip) * 8), tb = get_tap(sh_tapM + (vb * 64 + ip) * 8);
-    const float* ba = f.match + (size_t)va * f.h * f.w * f.match_ch + 32 * ca;
-    const float* bb = f.match + (size_t)vb * f.h * f.w * f.match_ch + 32 * cb;
-#if UFR_GATHER_BUFFER
     const unsigned mrow = (unsigned)f.match_ch * 4u;
     f32x4 fa = lerp_tap4_buf(rmatch, (unsigned)va * map_px * mrow + 128u * ca, (int)mrow, ta, 16u * c8);
     f32x4 fb = lerp_tap4_buf(rmatch, (unsigned)vb * map_px * mrow + 128u * cb, (int)mrow, tb, 16u * c8);
-#else
-    f32x4 fa = lerp_tap4(ba, f.match_ch, ta, 4 * c8);
-    f32x4 fb = lerp_tap4(bb, f.match_ch, tb, 4 * c8);
-#endif
     float na = fmaxf(sqrtf(fa[0] * fa[0] + fa[1] * fa[1] + fa[2] * fa[2] + fa[3] * fa[3]), 1e-8f);
     float nb = fmaxf(sqrtf(fb[0] * fb[0] + fb[1] * fb[1] + fb[2] * fb[2] + fb[3] * fb[3]), 1e-8f);
     // F.normalize(x) = x / max(|x|, eps) as x * (1 / max(|x|, eps)): two reciprocals instead of eight IEEE divisions
@@ -346,48 +288,17 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
   } else {
     const float zn = ((qz - f.vol_near) / (f.vol_far - f.vol_near)) * 2.f - 1.f;  // camera.py:400-401
     float fl[24], wl = 0.f;
-#if UFR_GATHER_PAIR && UFR_GATHER_BUFFER && !defined(UFR_GABL_NOVOL)
-    // lanes 2q, 2q + 1 (two consecutive samples of a ray, the same view) share every lookup: first the even lane's, then the
-    // odd lane's, per stage -- the owner loads the x0 side and keeps the result (volume_sample.h: sample_volume_pair)
-    {
-      const int odd = threadIdx.x & 1;
-      const float xo = pair_swap(x), yo = pair_swap(y), zo = pair_swap(zn);
-#pragma unroll
-      for (int s = 0; s < UFR_NUM_STAGES; ++s) {
-        const unsigned vox = (unsigned)(f.vD[s] * f.vH[s] * f.vW[s]);
-        const __amdgpu_buffer_rsrc_t rv = buf_rsrc(f.vol[s] + (size_t)vu * vox * kVolCh, vox * (unsigned)(kVolCh * 4));
-        float ev[9], od[9];
-        // the even lane's lookup: the even lane is the owner (side 0), the odd lane helps with ITS partner's coordinates
-        sample_volume_pair(rv, f.vD[s], f.vH[s], f.vW[s], odd ? xo : x, odd ? yo : y, odd ? zo : zn, odd, ev);
-        // the odd lane's lookup
-        sample_volume_pair(rv, f.vD[s], f.vH[s], f.vW[s], odd ? x : xo, odd ? y : yo, odd ? zn : zo, odd ^ 1, od);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) fl[8 * s + c] = odd ? od[c] : ev[c];
-        const float ws = odd ? od[8] : ev[8];
-        wl = s == 0 ? ws : wl + ws;                                               // :375-378
-      }
-    }
-#else
 #pragma unroll
     for (int s = 0; s < UFR_NUM_STAGES; ++s) {
       float fs[8], ws;
-      const float* vol = f.vol[s] + (size_t)v * f.vD[s] * f.vH[s] * f.vW[s] * kVolCh;
-#ifdef UFR_GABL_NOVOL   // ablation build: no frustum taps (timing only)
-      for (int c = 0; c < 8; ++c) fs[c] = x; ws = y;
-#else
-#if UFR_GATHER_BUFFER
+      const float* vol = f.vol[s];   // [NV][D][H][W][kVolCh]
       const unsigned vox = (unsigned)(f.vD[s] * f.vH[s] * f.vW[s]);
-      sample_volume_buf(buf_rsrc(f.vol[s] + (size_t)vu * vox * kVolCh, vox * (unsigned)(kVolCh * 4)), f.vD[s], f.vH[s], f.vW[s], x, y,
-                        zn, fs, ws);
-#else
-      sample_volume(vol, f.vD[s], f.vH[s], f.vW[s], x, y, zn, fs, ws);
-#endif
-#endif
+      sample_volume_buf(buf_rsrc(vol + (size_t)vu * vox * kVolCh, vox * (unsigned)(kVolCh * 4)), f.vD[s], f.vH[s], f.vW[s], x, y, zn,
+                        fs, ws);
 #pragma unroll
       for (int c = 0; c < 8; ++c) fl[8 * s + c] = fs[c];
       wl = s == 0 ? ws : wl + ws;                                                 // :375-378
     }
-#endif
 #pragma unroll
     for (int c = 0; c < 24; ++c) own[c] = fl[c] * wl;                             // features_L * weights_L
     own[24] = wl;

@@ -21,11 +21,9 @@
 #include "volume_sample.h"
 #include "weight_stream.h"   // static_for
 
-#ifndef UFR_GBWD_ROUNDS
-#define UFR_GBWD_ROUNDS 3   // fold aligned groups of 2, 4, 8 lanes (4: also 16, the whole DPP / shuffle row)
-#endif
-
 namespace ufr {
+
+constexpr int kGbwdRounds = 3;   // fold aligned groups of 2, 4, 8 lanes (4: also 16, the whole DPP / shuffle row)
 
 // value of lane + D / lane - D of the same 16-lane row (own value where that lane does not exist): __shfl_down / __shfl_up
 // with width 16, as a DPP row shift -- one VALU instruction; the ds_bpermute the shuffle intrinsics compile to is an LDS
@@ -190,7 +188,7 @@ __global__ void __launch_bounds__(448) gather_bwd_kernel(FrameDev f, VolGrads vg
         //      with the same offset add up through lane shifts and only the surviving lane of each group issues atomics.
 #pragma unroll
         for (int dz = 0; dz < 2; ++dz) {
-          static_for<UFR_GBWD_ROUNDS>([&](auto ri) __attribute__((always_inline)) {
+          static_for<kGbwdRounds>([&](auto ri) __attribute__((always_inline)) {
             constexpr int d = 1 << decltype(ri)::value;
             const int k_dn = row_down<d>(off[dz]);                           // offset of lane + d (groups never leave a row)
             const int k_up = row_up<d>(off[dz]);                             // offset of lane - d

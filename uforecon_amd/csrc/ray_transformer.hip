@@ -23,42 +23,12 @@
 namespace ufr {
 
 // load the ray-transformer input tile: [token-0 feature (80) | order PE (8)] in nat88 layout
-// Column tiles per wave and iteration.  Sweep 1 (K, V and the per-head state) always walks ONE 16-token tile: its two sets of
-// eight head tiles fill the registers.  Sweep 2 (Q, message, merge, MLP, DensityMLP: three quarters of the weight stream)
-// walks UFR_RT_C2 tiles per pass over the weights.  C2 = 2 (a weight fragment read from LDS feeds 6 MFMAs and the stream
-// is fetched half as often per token; the registers come from the per-head state KV_h waiting in LDS between the sweeps,
-// 8 KiB per wave) was built and measured in round 5: bit-identical output, static instructions per two tiles 8 166 ->
-// ~6 900, but 256 registers with 36 spilled and 0.391 vs 0.377 ms per 4096 x 128 launch on the same box -- like the
-// round-2 attempt over both sweeps (0.706 vs 0.641), the ray kernel is not bound by its weight stream.  Kept as a switch.
-#ifndef UFR_RT_C2
-#define UFR_RT_C2 1
-#endif
-constexpr int kRtC2 = UFR_RT_C2;
-// The NEXT tile's token rows are requested at the top of an iteration (24 registers): per-phase cycle counters put the
-// K / V and Q GEMMs -- the phases that open with the row-table lookup and the dependent row loads -- at 57 and 72 cycles
-// per MFMA against 33 for MLP0.
-#ifndef UFR_RT_LOCAL_DEN
-#define UFR_RT_LOCAL_DEN 1   // forward-only build: the ones column in every lane group's padding slot (see the KV accumulation)
-#endif
-#ifndef UFR_RT_PREFETCH
-#define UFR_RT_PREFETCH 0   // measured round 5: 0.378 vs 0.379 ms per 4096 x 128 launch -- the partner wave already covers those loads (as in round 3)
-#endif
-
-// UFR_RT_NT (development): bit 0 / bit 1 = sweep 1 / sweep 2 read the token rows with the non-temporal hint.  The rows are
-// read twice (2.05 x the algorithmic bytes reach the fabric: profiles/r5_pmc.json); measured round 6, see DESIGN.md.
-#ifndef UFR_RT_NT
-#define UFR_RT_NT 0
-#endif
-template <bool NT = false>
 __device__ __forceinline__ void load_ray_tile(const float* __restrict__ token0, const int* __restrict__ tok_row,
                                               const float* __restrict__ order_pe, size_t tok_base, int s_base, int g,
                                               int j, f32x4 (&x)[6]) {
   const float* row = token0 + (tok_row ? (size_t)tok_row[tok_base + j] : tok_base + j) * UFR_TOKEN_DIM;
 #pragma unroll
-  for (int t = 0; t < 5; ++t) {
-    if constexpr (NT) x[t] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + 16 * t + 4 * g));
-    else x[t] = ld4(row + 16 * t + 4 * g);
-  }
+  for (int t = 0; t < 5; ++t) x[t] = ld4(row + 16 * t + 4 * g);
   const float* pe = order_pe + (size_t)(s_base + j) * 8 + 2 * g;  // features 80+2g, 81+2g in registers 0,1
   x[5] = f32x4{pe[0], pe[1], 0.f, 0.f};
 }
@@ -103,12 +73,11 @@ __device__ __forceinline__ void layer_norm88(f32x4 (&tt)[C][6], const WS& ws, in
 }
 
 // 256-thread workgroups = 4 rays (one wave each, one per SIMD), two workgroups per CU; the four waves
-// walk the weight streams B_RT1 / B_RT2 together through LDS (weight_stream_f16.h).
-#ifndef UFR_RT_BLOCK
-#define UFR_RT_BLOCK 256
-#define UFR_RT_MINW 2
-#endif
-constexpr int kRtBlock = UFR_RT_BLOCK;
+// walk the weight streams B_RT1 / B_RT2 together through LDS (weight_stream_f16.h).  Both sweeps walk ONE 16-token
+// column tile per iteration: sweep 1's two sets of eight head tiles fill the registers, and the kernel is not bound by
+// its weight stream (sweep 2 over two tiles per weight pass was slower: DESIGN.md section 7).
+constexpr int kRtBlock = 256;
+constexpr int kRtMinW = 2;   // waves per SIMD the register budget is sized for
 constexpr int kRtWaves = kRtBlock / 64;
 
 #ifdef UFR_PHASE_TIMING  // development build: cycle counts per phase of wave 5 (tools/bench_kernels.py prints them)
@@ -125,9 +94,8 @@ __device__ unsigned long long g_rt_phase[32];
 
 // TAPE: the instantiation the backward launches (bwd_tape.h): the same arithmetic, plus one store per activation tile, the
 // transposed per-head state KV_h^T beside KV_h, and an even number of sweep-2 tiles (blocks of two).
-constexpr int kRtKvLdsBytes = kRtWaves * 8 * 1024;     // the waves' per-head states between the sweeps (C2 > 1)
-template <bool LOWP, bool TAPE = false, int C2 = 1>
-__global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transformer_kernel(const float* __restrict__ packed,
+template <bool LOWP, bool TAPE = false>
+__global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : kRtMinW) ray_transformer_kernel(const float* __restrict__ packed,
                                                                   const float* __restrict__ token0,
                                                                   const int* __restrict__ tok_row,
                                                                   const float* __restrict__ order_pe, int RN, int SN,
@@ -135,8 +103,6 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transfor
                                                                   float* __restrict__ ray_out,
                                                                   int* __restrict__ status, float* __restrict__ tape = nullptr,
                                                                   float* __restrict__ ray_state = nullptr) {
-  static_assert(!TAPE || C2 == 1, "the tape build walks one tile per iteration");
-  constexpr bool kKvLds = C2 > 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto ws = wstream_f16_begin<kRtWaves, LOWP>(packed, smem);
   wstream_f16_prime<B_RT1, kRtWaves>(ws);
@@ -167,9 +133,6 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transfor
   for (int h = 0; h < 8; ++h) KV[h] = splat4(0.f);
 #pragma unroll
   for (int h = 0; h < (TAPE ? 8 : 1); ++h) KVT[h] = splat4(0.f);
-  constexpr bool kPrefetch = UFR_RT_PREFETCH && C2 == 1 && !TAPE;   // (the tape build has no registers to spare)
-  f32x4 xn[6];     // kPrefetch: the next tile's rows, in flight
-  if constexpr (kPrefetch) load_ray_tile(token0, tok_row, order_pe, (size_t)ray * SN, 0, g, j, xn);
   for (int it = 0; it < n_iter; ++it) {
     constexpr int C = 1;
     const bool wrap = it + 1 < n_iter;
@@ -181,14 +144,7 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transfor
       const int tile = it * C + c;
       live[c] = tile < n_tiles;
       const int tl = live[c] ? tile : n_tiles - 1;
-      if constexpr (kPrefetch) {
-#pragma unroll
-        for (int t = 0; t < 6; ++t) x[c][t] = xn[t];
-        const int nx = wrap ? tl + 1 : 0;        // after the last tile: sweep 2's first one
-        load_ray_tile(token0, tok_row, order_pe, (size_t)ray * SN + nx * 16, nx * 16, g, j, xn);
-      } else {
-        load_ray_tile<(UFR_RT_NT & 1) != 0>(token0, tok_row, order_pe, (size_t)ray * SN + tl * 16, tl * 16, g, j, x[c]);
-      }
+      load_ray_tile(token0, tok_row, order_pe, (size_t)ray * SN + tl * 16, tl * 16, g, j, x[c]);
 #pragma unroll
       for (int h = 0; h < 8; ++h) { kt[c][h] = splat4(0.f); vt[c][h] = splat4(0.f); }
     }
@@ -224,7 +180,7 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transfor
     // ones column -> sum of K'.  The forward-only build puts it into EVERY lane group's padding slot (3, 7, 11, 15): the
     // normaliser Q'.sum K' then comes out of the message MFMAs in register 3 of every lane group -- no cross-lane exchange
     // (8 ds_bpermute round trips per tile); the tape build keeps slot 3 alone (the backward reads the state's layout)
-    const float pad_v = (!(UFR_RT_LOCAL_DEN && !TAPE) ? j == 3 : (j & 3) == 3) ? 1.f : 0.f;
+    const float pad_v = (TAPE ? j == 3 : (j & 3) == 3) ? 1.f : 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       float kk[8][4], vv[8][4];
@@ -252,12 +208,8 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transfor
       for (int r = 0; r < 4; ++r) {
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
-#ifdef UFR_ABL_NOKV   // ablation (timing only): no fp32 MFMAs for the per-head KV state
-          KV[h][r] += kk[h][r] * vv[h][r];
-#else
           KV[h] = mfma16(kk[h][r], vv[h][r], KV[h]);
           if constexpr (TAPE) KVT[h] = mfma16(vv[h][r], kk[h][r], KVT[h]);   // [V slot][K slot]: the A operand of d Q' = KV d acc
-#endif
         }
       }
     }
@@ -274,17 +226,9 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transfor
   }
   // ---------------- sweep 2 (slot 0 is free: every wave passed the barrier that opened sweep 1's last chunk)
   wstream_f16_prime<B_RT2, kRtWaves>(ws);
-  // C2 > 1: the per-head state leaves the registers (the wave's own 8 KiB behind the ring and the vector fragments; only
-  // this wave reads it back: program order within the wave is all the ordering it needs)
-  f32x4* const kv_lds = reinterpret_cast<f32x4*>(smem + kF16LdsBytes) + (threadIdx.x >> 6) * 512 + lane;
-  if constexpr (kKvLds) {
-#pragma unroll
-    for (int h = 0; h < 8; ++h) kv_lds[h * 64] = KV[h];
-  }
-  constexpr int C = C2;
-  // TAPE: whole blocks of two tiles (a padding tile is not live); C2 > 1: an odd tile count leaves the last iteration's
-  // second tile empty (masked)
-  const int n_iter2 = TAPE ? n_iter + (n_iter & 1) : (n_tiles + C - 1) / C;
+  constexpr int C = 1;
+  // TAPE: whole blocks of two tiles (a padding tile is not live)
+  const int n_iter2 = TAPE ? n_iter + (n_iter & 1) : n_iter;
   typedef RayTapeLayout<LOWP> TapeL;
   for (int it = 0; it < n_iter2; ++it) {
     const bool wrap = it + 1 < n_iter2;
@@ -300,14 +244,7 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transfor
       const int tile = it * C + c;
       live[c] = tile < n_tiles;
       tbase[c] = (live[c] ? tile : n_tiles - 1) * 16;
-      if constexpr (kPrefetch) {
-#pragma unroll
-        for (int t = 0; t < 6; ++t) x[c][t] = xn[t];
-        const int nx = (tile + 1 < n_tiles ? tile + 1 : n_tiles - 1) * 16;
-        if (wrap) load_ray_tile(token0, tok_row, order_pe, (size_t)ray * SN + nx, nx, g, j, xn);
-      } else {
-        load_ray_tile<(UFR_RT_NT & 2) != 0>(token0, tok_row, order_pe, (size_t)ray * SN + tbase[c], tbase[c], g, j, x[c]);
-      }
+      load_ray_tile(token0, tok_row, order_pe, (size_t)ray * SN + tbase[c], tbase[c], g, j, x[c]);
 #pragma unroll
       for (int t = 0; t < 6; ++t) q[c][t] = splat4(0.f);
     }
@@ -330,19 +267,12 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : UFR_RT_MINW) ray_transfor
       static_for<8>([&](auto hi) __attribute__((always_inline)) {
         constexpr int h = decltype(hi)::value;
         f32x4 acc = splat4(0.f);
-        f32x4 kvh;
-        if constexpr (kKvLds) kvh = kv_lds[h * 64];
-        else kvh = KV[h];
         static_for<3>([&](auto qi) __attribute__((always_inline)) {
           constexpr int qd = decltype(qi)::value, quad = 3 * h + qd;   // lane group g: head dim 3g + qd
           const float qq = (3 * g + qd < 11) ? elu1_acc(q[c][quad >> 2][quad & 3], q_dsc, q_l2e) : 0.f;
-#ifdef UFR_ABL_NOKV
-          acc[qd] += kvh[qd] * qq;
-#else
-          acc = mfma16(kvh[qd], qq, acc);            // rows = V slots: sum_d KV[d][v] Q'[d]; slot 3 = Q'.sum(K')
-#endif
+          acc = mfma16(KV[h][qd], qq, acc);          // rows = V slots: sum_d KV[d][v] Q'[d]; slot 3 = Q'.sum(K')
         });
-        const float den = (UFR_RT_LOCAL_DEN && !TAPE) ? acc[3] : __shfl(acc[3], j);   // every group's own / slot 3 of lane group 0
+        const float den = TAPE ? __shfl(acc[3], j) : acc[3];   // slot 3 of lane group 0 / every group's own (the ones columns)
         const float Z = fast_rcp(den + 1e-6f);         // linear_attention.py:43
         const float zs = Z * (float)SN;              // :44
         if constexpr (TAPE) zs_all[h] = zs;
@@ -489,11 +419,9 @@ template <bool LOWP, bool TAPE = false>
 static hipError_t launch_rt(const float* packed, const float* token0, const int* tok_row, const float* order_pe, int RN,
                             int SN, float* srdf, float* ray_out, int* status, hipStream_t s, float* tape = nullptr,
                             float* ray_state = nullptr) {
-  constexpr int C2 = TAPE ? 1 : kRtC2;
-  constexpr int lds = kF16LdsBytes + (C2 > 1 ? kRtKvLdsBytes : 0);
   static LdsAttrOnce lds_attr;   // per instantiation; thread-safe, once per device
-  if (const hipError_t attr = lds_attr.set(reinterpret_cast<const void*>(&ray_transformer_kernel<LOWP, TAPE, C2>), lds); attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((ray_transformer_kernel<LOWP, TAPE, C2>), dim3((RN + kRtWaves - 1) / kRtWaves), dim3(kRtBlock), lds, s,
+  if (const hipError_t attr = lds_attr.set(reinterpret_cast<const void*>(&ray_transformer_kernel<LOWP, TAPE>), kF16LdsBytes); attr != hipSuccess) return attr;
+  hipLaunchKernelGGL((ray_transformer_kernel<LOWP, TAPE>), dim3((RN + kRtWaves - 1) / kRtWaves), dim3(kRtBlock), kF16LdsBytes, s,
                      packed, token0, tok_row, order_pe, RN, SN, srdf, ray_out, status, tape, ray_state);
   return hipGetLastError();
 }

@@ -942,8 +942,9 @@ int side_pool_get(int n, SidePool** out) {
     // leave instead of taking turns with them
     int least = 0, greatest = 0;
     UFR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    // (measured round 6, configs[2] on one GPU, 24 frames, two runs each: 137.5 / 139.4 ms per frame against 140.5 / 140.6
-    // with flat priorities and 145.4 / 143.8 without the overlap: tools/dev/prio_ab.sh)
+    // (measured round 6, configs[2] on one GPU, 24 frames, two runs each: 137.5 / 139.4 ms per frame with the overlap,
+    // 145.4 / 143.8 without it.  The A/B's "flat priorities" leg, 140.5 / 140.6, changed no priority -- the variables it
+    // set were read nowhere -- so it ran this same configuration again: what the priorities themselves buy is unmeasured)
     UFR_HIP(hipStreamCreateWithPriority(&p.s[p.n], hipStreamNonBlocking, greatest));
     UFR_HIP(hipEventCreateWithFlags(&p.join[p.n], hipEventDisableTiming));
   }

@@ -17,24 +17,9 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 // 1 / x and 1 / sqrt(x) as the hardware approximations (v_rcp_f32 / v_rsq_f32: 1 ulp) for the normalisers INSIDE the
 // two transformer kernels (attention 1 / (Q.sum K + eps), LayerNorm 1 / sigma, the softmax denominator): an IEEE
 // division is ten vector instructions, a correctly rounded sqrt a dozen more -- 5 % of those kernels' vector work for
-// bits far below their own accumulation noise (4e-7, tests/accuracy_report.py).  -DUFR_FAST_DIV=0 restores the divisions.
-#ifndef UFR_FAST_DIV
-#define UFR_FAST_DIV 1
-#endif
-__device__ __forceinline__ float fast_rcp(float x) {
-#if UFR_FAST_DIV
-  return __builtin_amdgcn_rcpf(x);
-#else
-  return 1.f / x;
-#endif
-}
-__device__ __forceinline__ float fast_rsqrt(float x) {
-#if UFR_FAST_DIV
-  return __builtin_amdgcn_rsqf(x);
-#else
-  return 1.f / sqrtf(x);
-#endif
-}
+// bits far below their own accumulation noise (4e-7, tests/accuracy_report.py).
+__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float fast_rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
 // ReLU of a matrix-core accumulator as ONE instruction (v_med3_f32 x, 0, FLT_MAX; an infinite accumulator is reported by the probe).  fmaxf(x, 0.f) compiles to two: hipcc
 // first canonicalises an operand it cannot prove quiet (v_max_f32 x, x, x), then takes the maximum -- 96 extra vector
 // instructions per view-transformer iteration.  NOT inline assembly: the compiler's hazard recogniser does not look
@@ -146,21 +131,13 @@ __device__ __forceinline__ void axpy10_rot4(float (&acc)[10], float w, const flo
 // elu(x)+1 (linear_attention.py:10-11).  The negative branch is exp(x) in (0,1]: v_exp_f32 on
 // x*log2(e) (rel. error ~|x| 2^-24, i.e. < 1e-6 for the |x| < 16 that matter) instead of the
 // 15-instruction ocml expf -- 80 of them per view-transformer iteration.
-#ifdef UFR_ACCURATE_EXP
-__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x + 1.f : expf(x); }
-#else
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x + 1.f : __expf(x); }
-#endif
 // elu(s a) + 1 for a power-of-two s (a raw accumulator of the split-precision GEMMs): bit-identical to elu1(s * a), the
 // scale rides on the fma / on the exponent's log2(e) multiply
 template <int LOG2S>
 __device__ __forceinline__ float elu1_scaled(float a) {
   constexpr float s = LOG2S >= 0 ? (float)(1u << (LOG2S >= 0 ? LOG2S : 0)) : 1.f / (float)(1u << (LOG2S < 0 ? -LOG2S : 0));
-#ifdef UFR_ACCURATE_EXP
-  return a > 0.f ? __builtin_fmaf(a, s, 1.f) : expf(a * s);
-#else
   return a > 0.f ? __builtin_fmaf(a, s, 1.f) : __builtin_amdgcn_exp2f((0x1.715476p+0f * s) * a);
-#endif
 }
 
 // sum over the 4 lane groups (lanes l, l^16, l^32, l^48)

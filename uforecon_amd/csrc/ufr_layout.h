@@ -166,10 +166,7 @@ enum Stream : int { S_VT = 0, S_RT1, S_RT2, S_COUNT };
 constexpr int kChunkMaxFrags = 32;  // LDS slot = 32 KiB; two slots per workgroup
 
 __host__ __device__ constexpr int stream_len(int s) { return s == S_VT ? 9 : (s == S_RT1 ? 2 : 7); }
-#ifndef UFR_VT_OT
-#define UFR_VT_OT 1
-#endif
-__host__ __device__ constexpr int stream_ot(int s) { return s == S_VT ? UFR_VT_OT : 2; }  // out tiles interleaved per stage
+__host__ __device__ constexpr int stream_ot(int s) { return s == S_VT ? 1 : 2; }  // out tiles interleaved per stage
 __host__ __device__ constexpr int stream_chunks(int s) { return s == S_RT1 ? 4 : 10; }  // even: static slot parity
 __host__ __device__ constexpr int stream_mat(int s, int i) {
   switch (s) {

@@ -51,23 +51,14 @@ constexpr int kScaleExpWMin = -40, kScaleExpWMax = 24, kScaleExpXMin = -40, kSca
 // It is only the FLOOR: ufr_frame_prepare measures the frame's feature maps and volume features, and the table is re-derived
 // for a frame beyond it (ufr_weights_fit_frame) -- a checkpoint loads and renders without side information (main.py:186-190).
 constexpr float kDefaultInputAbsMax = 4094.f;
-#ifndef UFR_F16_CHUNK
-#define UFR_F16_CHUNK 12
-#endif
-constexpr int kF16ChunkFrags = UFR_F16_CHUNK;  // KiB per chunk: whole (tile, 2 planes) pairs; splits evenly over the 4 fetching waves
-#ifndef UFR_F16_SLOTS
-#define UFR_F16_SLOTS 3
-#endif
+constexpr int kF16ChunkFrags = 12;  // KiB per chunk: whole (tile, 2 planes) pairs; splits evenly over the 4 fetching waves
 // LDS ring depth: kF16Slots-1 chunks in flight.  Measured with the fp16x3 kernels (tools/dev/ab_kernels.sh, 4 rounds):
 // 3 x 12 KiB runs the view / ray transformer 4.5 % / 2 % faster than 2 x 24 KiB and needs 12 KiB less LDS per
 // workgroup (which the gather kernels of other chunks use when they share the CU); 4 x 12, 6 x 8 and 12 x 4 KiB are
 // no better.
-constexpr int kF16Slots = UFR_F16_SLOTS;
-#ifndef UFR_F16_DEPTH
-#define UFR_F16_DEPTH 2
-#endif
+constexpr int kF16Slots = 3;
 // stages (one out tile's plane fragments = 3 C MFMAs of cover) the LDS weight reads run ahead of their use
-constexpr int kF16Depth = UFR_F16_DEPTH;
+constexpr int kF16Depth = 2;
 static_assert(kF16Depth >= 1 && kF16Depth * kPlanes <= kF16ChunkFrags, "read-ahead must stay inside one chunk");
 
 // B_COUNT forward streams (fp16 planes, this header's arithmetic), then the data-gradient streams of the backward kernels:

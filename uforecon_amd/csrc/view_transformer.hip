@@ -76,14 +76,11 @@ __device__ __forceinline__ void layer_norm80(f32x4 (&t)[C][5], const WS& ws, int
 
 // 256-thread workgroups (one wave per SIMD), two per CU; each streams the layer chain's weight planes
 // through its own ring of three 12 KiB LDS slots (weight_stream_f16.h).
-#ifndef UFR_VT_BLOCK
-#define UFR_VT_BLOCK 256   // threads per workgroup
-#define UFR_VT_C 2         // token column tiles per wave
-#define UFR_VT_MINW 2      // waves per SIMD the register budget is sized for
-#endif
-#ifndef UFR_VT_OVERSUB
-#define UFR_VT_OVERSUB 4   // workgroups launched per resident slot
-#endif
+constexpr int kVtBlock = 256;   // threads per workgroup
+constexpr int kVtC = 2;         // token column tiles per wave
+constexpr int kVtMinW = 2;      // waves per SIMD the register budget is sized for
+constexpr int kVtOversub = 4;   // workgroups launched per resident slot
+constexpr int kVtWaves = kVtBlock / 64;
 #ifdef UFR_PHASE_TIMING  // development build: cycle counts per phase of wave 0 (tools/bench_kernels.py prints them)
 __device__ unsigned long long g_vt_phase[32];
 __device__ unsigned long long g_vt_wave[4096 * 2];  // start / end tick of every wave of the last launch
@@ -94,30 +91,12 @@ __device__ unsigned long long g_vt_wave[4096 * 2];  // start / end tick of every
     t_prev = t_now;                                                                    \
   }
 #else
-// production builds: optionally a scheduling fence at the phase boundaries (kPhaseFence).  Tried for the straddling L = 6
-// kernel while it ran 15 % slower than it should (the cause was scalar-register pressure: weight_stream_f16.h, ScalarFile):
-// no effect before or after that fix, so both knobs default to off.
-#define UFR_PHASE(i) \
-  { if constexpr (kPhaseFence) __builtin_amdgcn_sched_barrier(0); }
+#define UFR_PHASE(i)
 #endif
-#ifndef UFR_VT_FENCE_ALL
-#define UFR_VT_FENCE_ALL 0
-#endif
-#ifndef UFR_VT_FENCE_STRADDLE
-#define UFR_VT_FENCE_STRADDLE 0
-#endif
-#ifndef UFR_VT_SCORES_HOOK
-#define UFR_VT_SCORES_HOOK 1   // the attention scores ride on the v GEMM's MFMAs (L = 4, two column tiles).  Round 6, same box, two runs each: alone 0.3635-0.3641 vs 0.3648-0.3662 ms per launch (nothing); with UFR_HOOK_VALU 6 frame 122.1-122.3 vs 123.4-123.6 ms
-#endif
-#ifndef UFR_VT_RELOAD_X
-#define UFR_VT_RELOAD_X 0   // 1: the L = 6 kernel re-reads the token rows for the residual (see there); measured 395 -> 444 ms per
-#endif                      // 600x800 / 5-view frame once the scalar pressure was fixed (it had helped before: 434 -> 428)
-constexpr int kVtBlock = UFR_VT_BLOCK;
-constexpr int kVtWaves = kVtBlock / 64;
 
 // TAPE: the instantiation the backward launches (bwd_tape.h): the same arithmetic, plus one store per activation tile.
 template <int L, int C, bool LOWP, bool TAPE = false>
-__global__ void __launch_bounds__(kVtBlock, UFR_VT_MINW) view_transformer_kernel(const float* __restrict__ packed,
+__global__ void __launch_bounds__(kVtBlock, kVtMinW) view_transformer_kernel(const float* __restrict__ packed,
                                                                              const float* __restrict__ x_tokens,
                                                                              const float* __restrict__ x_point,
                                                                              const float* __restrict__ rgbm,
@@ -136,10 +115,10 @@ __global__ void __launch_bounds__(kVtBlock, UFR_VT_MINW) view_transformer_kernel
   constexpr bool STRADDLE = (L == 6 && C == 2 && !TAPE);   // the tape's consumers use the plain slot map
   static_assert(!TAPE || kBlockCols % C == 0, "tape blocks");
   constexpr int PPW = STRADDLE ? 5 : PPT * C;         // points per wave iteration
-  constexpr bool kReloadX = STRADDLE && UFR_VT_RELOAD_X;                 // the residual re-reads the token rows (see there)
-  constexpr bool kPhaseFence = (STRADDLE && UFR_VT_FENCE_STRADDLE) || UFR_VT_FENCE_ALL;
-  constexpr bool kScoresHook = UFR_VT_SCORES_HOOK && L == 4 && C == 2 && !TAPE;
-  (void)kPhaseFence;
+  // L = 4, two column tiles: the attention scores ride on the v GEMM's MFMAs (its user hook, one slot per k-step and out
+  // tile).  They are computed nowhere else, so every one of the 6 C slots must exist
+  constexpr bool kScoresHook = L == 4 && C == 2 && !TAPE;
+  static_assert(!kScoresHook || ksteps(M_VT_V) * mat_desc(M_VT_V).n_out >= 6 * C, "the v GEMM has too few hook slots for the scores");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto ws = wstream_f16_begin<kVtWaves, LOWP>(packed, smem);
   wstream_f16_prime<B_VT, kVtWaves>(ws);
@@ -221,28 +200,6 @@ __global__ void __launch_bounds__(kVtBlock, UFR_VT_MINW) view_transformer_kernel
     auto tape_st = [&](int tile, int c, f32x4 v) __attribute__((always_inline)) {
       if (grp < n_groups) tile_store<TapeL>(tape_blk, tile, col0 % kBlockCols + c, lane, v);
     };
-#ifdef UFR_FUSION_PROBE
-    // Feasibility probe for fusing the gather into this kernel: a synthetic producer phase with
-    // the gather's per-iteration footprint -- 3 dependent rounds (projection -> footprint -> taps) of UFR_FUSION_PROBE
-    // independent 16-byte loads inside a 256 KiB window (cache-resident like the feature maps), ~12 VALU per load --
-    // whose result is kept alive but unused.  The real gather needs ~8 points x 3 views x 176 lane-loads / 64 = 66 loads
-    // per wave iteration, i.e. UFR_FUSION_PROBE = 22.
-    {
-      f32x4 acc = splat4(0.f);
-      unsigned cursor = (unsigned)(grp * 64 + lane) * 2654435761u;
-      const float* window = x_tokens + (size_t)((unsigned)grp % 64u) * 65536u;
-      for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int k = 0; k < UFR_FUSION_PROBE; ++k) {
-          const unsigned off = ((cursor >> 8) + k * 977u) & 16383u;
-          const f32x4 v = ld4(window + (size_t)off * 4);
-          acc = acc * 1.0001f + v * v - acc * v * 0.5f + v * 0.25f;
-        }
-        cursor = cursor * 1664525u + 1013904223u + (unsigned)(int)(acc[0] * 1e-30f);
-      }
-      asm volatile("" ::"v"(acc));
-    }
-#endif
     // ---------------- load tokens: x[c][t] = features 16t+4g..+3 of token j
     f32x4 x[C][5];
     int pidx[C];
@@ -263,12 +220,7 @@ __global__ void __launch_bounds__(kVtBlock, UFR_VT_MINW) view_transformer_kernel
 #pragma unroll
       for (int t = 0; t < 5; ++t) {
         f32x4 tok = vec_frag<V_VIEW_TOKEN>(ws, t, g);
-#ifdef UFR_ABL_NOTOKLOAD   // ablation (timing only): what the token loads' latency costs
-        f32x4 val = splat4(0.001f * (float)(lane + t));
-        asm volatile("" : "+v"(val));
-#else
         f32x4 val = ld4(t < 2 ? row + 16 * t : t < 4 ? prow + 16 * (t - 2) : last);
-#endif
         dst[t] = tv == 0 ? tok : val;                     // ray_transformer.py:284-286
         if (!valid[c]) dst[t] = splat4(0.f);
       }
@@ -364,8 +316,8 @@ __global__ void __launch_bounds__(kVtBlock, UFR_VT_MINW) view_transformer_kernel
         for (int c = 0; c < C; ++c) Zs[c][hh] = (float)L * fast_rcp(den[c] + 1e-6f);   // Z * v_length (linear_attention.py:43-44)
       });
     } else if constexpr (kScoresHook) {
-      // round-6 experiment (UFR_VT_SCORES_HOOK): the scores of (column tile, head) pair u = 2 c + hh ride on the v GEMM's
-      // stages 3 u .. 3 u + 2 (elu of Q | elu of K | the L dot products, the normaliser) instead of running in front of it
+      // the scores of (column tile, head) pair u = 2 c + hh ride on the v GEMM's stages 3 u .. 3 u + 2 (elu of Q | elu of
+      // K | the L dot products, the normaliser) instead of running in front of it
     } else {
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -583,24 +535,13 @@ __global__ void __launch_bounds__(kVtBlock, UFR_VT_MINW) view_transformer_kernel
     } else {
       layer_norm80<C, V_VT_N2W, V_VT_N2B>(o, ws, g, sc[VS_EPS2], 1.f);
     }
-    // the residual.  UFR_VT_RELOAD_X (off): the straddling L = 6 kernel reads the token rows AGAIN here (they are in L2)
-    // instead of keeping 40 registers alive from the top of the iteration -- no spills then, but slower (see the macro)
-    if constexpr (kReloadX) {
+    // the residual (x stays in registers from the top of the iteration: re-reading the token rows was slower: DESIGN.md section 7)
 #pragma unroll
-      for (int c = 0; c < C; ++c) {
-        f32x4 xr[5];
-        load_x(c, xr);
+    for (int c = 0; c < C; ++c)
 #pragma unroll
-        for (int t = 0; t < 5; ++t) o[c][t] += xr[t];
-      }
-    } else {
+      for (int t = 0; t < 5; ++t)
 #pragma unroll
-      for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int t = 0; t < 5; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[c][t][r] += x[c][t][r];   // scalar adds: no v_pk_add_f32 (layer_norm80)
-    }
+        for (int r = 0; r < 4; ++r) o[c][t][r] += x[c][t][r];   // scalar adds: no v_pk_add_f32 (layer_norm80)
     if constexpr (TAPE) {
 #pragma unroll
       for (int c = 0; c < C; ++c) {
@@ -769,7 +710,7 @@ static hipError_t launch_vt(const float* packed, const float* x_tokens, const fl
                             float* token0, float* radiance, float* view_out, int* status, hipStream_t s, float* tape = nullptr) {
   // TAPE: one column tile per wave -- the tape stores keep a tile's activations alive longer, and with two column tiles
   // the kernel spilled 250..330 registers (1.2 ms per 131 072 points for 0.2 ms of arithmetic)
-  constexpr int C = TAPE ? 1 : UFR_VT_C;
+  constexpr int C = TAPE ? 1 : kVtC;
   constexpr int PPW = (L == 6 && C == 2 && !TAPE) ? 5 : (16 / L) * C;   // L = 6: a fifth point straddles the wave's two column tiles
   const int n_groups = TAPE ? ((P + (16 / L) * kBlockCols - 1) / ((16 / L) * kBlockCols)) * (kBlockCols / C) : (P + PPW - 1) / PPW;
   int blocks = (n_groups + kVtWaves - 1) / kVtWaves;
@@ -777,8 +718,8 @@ static hipError_t launch_vt(const float* packed, const float* x_tokens, const fl
   // 512 persistent workgroups the favoured half finishes ~25 % early and the rest runs alone, without a
   // partner wave to overlap its VALU phases with (measured per-wave lifetimes 1.27 .. 1.64 ms).  Launching a
   // few times more, shorter workgroups lets the dispatcher refill a CU as soon as one retires.
-  constexpr int resident = 256 * (UFR_VT_MINW * 4 / kVtWaves);   // workgroups the chip holds at once
-  const int max_blocks = resident * UFR_VT_OVERSUB;
+  constexpr int resident = 256 * (kVtMinW * 4 / kVtWaves);   // workgroups the chip holds at once
+  const int max_blocks = resident * kVtOversub;
   if (blocks > max_blocks) {
     // every wave runs the same number of iterations (the chunk barriers are workgroup-wide): size the grid so that
     // the groups divide evenly over them instead of leaving most waves idle in a last, partial iteration
@@ -794,16 +735,6 @@ static hipError_t launch_vt(const float* packed, const float* x_tokens, const fl
   }
   static LdsAttrOnce lds_attr;   // per instantiation; thread-safe, once per device
   if (const hipError_t attr = lds_attr.set(reinterpret_cast<const void*>(&view_transformer_kernel<L, C, LOWP, TAPE>), kF16LdsBytes); attr != hipSuccess) return attr;
-#ifdef UFR_VT_OCC_PROBE   // development: UFR_VT_PAD_LDS=<bytes> inflates the LDS request to limit the workgroups per CU
-  static const int pad_lds = getenv("UFR_VT_PAD_LDS") ? atoi(getenv("UFR_VT_PAD_LDS")) : 0;
-  if (pad_lds > 0) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&view_transformer_kernel<L, C, LOWP>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, kF16LdsBytes + pad_lds);
-    hipLaunchKernelGGL((view_transformer_kernel<L, C, LOWP>), dim3(blocks), dim3(kVtBlock), kF16LdsBytes + pad_lds, s, packed,
-                       x_tokens, x_point, rgb, dir, P, token0, radiance, view_out, status);
-    return hipGetLastError();
-  }
-#endif
   hipLaunchKernelGGL((view_transformer_kernel<L, C, LOWP, TAPE>), dim3(blocks), dim3(kVtBlock), kF16LdsBytes, s, packed, x_tokens,
                      x_point, rgb, dir, P, token0, radiance, view_out, status, tape);
   return hipGetLastError();

@@ -26,9 +26,6 @@ constexpr int kF16LdsBytes = kF16RingBytes + kVecBytes;
 // token is NaN (the products w_hi hi and w_hi lo are infinities of opposite sign, or 0 x inf) -- probe_gemm.  a_M comes
 // from an upper bound of the layer's input (prep.hip: weight_scale_kernel), so this happens only when the caller's
 // stated input bound (ufr_weights_pack_for) was wrong.
-#ifndef UFR_RANGE_MODE
-#define UFR_RANGE_MODE 1   // 0: no range tracking (timing ablation)
-#endif
 __device__ __forceinline__ void split_pair(float a, float b, float m, unsigned& h, unsigned& l) {
   if (__builtin_constant_p(a) && __builtin_constant_p(b) && a == 0.f && b == 0.f) {   // padding registers of a tile: the
     h = l = 0u;                                                                      // compiler cannot fold the asm below
@@ -92,10 +89,6 @@ __device__ __forceinline__ WStreamF16T<LOWP, BF16> wstream_f16_begin(const float
     ws.rsrc[3] = 0x00020000;                                                                  // gfx9 family: 32-bit data format
     ws.lds_wave = ws.ring_lds + (unsigned)ws.wave * 1024u;
   }
-#ifdef UFR_ABL_NOLDS
-  for (int d = 0; d < kF16Depth; ++d)
-    for (int p = 0; p < kPlanes; ++p) ws.pre[d][p] = __builtin_bit_cast(f16x8, u32x4{0x3c003c00u + ws.lane, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u});
-#endif
   f32x4* v = reinterpret_cast<f32x4*>(smem + kF16RingBytes);
   ws.vecs = v;
   constexpr int voff = vec_region_offset(), n4 = vec_region_floats() / 4;
@@ -108,23 +101,16 @@ __device__ __forceinline__ WStreamF16T<LOWP, BF16> wstream_f16_begin(const float
   return ws;
 }
 
-// One LDS-DMA piece: 64 lanes x 16 bytes from g_uniform + lane_off (scalar base, 32-bit lane offset: no address
-// VALU) to LDS address lds_addr + 16 lane.  Issued as inline assembly ON PURPOSE: with the compiler-visible
-// __builtin_amdgcn_global_load_lds in the loop, hipcc's s_waitcnt insertion gives up counting LDS reads and drains
-// lgkmcnt to 0 before every use of a weight fragment -- the read-ahead was worth nothing and the kernels ran
-// 15..22 % slower (the "no DMA" ablation).  Untracked vector-memory operations only make the compiler's own
-// vmcnt(N) waits conservative (loads return in order); the hand-off barrier waits for the pieces explicitly.
-__device__ __forceinline__ void lds_dma_16(const char* g_uniform, unsigned lane_off, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(g_uniform), "v"(lane_off), "s"(lds_addr) : "memory");
-}
-// The same piece through the BUFFER form: rsrc = the plane region shifted by the wave's 1 KiB, GOFF / LOFF = the piece's
-// byte offsets in the region / in the ring as literals.  Two scalar instructions per piece (m0, soffset) instead of
-// the eight to ten the 64-bit address of the global form costs (s_mov, s_ashr, three 64-bit adds, m0, s_nop): ~550
-// fewer issue slots per view-transformer iteration.  The soffset move sits between the m0 write and the DMA, which is
-// the wait state the hardware wants there.
-#ifndef UFR_DMA_BUFFER
-#define UFR_DMA_BUFFER 1
-#endif
+// One LDS-DMA piece: 64 lanes x 16 bytes through the buffer descriptor rsrc (the plane region shifted by the wave's 1 KiB)
+// to LDS address lds_wave + 16 lane; GOFF / LOFF = the piece's byte offsets in the region / in the ring as literals.
+// Issued as inline assembly ON PURPOSE: with the compiler-visible __builtin_amdgcn_global_load_lds in the loop, hipcc's
+// s_waitcnt insertion gives up counting LDS reads and drains lgkmcnt to 0 before every use of a weight fragment -- the
+// read-ahead was worth nothing and the kernels ran 15..22 % slower (the "no DMA" ablation).  Untracked vector-memory
+// operations only make the compiler's own vmcnt(N) waits conservative (loads return in order); the hand-off barrier
+// waits for the pieces explicitly.  Two scalar instructions per piece (m0, soffset) instead of the eight to ten the
+// 64-bit address of the global form costs (s_mov, s_ashr, three 64-bit adds, m0, s_nop): ~550 fewer issue slots per
+// view-transformer iteration.  The soffset move sits between the m0 write and the DMA, which is the wait state the
+// hardware wants there.
 template <unsigned GOFF, unsigned LOFF>
 __device__ __forceinline__ void lds_dma_piece(const i32x4& rsrc, unsigned lds_wave, unsigned lane_off) {
   unsigned soff;
@@ -143,19 +129,11 @@ __device__ __forceinline__ void wstream_f16_fetch(const WS& ws) {
     constexpr size_t goff = ((size_t)f16_stream_base_frags(S) + (size_t)CHK * kF16ChunkFrags) * 1024;
     constexpr int soff = (CHK % kF16Slots) * (kF16ChunkFrags * 1024);
     const unsigned lane_off = ws.lane * 16;
-#if UFR_DMA_BUFFER
     static_assert(goff + (size_t)kF16ChunkFrags * 1024 < (1ull << 31), "buffer offsets are 32-bit");
     static_for<P1 - P0>([&](auto ki) __attribute__((always_inline)) {
       constexpr unsigned k = P0 + decltype(ki)::value;
       lds_dma_piece<(unsigned)goff + k * NWAVES * 1024u, (unsigned)soff + k * NWAVES * 1024u>(ws.rsrc, ws.lds_wave, lane_off);
     });
-#else
-    int zero = 0;
-    asm volatile("" : "+s"(zero));  // keep the loop-invariant source address out of LICM's hands
-    const char* g = ws.src + zero + goff + ws.wave * 1024;   // wave-uniform: scalar base + 32-bit lane offset
-#pragma unroll
-    for (int k = P0; k < P1; ++k) lds_dma_16(g + k * NWAVES * 1024, lane_off, ws.ring_lds + soff + ws.wave * 1024 + k * NWAVES * 1024);
-#endif
   }
 }
 
@@ -164,14 +142,6 @@ __device__ __forceinline__ void wstream_f16_fetch(const WS& ws) {
 // be outstanding when chunk CHK must have landed.
 template <int S, int NWAVES, int CHK, class WS>
 __device__ __forceinline__ void wstream_f16_barrier(const WS& ws, bool wrap) {
-#ifdef UFR_ABL_NOBARRIER  // ablation builds (timing only, results are garbage): no hand-off at all / barrier without fetch
-  (void)ws; (void)wrap;
-  return;
-#endif
-#ifdef UFR_ABL_NODMA
-  __syncthreads();
-  return;
-#endif
   constexpr int per_chunk = kF16ChunkFrags / NWAVES, ahead = kF16Slots - 1, n_chunks = f16_stream_chunks(S);
   constexpr int younger = (kF16Slots - 2) * per_chunk;
   // lgkmcnt(0): this wave's reads of the chunk whose slot is refilled next have returned (the stages are read
@@ -192,10 +162,6 @@ __device__ __forceinline__ void wstream_f16_barrier(const WS& ws, bool wrap) {
 // CHK: an LDS-DMA instruction stalls its wave for 60..185 cycles (MI355X_MICROARCH.md), several in a row for longer.
 template <int S, int NWAVES, int CHK, int P0 = 0, int P1 = kF16ChunkFrags / NWAVES, class WS>
 __device__ __forceinline__ void wstream_f16_refill(const WS& ws, bool wrap) {
-#if defined(UFR_ABL_NOBARRIER) || defined(UFR_ABL_NODMA)
-  (void)ws; (void)wrap;
-  return;
-#endif
   constexpr int ahead = kF16Slots - 1, n_chunks = f16_stream_chunks(S);
   if constexpr (CHK + ahead < n_chunks) {
     wstream_f16_fetch<S, NWAVES, CHK + ahead, P0, P1>(ws);
@@ -236,16 +202,13 @@ __device__ __forceinline__ void wstream_f16_prime(const WS& ws) {
 // unordered compare per value pair.  Internally every divisor is positive and every exponent non-positive.
 template <int C, int N, class WS>
 __device__ __forceinline__ void probe_gemm(const f32x4 (&out)[C][N], WS& ws) {
-#if UFR_RANGE_MODE != 0
   bool bad = false;
 #pragma unroll
   for (int c = 0; c < C; ++c) bad |= __builtin_amdgcn_class(out[c][0][0], 0x207);   // sNaN | qNaN | -inf | +inf
   ws.bad_in |= __builtin_amdgcn_ballot_w64(bad);
-#endif
 }
 template <int C, int N, class WS>
 __device__ __forceinline__ void track_external(const f32x4 (&t)[C][N], WS& ws) {
-#if UFR_RANGE_MODE != 0
   bool nan = false;
 #pragma unroll
   for (int c = 0; c < C; ++c)
@@ -253,7 +216,6 @@ __device__ __forceinline__ void track_external(const f32x4 (&t)[C][N], WS& ws) {
     for (int i = 0; i < N; ++i)
       nan |= __builtin_isunordered(t[c][i][0], t[c][i][1]) | __builtin_isunordered(t[c][i][2], t[c][i][3]);
   ws.bad_out |= __builtin_amdgcn_ballot_w64(nan);
-#endif
 }
 
 // end of a kernel: raise the sticky range status (bit 0: a dense layer produced non-finite accumulators, i.e. one of its
@@ -314,16 +276,9 @@ __device__ __forceinline__ f32x4 mfma_planes(const f16x8& a, const f16x8& b, con
 // hook(integral_constant<to>) is VALU work without dependence on this panel (the split of the NEXT k-step's
 // operands): it is interleaved with the stage's MFMAs -- the 16-bit matrix pipe runs ~2 independent VALU
 // instructions per MFMA for free (tools/dev/mfma_valu2), so the split costs nothing once it sits there.
-#ifndef UFR_HOOK_VALU
-#define UFR_HOOK_VALU 6   // VALU instructions of the hook issued after each MFMA (2 until round 6: see UFR_VT_SCORES_HOOK)
-#endif
+constexpr int kHookValu = 6;   // VALU instructions of the hook issued after each MFMA (2 until round 6: DESIGN.md section 7)
 constexpr int kProducts = 3;   // MFMAs per fp32 product
-#ifndef UFR_SETPRIO
-#define UFR_SETPRIO 1          // s_setprio level of a wave inside a GEMM panel (0 outside)
-#endif
-#ifndef UFR_F16_SPREAD
-#define UFR_F16_SPREAD 1       // 1: a chunk's refill pieces are spread over its stages; 0: all right after the barrier
-#endif
+constexpr int kSetprio = 1;    // s_setprio level of a wave inside a GEMM panel (0 outside)
 struct NoHook {
   template <class T> __device__ __forceinline__ void operator()(T) const {}
 };
@@ -342,7 +297,7 @@ __device__ __forceinline__ void gemm_f16_panel(WS& ws, const BStep (&b)[C], f32x
   // inside a GEMM panel the wave wins issue arbitration over a partner that is in a VALU-only phase (measured: view
   // transformer -1.7 %, ray transformer -1.4 % alone, 0.1 % on the whole frame with the gather beside them; priority 3
   // no better, the inverse scheme no effect)
-  __builtin_amdgcn_s_setprio(UFR_SETPRIO);
+  __builtin_amdgcn_s_setprio(kSetprio);
   static_for<n_out>([&](auto ti) __attribute__((always_inline)) {
     constexpr int to = decltype(ti)::value;
     constexpr int f = F0 + to * kPlanes;                 // first of the stage's plane fragments
@@ -359,12 +314,9 @@ __device__ __forceinline__ void gemm_f16_panel(WS& ws, const BStep (&b)[C], f32x
       constexpr int n_st = (in_frags < kF16ChunkFrags ? in_frags : kF16ChunkFrags) / kPlanes, j = in_chk / kPlanes;
       constexpr int pieces = kF16ChunkFrags / NWAVES;
       if constexpr (in_chk == 0) wstream_f16_barrier<ST, NWAVES, chk>(ws, wrap);
-      wstream_f16_refill<ST, NWAVES, chk, UFR_F16_SPREAD ? j * pieces / n_st : (j == 0 ? 0 : pieces),
-                         UFR_F16_SPREAD ? (j + 1) * pieces / n_st : pieces>(ws, wrap);
-#ifndef UFR_ABL_NOLDS   // ablation (timing only): the weight fragments are never read from LDS
+      wstream_f16_refill<ST, NWAVES, chk, j * pieces / n_st, (j + 1) * pieces / n_st>(ws, wrap);
 #pragma unroll
       for (int p = 0; p < n_planes; ++p) ws.pre[s2 % kF16Depth][p] = lds[base + p * 64];
-#endif
     };
     if constexpr (sidx == 0)                             // start of a pass: nothing is in flight yet
       static_for<kF16Depth>([&](auto di) __attribute__((always_inline)) { read_stage(di); });
@@ -389,7 +341,7 @@ __device__ __forceinline__ void gemm_f16_panel(WS& ws, const BStep (&b)[C], f32x
 #pragma unroll
       for (int i = 0; i < n_products * C; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, UFR_HOOK_VALU, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, kHookValu, 0);
       }
     }
 #pragma unroll
@@ -430,11 +382,7 @@ __device__ __forceinline__ void bwords_to_bstep(const BWords<C>& bw, BStep (&b)[
 // elu(value) + 1 of a raw accumulator a = value / dsc (dsc a power of two; dsc_l2e = dsc log2(e), exact): bit-identical
 // to elu1(dsc * a), the scale rides on the fma / on the exponent's log2(e) multiply
 __device__ __forceinline__ float elu1_acc(float a, float dsc, float dsc_l2e) {
-#ifdef UFR_ACCURATE_EXP
-  return a > 0.f ? __builtin_fmaf(a, dsc, 1.f) : expf(a * dsc);
-#else
   return a > 0.f ? __builtin_fmaf(a, dsc, 1.f) : __builtin_amdgcn_exp2f(dsc_l2e * a);
-#endif
 }
 constexpr float kLog2e = 0x1.715476p+0f;
 
@@ -449,7 +397,7 @@ template <int M, int C, int NWAVES, int STREAM = -1, int NIN, class WS, class UH
 __device__ __forceinline__ void gemm_f16(WS& ws, const f32x4 (&in)[C][NIN], f32x4 (&out)[C][mat_desc(M).n_out],
                                         bool wrap, float m = 1.f, UHook&& uhook = NoHook{}) {
   // uhook(integral_constant<k-step * n_out + out tile>): the CALLER's VALU work that does not depend on this GEMM, issued
-  // with the stage's MFMAs like the operand split (round 6 experiment: the attention scores under the v GEMM)
+  // with the stage's MFMAs like the operand split (the view transformer's attention scores under its v GEMM)
   static_assert(NIN == mat_desc(M).n_in, "input tile count");
   constexpr int n_out = mat_desc(M).n_out, NU = 4 * C;
   constexpr bool BF = f16_mat_is_bf16(M);   // bf16 planes: no scales, so the output is exact as it stands and never probed
@@ -460,12 +408,7 @@ __device__ __forceinline__ void gemm_f16(WS& ws, const f32x4 (&in)[C][NIN], f32x
     constexpr int s = decltype(si)::value;
     BStep b[C];
     bwords_to_bstep(cur, b);
-#ifdef UFR_NO_HOOK
-    constexpr bool use_hook = false;
-#else
-    constexpr bool use_hook = true;
-#endif
-    if constexpr (use_hook && s + 1 < ksteps(M) && n_out >= 2) {
+    if constexpr (s + 1 < ksteps(M) && n_out >= 2) {
       BWords<C> nxt;
       gemm_f16_panel<M, s, C, NWAVES, false, STREAM>(ws, b, out, wrap, [&](auto ti) __attribute__((always_inline)) {
         constexpr int to = decltype(ti)::value;
