@@ -32,7 +32,7 @@ enum ufr_status {
 
 /* Version of this header's ABI (argument lists, struct layouts, packed-blob layout).  ufr_version() returns the value
  * the library was built with: a binding must refuse a library whose version differs (uforecon_amd/_lib.py does). */
-#define UFR_ABI_VERSION 504
+#define UFR_ABI_VERSION 505
 
 #define UFR_MAX_VIEWS 7
 #define UFR_NUM_STAGES 3
@@ -562,6 +562,48 @@ int ufr_marching_cubes_count(const float* vol, const int32_t* dim, float level, 
 int ufr_marching_cubes_emit(const float* vol, const int32_t* dim, float level, void* workspace, size_t workspace_bytes,
                             float* verts, float* normals, int32_t* faces, int32_t n_verts, int32_t n_faces, ufr_stream stream);
 int ufr_marching_cubes_table(int8_t* out, int32_t out_len);
+
+/* ---- DTU chamfer evaluation of a mesh or point cloud (ABI 505) ----------------------------------------------
+ * The device side of evaluation/dtu_eval.py: sample the mesh (:68-91), thin the cloud to the density (:105-115), nearest
+ * neighbour distances and their means (:139-155).  Positions and distances are fp64 as in the reference; every count n, V, F
+ * below is 1 .. 2^31 - 1.  uforecon_amd/dtu_eval.py is the caller that strings them together.
+ *
+ * ufr_mesh_sample_*: verts (V,3) fp64, faces (F,3) int32 (device).  Per triangle (p0, p1, p2), v1 = p1 - p0, v2 = p2 - p0,
+ *   l = |v|, area2 = |v1 x v2| (sums of three squares left to right, no fused multiply-add): none if area2 <= 0; else
+ *   thr = density * sqrt(l1 * l2 / area2), n = floor(l / thr), none if n1 or n2 is 0; else the points (v1 * a + v2 * b) + p0
+ *   for a = (i + 0.5) / n1, b = (j + 0.5) / n2, i = 0..n1, j = 0..n2 where a + b < 1, in (triangle, i, j) order.  A
+ *   triangle with an index outside 0..V-1 gives none.  Two calls with the same arguments and workspace
+ *   (>= ufr_mesh_sample_workspace_bytes(F), device):
+ *     ufr_mesh_sample_count: *total_host = the number of points.  SYNCHRONISES the stream.
+ *     ufr_mesh_sample_emit: out (capacity,3) fp64 (device); nothing beyond capacity is written.  Does not synchronise.
+ * ufr_points_cell_keys: keys[i] = the 63-bit Morton key (x the highest of every bit triple) of point i's grid cell,
+ *   floor((p - origin) / cell) per axis clamped to 0 .. 2^21 - 1.  points (n,3) fp64, keys (n) int64: device; origin: host
+ *   double[3]; cell > 0.  Does not synchronise.  The two calls below take points sorted by this key.
+ * ufr_points_thin: the keep-mask of the reference's sequential thinning: in the order given by rank (a permutation of
+ *   0..n-1, int32), a point is kept iff no earlier kept point lies within (dx*dx + dy*dy) + dz*dz <= radius*radius.
+ *   points / keys / rank: sorted by key, keys made with cell >= radius * (1 + 1e-9) and an origin below every point by at
+ *   least one cell.  state (n) uint8 (device): 1 = kept, 2 = removed on return.  Runs rounds of a fixpoint whose result
+ *   does not depend on scheduling; SYNCHRONISES the stream once per round; *rounds_host (nullable) = rounds taken.  A round
+ *   without progress, or more than n rounds, is UFR_ERR_HIP (cannot happen for a valid rank).
+ * ufr_points_nn_dist: dist[i] = the distance from query i to its nearest reference point, sqrt((dx*dx + dy*dy) + dz*dz),
+ *   exact wherever it is < max_dist; elsewhere some value >= max_dist (+inf when nothing is near).  query (nq,3), dist (nq):
+ *   device, any order (a wave is fastest when its queries are neighbours); ref (nr,3) with ref_keys (nr): sorted by key, with
+ *   the origin and cell the keys were made with.  mean_out (device double[2], nullable): the sum of the distances < max_dist
+ *   and their count, summed in a fixed order (the same bits run after run).  workspace >=
+ *   ufr_points_nn_dist_workspace_bytes(nq) (device).  Does not synchronise.                                         */
+size_t ufr_mesh_sample_workspace_bytes(int64_t F);
+int ufr_mesh_sample_count(const double* verts, const int32_t* faces, int64_t V, int64_t F, double density, void* workspace,
+                          size_t workspace_bytes, int64_t* total_host, ufr_stream stream);
+int ufr_mesh_sample_emit(const double* verts, const int32_t* faces, int64_t V, int64_t F, double density, void* workspace,
+                         size_t workspace_bytes, double* out, int64_t capacity, ufr_stream stream);
+int ufr_points_cell_keys(const double* points, int64_t n, const double* origin, double cell, int64_t* keys, ufr_stream stream);
+size_t ufr_points_thin_workspace_bytes(int64_t n);
+int ufr_points_thin(const double* points, const int64_t* keys, const int32_t* rank, int64_t n, double radius, uint8_t* state,
+                    void* workspace, size_t workspace_bytes, int32_t* rounds_host, ufr_stream stream);
+size_t ufr_points_nn_dist_workspace_bytes(int64_t nq);
+int ufr_points_nn_dist(const double* query, int64_t nq, const double* ref, const int64_t* ref_keys, int64_t nr,
+                       const double* origin, double cell, double max_dist, double* dist, double* mean_out, void* workspace,
+                       size_t workspace_bytes, ufr_stream stream);
 
 /* Pixel-wise view weights of the first cascade stage and the weighted aggregate (DepthNet.forward,
  * code1/encoder_utils/fmt/TransMVSNet.py:80-97 with PixelwiseNet :23-41), one pass over the similarity volume:

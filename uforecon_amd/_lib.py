@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # UFR_LIB selects an alternative in-tree build (A/B kernel variants during development)
 LIB_PATH = os.environ.get("UFR_LIB") or os.path.join(HERE, "lib", "libufr.so")
 
-ABI_VERSION = 504   # = UFR_ABI_VERSION of include/ufr.h; load() refuses a library built against another header
+ABI_VERSION = 505   # = UFR_ABI_VERSION of include/ufr.h; load() refuses a library built against another header
 MAX_VIEWS = 7
 NUM_STAGES = 3
 TOKEN_DIM = 80
@@ -64,7 +64,7 @@ class RenderArgs(C.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/ufr.h declares
-i32, sz, vp = C.c_int32, C.c_size_t, C.c_void_p
+i32, i64, sz, vp = C.c_int32, C.c_int64, C.c_size_t, C.c_void_p
 SIGNATURES = {
     "ufr_version": (C.c_int, []),
     "ufr_last_error": (C.c_char_p, []),
@@ -134,6 +134,14 @@ SIGNATURES = {
     "ufr_marching_cubes_count": (C.c_int, [vp, C.POINTER(i32), C.c_float, vp, sz, C.POINTER(i32), vp]),
     "ufr_marching_cubes_emit": (C.c_int, [vp, C.POINTER(i32), C.c_float, vp, sz, vp, vp, vp, i32, i32, vp]),
     "ufr_marching_cubes_table": (C.c_int, [C.POINTER(C.c_int8), i32]),
+    "ufr_mesh_sample_workspace_bytes": (sz, [i64]),
+    "ufr_mesh_sample_count": (C.c_int, [vp, vp, i64, i64, C.c_double, vp, sz, C.POINTER(i64), vp]),
+    "ufr_mesh_sample_emit": (C.c_int, [vp, vp, i64, i64, C.c_double, vp, sz, vp, i64, vp]),
+    "ufr_points_cell_keys": (C.c_int, [vp, i64, C.POINTER(C.c_double), C.c_double, vp, vp]),
+    "ufr_points_thin_workspace_bytes": (sz, [i64]),
+    "ufr_points_thin": (C.c_int, [vp, vp, vp, i64, C.c_double, vp, vp, sz, C.POINTER(i32), vp]),
+    "ufr_points_nn_dist_workspace_bytes": (sz, [i64]),
+    "ufr_points_nn_dist": (C.c_int, [vp, i64, vp, vp, i64, C.POINTER(C.c_double), C.c_double, C.c_double, vp, vp, vp, sz, vp]),
     "ufr_pixelwise_view_weights": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ufr_deform_conv2d_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ufr_deform_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),

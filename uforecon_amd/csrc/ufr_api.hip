@@ -1346,6 +1346,160 @@ int ufr_marching_cubes_table(int8_t* out, int32_t out_len) {
   return UFR_MC_TABLE_ROW;
 }
 
+// ------------------------------------------------------------------ DTU chamfer evaluation
+namespace {
+constexpr long long kChMax = (1ll << 31) - 1;
+
+struct SampleWorkspace {   // [per-triangle offset in its block int64 | block sums int64 | block offsets int64 | total int64]
+  long long *tri_off, *block_tot, *block_off, *total;
+  size_t bytes;
+  SampleWorkspace(void* base, long long F) {
+    const size_t blocks = (size_t)chamfer_blocks(F);
+    char* b = static_cast<char*>(base);
+    size_t off = 0;
+    tri_off = reinterpret_cast<long long*>(b + off);
+    off += align_up((size_t)F * sizeof(long long));
+    block_tot = reinterpret_cast<long long*>(b + off);
+    off += align_up(blocks * sizeof(long long));
+    block_off = reinterpret_cast<long long*>(b + off);
+    off += align_up(blocks * sizeof(long long));
+    total = reinterpret_cast<long long*>(b + off);
+    off += align_up(sizeof(long long));
+    bytes = off;
+  }
+};
+
+int sample_check(const char* who, const double* verts, const int32_t* faces, int64_t V, int64_t F, double density, void* ws,
+                 size_t ws_bytes) {
+  UFR_REQUIRE(verts && faces && ws, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax, "%s: V %lld, F %lld (each must be 1 .. 2^31 - 1)", who, (long long)V,
+              (long long)F);
+  UFR_REQUIRE(density > 0.0 && std::isfinite(density), "%s: density %g (must be positive and finite)", who, density);
+  const size_t need = SampleWorkspace(nullptr, F).bytes;
+  if (ws_bytes < need) return fail(UFR_ERR_WORKSPACE, "%s: workspace %zu bytes, needs %zu", who, ws_bytes, need);
+  return UFR_OK;
+}
+
+struct NnWorkspace {   // [block sums fp64 | block counts int64]
+  double* block_sum;
+  long long* block_cnt;
+  size_t bytes;
+  NnWorkspace(void* base, long long nq) {
+    const size_t blocks = (size_t)chamfer_blocks(nq);
+    char* b = static_cast<char*>(base);
+    block_sum = reinterpret_cast<double*>(b);
+    size_t off = align_up(blocks * sizeof(double));
+    block_cnt = reinterpret_cast<long long*>(b + off);
+    off += align_up(blocks * sizeof(long long));
+    bytes = off;
+  }
+};
+}  // namespace
+
+size_t ufr_mesh_sample_workspace_bytes(int64_t F) { return (F >= 1 && F <= kChMax) ? SampleWorkspace(nullptr, F).bytes : 0; }
+
+int ufr_mesh_sample_count(const double* verts, const int32_t* faces, int64_t V, int64_t F, double density, void* workspace,
+                          size_t workspace_bytes, int64_t* total_host, ufr_stream stream) {
+  if (int rc = sample_check("ufr_mesh_sample_count", verts, faces, V, F, density, workspace, workspace_bytes)) return rc;
+  UFR_REQUIRE(total_host, "ufr_mesh_sample_count: null argument (total_host)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SampleWorkspace w(workspace, F);
+  {
+    ProfScope p("mesh_sample_count", s);
+    UFR_HIP(launch_mesh_sample_count(verts, faces, V, F, density, w.tri_off, w.block_tot, s));
+  }
+  {
+    ProfScope p("mesh_sample_scan", s);
+    UFR_HIP(launch_mesh_sample_scan(w.block_tot, chamfer_blocks(F), w.block_off, w.total, s));
+  }
+  long long tot = 0;
+  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  *total_host = (int64_t)tot;
+  return UFR_OK;
+}
+
+int ufr_mesh_sample_emit(const double* verts, const int32_t* faces, int64_t V, int64_t F, double density, void* workspace,
+                         size_t workspace_bytes, double* out, int64_t capacity, ufr_stream stream) {
+  if (int rc = sample_check("ufr_mesh_sample_emit", verts, faces, V, F, density, workspace, workspace_bytes)) return rc;
+  UFR_REQUIRE(capacity >= 0, "ufr_mesh_sample_emit: capacity %lld", (long long)capacity);
+  UFR_REQUIRE(capacity == 0 || out, "ufr_mesh_sample_emit: null argument (out)");
+  if (capacity == 0) return UFR_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  SampleWorkspace w(workspace, F);
+  ProfScope p("mesh_sample_emit", s);
+  UFR_HIP(launch_mesh_sample_emit(verts, faces, V, F, density, w.tri_off, w.block_off, out, capacity, s));
+  return UFR_OK;
+}
+
+int ufr_points_cell_keys(const double* points, int64_t n, const double* origin, double cell, int64_t* keys, ufr_stream stream) {
+  UFR_REQUIRE(points && origin && keys, "ufr_points_cell_keys: null argument");
+  UFR_REQUIRE(n >= 1 && n <= kChMax, "ufr_points_cell_keys: n %lld (must be 1 .. 2^31 - 1)", (long long)n);
+  UFR_REQUIRE(cell > 0.0 && std::isfinite(cell) && std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]),
+              "ufr_points_cell_keys: cell %g, origin (%g, %g, %g) (cell must be positive, all finite)", cell, origin[0], origin[1],
+              origin[2]);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ProfScope p("points_cell_keys", s);
+  UFR_HIP(launch_points_cell_keys(points, n, origin, cell, reinterpret_cast<long long*>(keys), s));
+  return UFR_OK;
+}
+
+size_t ufr_points_thin_workspace_bytes(int64_t n) { return (n >= 1 && n <= kChMax) ? align_up(sizeof(int)) : 0; }
+
+int ufr_points_thin(const double* points, const int64_t* keys, const int32_t* rank, int64_t n, double radius, uint8_t* state,
+                    void* workspace, size_t workspace_bytes, int32_t* rounds_host, ufr_stream stream) {
+  UFR_REQUIRE(points && keys && rank && state && workspace, "ufr_points_thin: null argument");
+  UFR_REQUIRE(n >= 1 && n <= kChMax, "ufr_points_thin: n %lld (must be 1 .. 2^31 - 1)", (long long)n);
+  UFR_REQUIRE(radius >= 0.0 && std::isfinite(radius), "ufr_points_thin: radius %g (must be finite and >= 0)", radius);
+  const size_t need = ufr_points_thin_workspace_bytes(n);
+  if (workspace_bytes < need) return fail(UFR_ERR_WORKSPACE, "ufr_points_thin: workspace %zu bytes, needs %zu", workspace_bytes, need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int* undecided = static_cast<int*>(workspace);
+  UFR_HIP(hipMemsetAsync(state, 0, (size_t)n, s));
+  long long prev = n;
+  int rounds = 0;
+  while (prev > 0) {       // every round decides at least the earliest undecided point: at most n rounds
+    if (rounds >= n) return fail(UFR_ERR_HIP, "ufr_points_thin: no fixpoint after %d rounds", rounds);
+    int und = 0;
+    UFR_HIP(hipMemsetAsync(undecided, 0, sizeof(int), s));
+    {
+      ProfScope p("points_thin_round", s);
+      UFR_HIP(launch_thin_round(points, reinterpret_cast<const long long*>(keys), rank, n, radius, state, undecided, s));
+    }
+    UFR_HIP(hipMemcpyAsync(&und, undecided, sizeof(int), hipMemcpyDeviceToHost, s));
+    UFR_HIP(hipStreamSynchronize(s));
+    ++rounds;
+    if (und < 0 || und >= prev)
+      return fail(UFR_ERR_HIP, "ufr_points_thin: round %d left %d of %lld points undecided (rank is not a permutation?)", rounds, und,
+                  prev);
+    prev = und;
+  }
+  if (rounds_host) *rounds_host = rounds;
+  return UFR_OK;
+}
+
+size_t ufr_points_nn_dist_workspace_bytes(int64_t nq) { return (nq >= 1 && nq <= kChMax) ? NnWorkspace(nullptr, nq).bytes : 0; }
+
+int ufr_points_nn_dist(const double* query, int64_t nq, const double* ref, const int64_t* ref_keys, int64_t nr,
+                       const double* origin, double cell, double max_dist, double* dist, double* mean_out, void* workspace,
+                       size_t workspace_bytes, ufr_stream stream) {
+  UFR_REQUIRE(query && ref && ref_keys && origin && dist && workspace, "ufr_points_nn_dist: null argument");
+  UFR_REQUIRE(nq >= 1 && nq <= kChMax && nr >= 1 && nr <= kChMax, "ufr_points_nn_dist: nq %lld, nr %lld (each must be 1 .. 2^31 - 1)",
+              (long long)nq, (long long)nr);
+  UFR_REQUIRE(cell > 0.0 && std::isfinite(cell) && std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]),
+              "ufr_points_nn_dist: cell %g, origin (%g, %g, %g) (cell must be positive, all finite)", cell, origin[0], origin[1],
+              origin[2]);
+  UFR_REQUIRE(max_dist > 0.0 && max_dist < 1e150, "ufr_points_nn_dist: max_dist %g (must be positive, below 1e150)", max_dist);
+  const size_t need = NnWorkspace(nullptr, nq).bytes;
+  if (workspace_bytes < need) return fail(UFR_ERR_WORKSPACE, "ufr_points_nn_dist: workspace %zu bytes, needs %zu", workspace_bytes, need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  NnWorkspace w(workspace, nq);
+  ProfScope p("points_nn_dist", s);
+  UFR_HIP(launch_nn_dist(query, nq, ref, reinterpret_cast<const long long*>(ref_keys), nr, origin, cell, max_dist, dist, w.block_sum,
+                         w.block_cnt, mean_out, s));
+  return UFR_OK;
+}
+
 int ufr_pixelwise_view_weights(const float* similarity, const float* params, float* view_weights, float* aggregated, int32_t NS,
                                int32_t D, int32_t H, int32_t W, ufr_stream stream) {
   UFR_REQUIRE(similarity && params && view_weights, "ufr_pixelwise_view_weights: null argument");

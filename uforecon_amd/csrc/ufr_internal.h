@@ -141,6 +141,22 @@ hipError_t launch_mcubes_verts(const float* vol, const int* dim, float level, co
                                float* verts, float* normals, long long n_verts, hipStream_t s);
 hipError_t launch_mcubes_faces(const float* vol, const int* dim, float level, const long long* tile_off, const int* index,
                                int* faces, long long n_faces, hipStream_t s);
+// chamfer.hip: DTU chamfer evaluation in fp64 (mesh sampling, cell keys, thinning rounds, nearest neighbours; see the file header)
+long long chamfer_blocks(long long n);   // blocks of the per-item kernels: sizes the per-block workspace arrays
+hipError_t launch_points_cell_keys(const double* pts, long long n, const double* origin, double cell, long long* keys,
+                                   hipStream_t s);
+hipError_t launch_mesh_sample_count(const double* verts, const int* faces, long long V, long long F, double density,
+                                    long long* tri_off, long long* block_tot, hipStream_t s);
+hipError_t launch_mesh_sample_scan(const long long* block_tot, long long n_blocks, long long* block_off, long long* total,
+                                   hipStream_t s);
+hipError_t launch_mesh_sample_emit(const double* verts, const int* faces, long long V, long long F, double density,
+                                   const long long* tri_off, const long long* block_off, double* out, long long capacity,
+                                   hipStream_t s);
+hipError_t launch_thin_round(const double* pts, const long long* keys, const int* rank, long long n, double radius,
+                             unsigned char* state, int* undecided, hipStream_t s);
+hipError_t launch_nn_dist(const double* query, long long nq, const double* ref, const long long* keys, long long nr,
+                          const double* origin, double cell, double max_dist, double* dist, double* block_sum,
+                          long long* block_cnt, double* mean_out, hipStream_t s);
 // conv2d.hip: the plain 2-D convolutions of FeatureNet on channel-last tensors, epilogue fused (see the file header)
 struct Conv2dArgs {
   const float* in;      // [B][H][W][CIN] (the stem: planar [B][3][H][W])

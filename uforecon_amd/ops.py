@@ -765,6 +765,137 @@ def marching_cubes_table():
 MC_TABLE_ROW = 16   # UFR_MC_TABLE_ROW of include/ufr.h
 
 
+# ---- DTU chamfer evaluation (csrc/chamfer.hip; uforecon_amd/dtu_eval.py strings these together)
+def _points64(t: torch.Tensor, name: str) -> int:
+    p = _dev(t, name, torch.float64)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise UfrError(f"{name}: expected shape (N, 3), got {tuple(t.shape)}")
+    if t.shape[0] >= 2 ** 31:
+        raise UfrError(f"{name}: {t.shape[0]} points: 2^31 or more")
+    return p
+
+
+def _finite_bounds(t: torch.Tensor, name: str):
+    mn, mx = t.min(0).values, t.max(0).values
+    if not bool(torch.isfinite(mn).all() and torch.isfinite(mx).all()):
+        raise UfrError(f"{name}: contains NaN or infinite coordinates")
+    return mn, mx
+
+
+def cell_keys(points: torch.Tensor, origin, cell: float) -> torch.Tensor:
+    """ufr_points_cell_keys: the int64 Morton key of every point's grid cell (floor((p - origin) / cell), 21 bits per axis,
+    clamped).  ``points`` (N,3) CUDA float64; ``origin`` three floats."""
+    p = _points64(points, "points")
+    keys = torch.empty(points.shape[0], dtype=torch.int64, device=points.device)
+    if points.shape[0]:
+        o = (C.c_double * 3)(*[float(v) for v in origin])
+        _lib.check(_lib.load().ufr_points_cell_keys(p, points.shape[0], o, float(cell), keys.data_ptr(), _stream()),
+                   "ufr_points_cell_keys")
+    return keys
+
+
+def sample_mesh(verts: torch.Tensor, faces: torch.Tensor, density: float) -> torch.Tensor:
+    """The point cloud dtu_eval.py:68-91 makes of a mesh: the vertices, then the points sampled on every triangle at
+    ``density`` in (triangle, i, j) order (include/ufr.h, ufr_mesh_sample_*).  ``verts`` (V,3) CUDA float64, ``faces`` (F,3)
+    CUDA int32 with every index in 0..V-1.  One host synchronisation (the count sizes the output)."""
+    pv = _points64(verts, "verts")
+    pf = _dev(faces, "faces", torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if F == 0 or V == 0:
+        if F:
+            raise UfrError("sample_mesh: faces without vertices")
+        return verts.clone()
+    if int(faces.min()) < 0 or int(faces.max()) >= V:
+        raise UfrError(f"sample_mesh: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
+    lib = _lib.load()
+    nbytes = lib.ufr_mesh_sample_workspace_bytes(F)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
+    total = C.c_int64(0)
+    _lib.check(lib.ufr_mesh_sample_count(pv, pf, V, F, float(density), ws.data_ptr(), nbytes, C.byref(total), _stream()),
+               "ufr_mesh_sample_count")
+    M = int(total.value)
+    if V + M >= 2 ** 31:
+        raise UfrError(f"sample_mesh: {V} vertices + {M} samples: 2^31 points or more")
+    out = torch.empty((V + M, 3), dtype=torch.float64, device=verts.device)
+    out[:V] = verts
+    if M:
+        _lib.check(lib.ufr_mesh_sample_emit(pv, pf, V, F, float(density), ws.data_ptr(), nbytes, out[V:].data_ptr(), M, _stream()),
+                   "ufr_mesh_sample_emit")
+    return out
+
+
+def thin_points(points: torch.Tensor, radius: float, return_rounds: bool = False):
+    """The keep-mask of dtu_eval.py:105-115 (bool, (N,)): in the order of ``points`` ((N,3) CUDA float64, already shuffled), a
+    point is kept iff no earlier kept point lies within ``radius`` (inclusive).  Exactly the sequential loop's result, run as
+    rounds of a fixpoint (include/ufr.h, ufr_points_thin); synchronises once per round."""
+    _points64(points, "points")
+    N = int(points.shape[0])
+    radius = float(radius)
+    if not (radius >= 0.0 and radius < float("inf")):
+        raise UfrError(f"thin_points: radius {radius}")
+    if N == 0:
+        keep = torch.zeros(0, dtype=torch.bool, device=points.device)
+        return (keep, 0) if return_rounds else keep
+    mn, mx = _finite_bounds(points, "points")
+    extent = float((mx - mn).max())
+    # cells no smaller than the radius (27 cells then hold every neighbour), and no more of them than the 21-bit keys hold
+    cell = max(radius * (1.0 + 1e-9), extent / float(2 ** 21 - 4))
+    if cell <= 0.0:
+        cell = 1.0
+    keys = cell_keys(points, (mn - cell).tolist(), cell)
+    keys, perm = torch.sort(keys)
+    pts = points[perm].contiguous()
+    rank = perm.to(torch.int32)
+    state = torch.empty(N, dtype=torch.uint8, device=points.device)
+    lib = _lib.load()
+    nbytes = lib.ufr_points_thin_workspace_bytes(N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+    rounds = C.c_int32(0)
+    _lib.check(lib.ufr_points_thin(pts.data_ptr(), keys.data_ptr(), rank.data_ptr(), N, radius, state.data_ptr(), ws.data_ptr(),
+                                   nbytes, C.byref(rounds), _stream()), "ufr_points_thin")
+    keep = torch.empty(N, dtype=torch.bool, device=points.device)
+    keep[perm] = state == 1
+    return (keep, int(rounds.value)) if return_rounds else keep
+
+
+def nn_distance(query: torch.Tensor, ref: torch.Tensor, max_dist: float, return_sums: bool = False):
+    """Distance from every ``query`` point to its nearest ``ref`` point ((N,3) CUDA float64 both): exact fp64 wherever it is
+    below ``max_dist``, some value >= ``max_dist`` (inf when nothing is near) elsewhere (include/ufr.h, ufr_points_nn_dist).
+    ``return_sums``: also a CUDA float64 pair (sum of the distances < max_dist, their count), summed in a fixed order."""
+    _points64(query, "query")
+    _points64(ref, "ref")
+    nq, nr = int(query.shape[0]), int(ref.shape[0])
+    max_dist = float(max_dist)
+    if not (0.0 < max_dist < 1e150):
+        raise UfrError(f"nn_distance: max_dist {max_dist}")
+    if nr == 0:
+        raise UfrError("nn_distance: empty reference set")
+    sums = torch.zeros(2, dtype=torch.float64, device=query.device)
+    if nq == 0:
+        dist = torch.zeros(0, dtype=torch.float64, device=query.device)
+        return (dist, sums) if return_sums else dist
+    mn, mx = _finite_bounds(ref, "ref")
+    extent = float((mx - mn).max())
+    cell = extent / float(2 ** 20) if extent > 0.0 else 1.0      # the octree is adaptive: the cell only sets its finest level
+    origin = (mn - cell).tolist()
+    rkeys, rperm = torch.sort(cell_keys(ref, origin, cell))
+    rpts = ref[rperm].contiguous()
+    qperm = torch.sort(cell_keys(query, origin, cell)).indices        # neighbouring queries share a wave
+    qpts = query[qperm].contiguous()
+    lib = _lib.load()
+    nbytes = lib.ufr_points_nn_dist_workspace_bytes(nq)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+    d = torch.empty(nq, dtype=torch.float64, device=query.device)
+    o = (C.c_double * 3)(*origin)
+    _lib.check(lib.ufr_points_nn_dist(qpts.data_ptr(), nq, rpts.data_ptr(), rkeys.data_ptr(), nr, o, cell, max_dist, d.data_ptr(),
+                                      sums.data_ptr(), ws.data_ptr(), nbytes, _stream()), "ufr_points_nn_dist")
+    dist = torch.empty_like(d)
+    dist[qperm] = d
+    return (dist, sums) if return_sums else dist
+
+
 CONV3D_S1, CONV3D_S2, CONV3D_T2 = 0, 1, 2
 
 
