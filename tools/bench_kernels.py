@@ -57,6 +57,15 @@ def main():
     tag = os.environ.get("UFR_LIB", "default").split("/")[-1]
     t = timeit(lambda: ops.project_gather(fh, W, ray_o, ray_d, z))
     print(f"[{tag}] gather            {t:8.3f} ms  {P / t / 1e6:8.2f} Gpt/s... ({P} points)")
+    if hasattr(lib, "ufr_debug_gather_phases"):  # -DUFR_PHASE_TIMING development build: wave 0, mean over all blocks
+        gbuf = (C.c_ulonglong * 32)()
+        lib.ufr_debug_gather_phases(gbuf, 32, 1)
+        gnames = ["phase A (narrow taps, PE)", "cooperative gathers", "frustum taps", "means + frustum blend", "pre_sim_mlp",
+                  "token assembly"]
+        gtot, gblocks = sum(gbuf[:6]), max(gbuf[6], 1)
+        for i, nm in enumerate(gnames):
+            print(f"   gather phase {nm:26s} {gbuf[i] / gblocks:9.0f} cyc/block  {100.0 * gbuf[i] / max(gtot, 1):5.1f} %")
+        print(f"   gather total {gtot / gblocks:.0f} cycle-counter ticks per block (wave 0, barrier waits included; {gblocks} blocks)")
     ops.profile_enable(True)
     for _ in range(5):
         lib.ufr_aggregate(W.packed.data_ptr(), x.data_ptr(), rgbm.data_ptr(), dirs.data_ptr(), RN, SN, NV,

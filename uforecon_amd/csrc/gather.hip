@@ -11,6 +11,8 @@
 // clock and was the kernel's limiter (r2 PMC: TCP busy ~100 %, 3.1e8 line accesses per 524 288 points).
 // All maps are channel-last (prep.hip).  Cross-view reductions (pair similarities, frustum blending) go
 // through LDS in the reference's summation order.
+#include <algorithm>
+#include <cstdlib>
 #include "ufr_device.h"
 #include "ufr_internal.h"
 #include "volume_sample.h"
@@ -128,17 +130,35 @@ __device__ __forceinline__ void presim_block(const PreSim& ps, const float* sim,
   for (int u = 0; u < 4; ++u) st4(out + (16 * u + j) * out_stride + 24 + 4 * g, o[u]);
 }
 
-// LDS layout (floats): sim[64][NPAIR][8] | { tapF[NV][64][8] | tapM[NV][64][8] } aliased with volp[64][NV-1][25] (views
-// >= 1; wave 0 keeps its own in registers: the frustums are sampled AFTER the cooperative gathers, when the footprints
-// are dead) | outv[64][40] -- which moves into the (then dead) similarity slots of its point when they are large enough
-// (NV >= 4: a slot is NPAIR * 8 >= 48 floats).  The footprint of a block bounds the CU's occupancy -- of this kernel, and
-// of the mix when it runs beside the transformer kernels of another chunk (side streams): 31 -> 29 KB at NV = 3 (no
-// effect: 4 blocks per CU are enough there), 66 -> 46 KB at NV = 5 (2 -> 3 blocks per CU).
+// LDS layout (floats): sim[64][NPAIR][8] | region 2, which holds in turn { tapF[NV][64][8] | tapM[NV][64][8] }, then
+// volp[64][NV-1][25] (views >= 1; wave 0 keeps its own in registers: the frustums are sampled AFTER the cooperative
+// gathers, when the footprints are dead), then outv[64][40] (NV <= 3: wave 0 alone reads the frustum partials, and writes
+// its points' rows only after its last lane has read them).  At NV >= 4 outv lies in the (by then dead) similarity slots
+// of its point instead: a slot is NPAIR * 8 >= 48 floats.  The footprint of a block bounds the CU's occupancy -- of this
+// kernel, and of the mix when it runs beside the transformer kernels of another chunk (side streams): 18.5 KB at NV = 3
+// (the LDS allows 8 blocks per CU, the registers 6: DESIGN.md 3.2), 46 KB at NV = 5 (3 blocks per CU).
+// Registers: the second launch bound keeps every instantiation within 96 VGPRs (5 waves per SIMD).  Without it the
+// compiler gave pre_sim_mlp's accumulators 64 AGPRs of their own at NV <= 4: 156-160 registers, 3 waves per SIMD
+// (tests/test_gather_registers.py).
 // NVT: the view count as a compile-time constant (round 5): the item / NV, item / npair divisions and the pair-index walk
 // of the cooperative loops sit in the address chains of the gathers; as run-time values they were 143 32-bit multiplies
 // and two ~20-instruction divisions per item.
+constexpr int kGatherMinW = 5;   // waves per SIMD the register budget is sized for
+
+#ifdef UFR_PHASE_TIMING  // development build: cycle counts per phase of every block's wave 0 (tools/bench_kernels.py prints them)
+__device__ unsigned long long g_gather_phase[32];
+#define UFR_G_PHASE(i)                                                                 \
+  {                                                                                    \
+    const unsigned long long t_now = __builtin_readcyclecounter();                     \
+    g_acc[i] = t_now - g_prev;                                                         \
+    g_prev = t_now;                                                                    \
+  }
+#else
+#define UFR_G_PHASE(i)
+#endif
+
 template <int NVT>
-__global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps, const float* __restrict__ ray_o,
+__global__ void __launch_bounds__(64 * NVT, kGatherMinW) gather_kernel(FrameDev f, PreSim ps, const float* __restrict__ ray_o,
                                                       int o_stride, const float* __restrict__ ray_d,
                                                       const float* __restrict__ zval, int P, int SN,
                                                       float* __restrict__ x_tokens, float* __restrict__ x_point,
@@ -157,9 +177,12 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
   float* sh_vol = sh_tapF;                     // 64*(NV-1)*25, written after the last footprint read
   constexpr int sim_slot = npair * 8;              // floats per point in sh_sim
   constexpr bool out_in_sim = sim_slot >= 48;      // [64][40] = frustum blend 24 | pre_sim_mlp 16 ...
-  constexpr int region2 = 2 * NV * 64 * 8 > 64 * (NV - 1) * 25 ? 2 * NV * 64 * 8 : 64 * (NV - 1) * 25;
-  float* sh_out = out_in_sim ? sh_sim + 8 : sh_tapF + region2;   // ... behind the point's 8 pre_sim_mlp inputs, or on its own
+  float* sh_out = out_in_sim ? sh_sim + 8 : sh_tapF;   // ... behind the point's 8 pre_sim_mlp inputs, or over region 2
   constexpr int out_stride = out_in_sim ? sim_slot : 40;
+#ifdef UFR_PHASE_TIMING
+  unsigned long long g_acc[8] = {};
+  unsigned long long g_prev = __builtin_readcyclecounter();
+#endif
 
   const int v = threadIdx.x >> 6, p = threadIdx.x & 63;
   const int vu = __builtin_amdgcn_readfirstlane(v);      // a wave = one view: per-view descriptors live in scalar registers
@@ -239,6 +262,7 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
   }
 
   __syncthreads();
+  UFR_G_PHASE(0)  // projection, footprints, colour / depth taps, depth PE, direction
 
   // ---- cooperative 32-channel gathers: lane group of 8 = one footprint, lane c8 = channels 4*c8..4*c8+3
   const int c8 = threadIdx.x & 7, grp = threadIdx.x >> 3;
@@ -278,6 +302,7 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
                                         (fa[2] * ra) * (fb[2] * rb) + (fa[3] * ra) * (fb[3] * rb);
   }
   __syncthreads();
+  UFR_G_PHASE(1)  // cooperative gathers: image features, pair similarities
 
   // ---- correlation frustums of view v (model.py:359-386); skipped when the caller supplies the blended lookup
   // (RayTransformer.forward receives it as `fea_volume`, ray_transformer.py:175, 199)
@@ -309,6 +334,7 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
     }
   }
   __syncthreads();
+  UFR_G_PHASE(2)  // frustum taps
 
   // ---- per-point reductions by wave 0: mean similarity, frustum blend, pre_sim_mlp
   if (v == 0) {
@@ -320,7 +346,6 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
       sim[gi] = s / (float)npair;                                                 // torch.mean over pairs
       if (sim8_in) sim[gi] = sim8_in[(size_t)pc * 8 + gi];                        // cond_info['feat_info'] given
     }
-    float* ov = sh_out + p * out_stride;
     {
       float Wsum = own[24];                                                       // view 0 first, then 1..NV-1
       for (int n = 1; n < NV; ++n) Wsum += sh_vol[(p * (NV - 1) + n - 1) * 25 + 24];
@@ -329,39 +354,62 @@ __global__ void __launch_bounds__(64 * NVT) gather_kernel(FrameDev f, PreSim ps,
       for (int c = 0; c < 24; ++c) {
         float G = own[c];
         for (int n = 1; n < NV; ++n) G += sh_vol[(p * (NV - 1) + n - 1) * 25 + c];
-        ov[c] = G * rW;                                                           // model.py:388
-        if (vol24_in) ov[c] = vol24_in[(size_t)pc * 24 + c];
+        own[c] = G * rW;                                                          // model.py:388
+        if (vol24_in) own[c] = vol24_in[(size_t)pc * 24 + c];
       }
     }
-    // pre_sim_mlp of the block's 64 points on this wave's matrix core (presim_tile below): the similarities change
-    // from "thread p holds point p" to the MFMA operand layout through the point's own (now dead) sh_sim slots
-    {
-      float* mine = sh_sim + p * npair * 8;
-      st4(mine, f32x4{sim[0], sim[1], sim[2], sim[3]});
-      st4(mine + 4, f32x4{sim[4], sim[5], sim[6], sim[7]});
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      presim_block(ps, sh_sim, sim_slot, sh_out, out_stride, p);
-    }
-    if (active && sim8_out) {
+    // sh_sim and sh_vol are dead once every lane of this wave has read its point (no other wave reads them): the means go
+    // to the first 8 floats of the point's similarity slot (pre_sim_mlp's input), the blend to its sh_out row
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float* mine = sh_sim + p * sim_slot;
+    st4(mine, f32x4{sim[0], sim[1], sim[2], sim[3]});
+    st4(mine + 4, f32x4{sim[4], sim[5], sim[6], sim[7]});
+    float* ov = sh_out + p * out_stride;
 #pragma unroll
-      for (int gi = 0; gi < 8; ++gi) sim8_out[(size_t)pidx * 8 + gi] = sim[gi];
-    }
-    if (active && vol24_out) {
-      for (int c = 0; c < 24; ++c) vol24_out[(size_t)pidx * 24 + c] = ov[c];
-    }
+    for (int c = 0; c < 24; c += 4) st4(ov + c, f32x4{own[c], own[c + 1], own[c + 2], own[c + 3]});
+    UFR_G_PHASE(3)  // similarity means, frustum blend
+    // pre_sim_mlp of the block's 64 points on this wave's matrix core: the similarities change from "thread p holds point
+    // p" to the MFMA operand layout through LDS.  (Dealing the four tiles over the waves was measured and is slower: every
+    // wave then loads the layer weights, and a wave with one tile has one accumulate chain: DESIGN.md section 7.)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    presim_block(ps, sh_sim, sim_slot, sh_out, out_stride, p);
   }
   __syncthreads();
+  UFR_G_PHASE(4)  // pre_sim_mlp
 
-  // ---- token assembly: [feat 32 | vol 24 | sim 16 | depth PE 8] (ray_transformer.py:258-281)
-  // (public layout: the per-point columns go into every view's row; compact: once, by view 0's thread)
-  if (active && (!x_point || v == 0)) {
-    const float* ov = sh_out + p * out_stride;
-    float* dst = x_point ? x_point + (size_t)pidx * kPointCols : xrow + 32;
-#pragma unroll
-    for (int c = 0; c < 40; c += 4) st4(dst + c, ld4(ov + c));   // frustum lookup 32..55, pre_sim_mlp output 56..71
+  // ---- token assembly: [feat 32 | vol 24 | sim 16 | depth PE 8] (ray_transformer.py:258-281): the block's sh_out rows,
+  // frustum lookup 32..55 | pre_sim_mlp output 56..71, copied by all its threads, consecutive lanes = consecutive 16 bytes
+  const int npts = P - blk * 64 < 64 ? P - blk * 64 : 64;    // the last block may be partial
+  if (x_point) {   // compact layout: once per point; the block's rows are one contiguous piece of x_point
+    float* dst = x_point + (size_t)blk * 64 * kPointCols;
+    for (int i = threadIdx.x; i < npts * 10; i += 64 * NV) {
+      const int ip = i / 10, c = i - ip * 10;
+      st4(dst + 4 * i, ld4(sh_out + ip * out_stride + 4 * c));
+    }
+  } else {         // public layout: the per-point columns go into every view's row
+    for (int i = threadIdx.x; i < npts * NV * 10; i += 64 * NV) {
+      const int row = i / 10, c = i - row * 10;
+      st4(x_tokens + ((size_t)blk * 64 * NV + row) * UFR_TOKEN_DIM + 32 + 4 * c, ld4(sh_out + (row / NV) * out_stride + 4 * c));
+    }
   }
+  if (vol24_out)
+    for (int i = threadIdx.x; i < npts * 24; i += 64 * NV) {
+      const int ip = i / 24;
+      vol24_out[(size_t)blk * 64 * 24 + i] = sh_out[ip * out_stride + (i - ip * 24)];
+    }
+  if (sim8_out)
+    for (int i = threadIdx.x; i < npts * 8; i += 64 * NV) sim8_out[(size_t)blk * 64 * 8 + i] = sh_sim[(i >> 3) * sim_slot + (i & 7)];
+  UFR_G_PHASE(5)  // token assembly
+#ifdef UFR_PHASE_TIMING
+  if (threadIdx.x == 0) {
+    for (int i = 0; i < 6; ++i) atomicAdd(&g_gather_phase[i], g_acc[i]);
+    atomicAdd(&g_gather_phase[6], 1ull);   // blocks counted
+  }
+#endif
 }
 
 hipError_t launch_gather(const FrameDev& f, const PreSim& ps, const float* ray_o, int o_stride, const float* ray_d,
@@ -371,7 +419,7 @@ hipError_t launch_gather(const FrameDev& f, const PreSim& ps, const float* ray_o
   const int P = RN * SN, NV = f.NV;
   const int npair = NV * (NV - 1) / 2;
   const size_t taps = 2 * (size_t)NV * 64 * 8, volp = (size_t)64 * (NV - 1) * 25, outv = npair * 8 >= 48 ? 0 : 64 * 40;
-  size_t lds = sizeof(float) * ((size_t)64 * npair * 8 + (taps > volp ? taps : volp) + outv);
+  size_t lds = sizeof(float) * ((size_t)64 * npair * 8 + std::max(std::max(taps, volp), outv));
   switch (NV) {
 #define UFR_GATHER_CASE(N)                                                                                                   \
     case N:                                                                                                                  \
@@ -386,3 +434,16 @@ hipError_t launch_gather(const FrameDev& f, const PreSim& ps, const float* ray_o
 }
 
 }  // namespace ufr
+
+#ifdef UFR_PHASE_TIMING
+extern "C" int ufr_debug_gather_phases(unsigned long long* out, int n, int reset) {
+  unsigned long long h[32] = {};
+  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ufr::g_gather_phase), sizeof(h)) != hipSuccess) return -1;
+  for (int i = 0; i < n && i < 32; ++i) out[i] = h[i];
+  if (reset) {
+    unsigned long long z[32] = {};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(ufr::g_gather_phase), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#endif
