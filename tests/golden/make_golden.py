@@ -415,9 +415,57 @@ def run_costreg_grad_case(name, c, weight_seed=0, sampler_seed=1):
     print(f"{name}: loss {float(loss):.6f}, {len(out)} arrays, {os.path.getsize(os.path.join(HERE, name + '.npz')) / 1e6:.2f} MB")
 
 
+# the gather's rows on rays that leave the fixtures' comfortable geometry (tests/gather_ref.py: tilted off the render view's
+# axis, started behind the camera arc, z beyond near_fars): the reference evaluates GIVEN points through sample2rgb
+ROWS_OFFAXIS = dict(NVS=(3, 5), RN=6, SN=24)
+
+
+def run_rows_offaxis(name="rows_offaxis", weight_seed=0):
+    sys.path.insert(0, os.path.dirname(HERE))
+    import gather_ref as G
+
+    c = ROWS_OFFAXIS
+    out = {"weight_seed": np.int64(weight_seed)}
+    for NV in c["NVS"]:
+        model = build_reference_model(weight_seed, test_n_view=NV, extract_geometry=True)
+        fr = G.frame_for(NV)
+        ray_o, ray_d, z = G.offaxis_rays(fr, c["RN"], c["SN"], NV, True)
+        pts = G.points(ray_o, ray_d, z)
+        cap = {}
+        orig_qci, orig_qdv = model.query_cond_info, model.query_depth_from_volume
+
+        def qci(*a, **k):
+            r = orig_qci(*a, **k)
+            cap["sim8"], cap["xy"], cap["mask_z"] = r[0]["feat_info"][0].detach().clone(), r[1][0].detach().clone(), r[2][0].detach().clone()
+            return r
+
+        def qdv(*a, **k):
+            r = orig_qdv(*a, **k)
+            cap["vol24"] = r[0].detach().clone()
+            return r
+
+        h = model.ray_transformer.density_view_transformer.register_forward_hook(
+            lambda mod, inp, o: cap.__setitem__("x_tokens", inp[0].detach().clone()))
+        model.query_cond_info, model.query_depth_from_volume = qci, qdv
+        with torch.no_grad():
+            model.sample2rgb(fr.batch, pts[None], z[None], ray_d, torch.zeros(1, c["RN"], dtype=torch.long), fr.source_imgs_feat,
+                             fr.feature_volume, fr.match_feature)
+        h.remove()
+        model.query_cond_info, model.query_depth_from_volume = orig_qci, orig_qdv
+        out[f"nv{NV}.input_digest"] = np.float64(frame_digest(fr))
+        out[f"nv{NV}.pts"] = pts.numpy()
+        out[f"nv{NV}.x"] = cap["x_tokens"][:, 1:].numpy()           # without the view token
+        for k in ("xy", "mask_z", "sim8", "vol24"):
+            out[f"nv{NV}.{k}"] = cap[k].numpy()
+    np.savez_compressed(os.path.join(HERE, f"{name}.npz"), **out)
+    print(f"{name}: {len(out)} arrays, {os.path.getsize(os.path.join(HERE, name + '.npz')) / 1e6:.2f} MB")
+
+
 def main():
     model = None
     only = sys.argv[1:]
+    if not only or "rows_offaxis" in only:
+        run_rows_offaxis()
     for name, c in COSTREG_CASES.items():
         if only and name not in only:
             continue

@@ -284,18 +284,37 @@ def test_side_streams_are_invisible(weights):
                 assert torch.equal(out[k], base[k]), (chunk, streams, k)
 
 
-def test_fine_pass_pool_equals_full_reevaluation(weights):
+# (NV, SN, PN, RN, chunk_rays): the first is the 64+64 case at NV = 3 this test began with (the frame of c2_hier_small).  The
+# others: every view count; sample and ray counts whose point totals RN*SN and RN*PN are not multiples of the gather's
+# 64-point blocks (37 x 48 = 27 blocks + 48, 37 x 16 = 9 blocks + 16; 3 x 16 = 48 < 64; 5 x 32 = 2 blocks + 32), so the
+# compact x_point layout -- which only ufr_render_rays uses -- is written by partial blocks; and chunked workspaces whose
+# chunks end in a partial block (10 rays x 48 = 7.5 blocks, 10 x 16 = 2.5).
+FINE_PASS_CASES = ([(3, 64, 64, 256, 0)] + [(NV, 64, 64, 24, 0) for NV in (2, 4, 5, 6, 7)]
+                   + [(NV, 48, 16, 37, 0) for NV in (2, 3, 4, 5, 6, 7)]
+                   + [(4, 16, 16, 3, 0), (7, 16, 16, 3, 0), (2, 64, 32, 5, 0), (5, 64, 32, 5, 0)]
+                   + [(3, 48, 16, 37, 10), (4, 48, 16, 37, 10), (6, 48, 16, 37, 10)])
+
+
+@pytest.mark.parametrize("NV,SN,PN,RN,chunk", FINE_PASS_CASES)
+def test_fine_pass_pool_equals_full_reevaluation(NV, SN, PN, RN, chunk, weights):
     """ufr_render_rays keeps the coarse samples' per-point results and evaluates only the new points in the
     fine pass; the reference (model.py:466-472) re-evaluates all merged samples.  Walking the reference's order
     through the stepwise entry points gives the same bits: a point's gathers and view-transformer output depend
-    on that point alone."""
-    fr, idx, U1, U2, g = case_inputs("c2_hier_small")
-    f = fr.to(DEV)
+    on that point alone.  ufr_render_rays reads the gather's compact x_point layout, the stepwise calls the public
+    80-column rows: the two layouts hold the same bits at every view count, in partial blocks and across chunks."""
+    from uforecon_amd.scene import make_frame, sampler_uniforms
+
+    if (NV, SN, PN, RN) == (3, 64, 64, 256):
+        fr, idx, U1, U2, g = case_inputs("c2_hier_small")
+    else:
+        fr = make_frame(48, 64, NV, seed=70 + NV)
+        idx = ((torch.arange(RN) * 79 + 131) % (48 * 64))[None]
+        U1, U2 = sampler_uniforms(11, SN, PN, RN)
     fh = _frame_handle(fr)
     ray_o, ray_d, near, far = (t.to(DEV) for t in _ray_setup(fr, idx))
     var = weights.variance
     z1 = ops.sample_fixed(near, far, U1.to(DEV))
-    RN, SN = z1.shape
+    assert tuple(z1.shape) == (RN, SN)
     x, rgbm, dirs, _ = ops.project_gather(fh, weights, ray_o, ray_d, z1)
     rad1, srdf1, _ = ops.aggregate(weights, x, rgbm, dirs, RN, SN)
     _, _, _, w1 = ops.composite(z1, rad1, srdf1, var)
@@ -304,7 +323,8 @@ def test_fine_pass_pool_equals_full_reevaluation(weights):
     x, rgbm, dirs, _ = ops.project_gather(fh, weights, ray_o, ray_d, z2)         # all SN+PN merged samples
     rad2, srdf2, _ = ops.aggregate(weights, x, rgbm, dirs, RN, S2)
     rgb2, depth2, _, _ = ops.composite(z2, rad2, srdf2, var)
-    out = ops.render_rays(fh, weights, idx.to(DEV), U1.to(DEV), U2.to(DEV))
+    ws = ops.RenderWorkspace(DEV, SN, PN, NV, chunk_rays=chunk) if chunk else None
+    out = ops.render_rays(fh, weights, idx.to(DEV), U1.to(DEV), U2.to(DEV), workspace=ws)
     assert torch.equal(out["z_all"], z2)
     assert torch.equal(out["srdf"], srdf2)
     assert torch.equal(out["depth"], depth2) and torch.equal(out["rgb"], rgb2)

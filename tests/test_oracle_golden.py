@@ -71,6 +71,33 @@ def test_rows_match_reference_golden():
         assert rel_err(w["rgb"], g[f"{tag}.rgb"]) < EXACT
 
 
+def test_offaxis_rows_match_reference_golden():
+    """The goldens above pin the oracle on in-view rays only.  rows_offaxis.npz holds the reference's own rows (sample2rgb on
+    given points) on the off-axis ray set of tests/gather_ref.py at NV = 3 and 5: samples behind source cameras, outside
+    the images, outside every frustum.  Same bound as the rows above."""
+    import gather_ref as G
+    from helpers import load_golden
+    from uforecon_amd.scene import frame_digest
+
+    g = load_golden("rows_offaxis")
+    P = load_weights()
+    for NV in (3, 5):
+        fr = G.frame_for(NV)
+        dig = frame_digest(fr)
+        assert abs(dig - float(g[f"nv{NV}.input_digest"])) <= 1e-9 * abs(dig)
+        RN, SN = g[f"nv{NV}.pts"].shape[:2]
+        o, d, z = G.offaxis_rays(fr, RN, SN, NV, True)
+        w = G.rows(P, fr, o, d, z, torch.float32)
+        assert rel_err(w["pts"], g[f"nv{NV}.pts"]) == 0.0
+        s = G.geometry_shares(G.rows(P, fr, o, d, z))
+        assert s["behind"] > 0.02 and s["outside_image"] > 0.2 and s["all_outside"] > 0.05, s
+        assert rel_err(w["xy"], g[f"nv{NV}.xy"]) < EXACT
+        assert rel_err(w["mask_z"], g[f"nv{NV}.mask_z"]) == 0.0
+        assert rel_err(w["sim8"], g[f"nv{NV}.sim8"]) < EXACT
+        assert rel_err(w["vol24"], g[f"nv{NV}.vol24"]) < EXACT
+        assert rel_err(w["x"], g[f"nv{NV}.x"]) < EXACT
+
+
 def test_train_layout_forward_matches_reference_golden():
     fr, idx, U1, U2, g = case_inputs("c5_train_fwd")
     P = load_weights()

@@ -283,9 +283,9 @@ def project_gather(frame: FrameHandle, weights: PackedWeights, ray_o: torch.Tens
         rgb = torch.empty(P, NV, 4, dtype=torch.float32, device=dev)
         dirs = torch.empty(P, NV, 4, dtype=torch.float32, device=dev)
     dbg = {}
-    if debug:
-        dbg = dict(sim8=torch.empty(P, 8, device=dev), vol24=torch.empty(P, 24, device=dev),
-                   xy=torch.empty(NV, P, 2, device=dev), mask_z=torch.empty(NV, P, device=dev))
+    if debug:       # NaN-filled: a row the kernel leaves unwritten must not pass by holding an earlier call's values
+        nan = lambda *shape: torch.full(shape, float("nan"), device=dev)
+        dbg = dict(sim8=nan(P, 8), vol24=nan(P, 24), xy=nan(NV, P, 2), mask_z=nan(NV, P))
     else:
         if sim8_out is not None:   # ... into a row range of the two-pass step's pool
             dbg["sim8"] = sim8_out
