@@ -1,0 +1,328 @@
+"""Float64 yardsticks and seeded inputs of the forward hot path: both transformers with their heads, the compositor with
+its adjoint, the importance sampler with its merge.
+
+Everything here runs on the CPU.  tests/test_forward_refs.py keeps the conditioning of these inputs true on any host (the
+float32 oracle's own distance from float64 stays below caps that sit under the GPU bounds); tests/test_gpu_forward_rows.py
+and tests/test_gpu_compositor_sampler.py compare the HIP kernels with the same float64 results.
+
+A bound of a GPU test is ``max(project bound, 2 x the float32 oracle's distance from float64 on that case)`` (``bound``),
+the rule of test_aggregate_rows_weight_magnitudes.
+"""
+from __future__ import annotations
+
+import functools
+import math
+
+import torch
+
+from helpers import load_weights, rel_err
+from oracle import ufo_oracle as O
+from uforecon_amd.scene import make_frame
+
+# ------------------------------------------------------------------ metrics
+RGB_FLOOR = 0.05        # the floor of the project's RGB checks (test_gpu_parity: max_rel_elem(..., floor=0.05))
+
+
+def row_errs(got, ref, floor: float = 1e-30) -> torch.Tensor:
+    """Per row of a (..., C) tensor: max |got - ref| / max(max |ref|, floor) over that row.  -> (rows,) float64."""
+    ref = torch.as_tensor(ref).double().cpu()
+    got = torch.as_tensor(got).double().cpu().reshape(ref.shape)
+    C = ref.shape[-1]
+    d = (got - ref).abs().reshape(-1, C).amax(1)
+    return d / ref.abs().reshape(-1, C).amax(1).clamp_min(floor)
+
+
+def row_err(got, ref, floor: float = 1e-30) -> float:
+    """The worst row of row_errs: an error confined to one token slot or one padding column shows here at the size it has
+    against that row, where a whole-tensor maximum measures it against the largest row of the tensor."""
+    return float(row_errs(got, ref, floor).max())
+
+
+def bound(base: float, yardstick: float) -> float:
+    return max(base, 2.0 * yardstick)
+
+
+# ------------------------------------------------------------------ transformer rows
+# (NV, SN, RN): every view count; one ray tile (16), odd and even tile counts, the API's largest SN, both branches of the
+# 1/SN scaling (a power of two multiplies, any other SN divides); RN of 1, 3, 4, 5 leaves 3, 1, 0, 3 idle waves in the last
+# 4-ray workgroup
+AGG_SHAPES = [(2, 16, 5), (3, 48, 3), (4, 80, 3), (5, 112, 3), (6, 240, 1), (7, 32, 4), (3, 256, 1), (5, 16, 1)]
+MASKS = ("gathered", "all_masked", "one_unmasked")
+ROW_BOUNDS = dict(view_out=2e-5, ray_out=2e-5, radiance=2e-5, srdf=5e-5)      # the bounds of test_aggregate_rows
+ROW_FLOORS = dict(radiance=RGB_FLOOR)
+POINTS = 45             # more than four waves of the widest view-transformer instantiation (4 x 10 points at NV = 2)
+
+
+@functools.lru_cache(maxsize=None)
+def frame(NV: int):
+    return make_frame(48, 64, NV, seed=40 + NV, train_layout=True)
+
+
+def ray_inputs(NV: int, RN: int, SN: int, seed: int):
+    """(ray_o (3,), ray_d (RN,3), near (RN,), far (RN,), U (SN,RN)) of RN seeded rays of frame(NV), on the CPU."""
+    fr = frame(NV)
+    g = torch.Generator().manual_seed(100 + seed)
+    idx = torch.randperm(48 * 64, generator=g)[:RN]
+    ray_d = fr.batch["ray_d"][0][:, idx].t().contiguous()
+    ray_o = fr.batch["ray_o"][0].contiguous()
+    near = fr.batch["near_fars"][0, 0, 0].expand(RN).contiguous()
+    far = fr.batch["near_fars"][0, 0, 1].expand(RN).contiguous()
+    return ray_o, ray_d, near, far, torch.rand(SN, RN, generator=g)
+
+
+def oracle_tokens(NV: int, RN: int, SN: int, seed: int):
+    """(x (P,NV,80), rgbm (P,NV,4), dirs (P,NV,4)) in the kernels' layout from the ORACLE's gather: what the GPU tests take
+    from the HIP gather on the same rays, for the tests that run without a GPU."""
+    fr = frame(NV)
+    b = fr.batch
+    ray_o, ray_d, near, far, U = ray_inputs(NV, RN, SN, seed)
+    P = load_weights()
+    with torch.no_grad():
+        pts, _ = O.fixed_sample(ray_o[None].expand(RN, 3), ray_d, near, far, U)
+        poses = b["source_poses"][0]
+        xy, _, mask_z = O.project(poses, pts)
+        sim8 = O.pair_similarity(xy, fr.match_feature[0][0], NV)
+        vol24 = O.volume_lookup(poses, pts, fr.feature_volume, b["near_fars"][0][0])
+        x, rgb, dirs, mask = O.gather_inputs(P, pts, b, fr.source_imgs_feat[0], vol24, sim8, xy, mask_z,
+                                             b["start_idx"] if "start_idx" in b else 1)
+    rgbm = torch.cat([rgb.permute(2, 3, 0, 1).reshape(RN * SN, NV, 3), mask.permute(1, 2, 0).reshape(RN * SN, NV, 1)], -1)
+    dirs = torch.cat([dirs.permute(1, 2, 0, 3).reshape(RN * SN, NV, 3), torch.zeros(RN * SN, NV, 1)], -1)
+    return x.contiguous(), rgbm.contiguous(), dirs.contiguous()
+
+
+def force_masks(rgbm: torch.Tensor, masks: str) -> torch.Tensor:
+    """The forced masks of the backward tests (_view_inputs), in place on rgbm (P,NV,4): 'all_masked' = every view masked
+    on every other point, 'one_unmasked' = exactly view ``point % NV`` unmasked on every other point, 'gathered' = as they
+    come.  -> the forced points."""
+    P, NV = rgbm.shape[:2]
+    pts = torch.arange(0, P, 2, device=rgbm.device)
+    if masks == "gathered":
+        return pts[:0]
+    assert masks in ("all_masked", "one_unmasked"), masks
+    rgbm[pts, :, 3] = 0.0
+    if masks == "one_unmasked":
+        rgbm[pts, pts % NV, 3] = 1.0
+    return pts
+
+
+def alternate_masks(rgbm: torch.Tensor):
+    """Point i: as gathered (i % 3 == 0), every view masked (1), only view ``i % NV`` unmasked (2).  In place."""
+    P, NV = rgbm.shape[:2]
+    i = torch.arange(P, device=rgbm.device)
+    forced = i[i % 3 != 0]
+    rgbm[forced, :, 3] = 0.0
+    one = i[i % 3 == 2]
+    rgbm[one, one % NV, 3] = 1.0
+    return i[i % 3 == 1], one
+
+
+def mask_census(rgbm: torch.Tensor):
+    """(points with every view masked, points with exactly one view left)"""
+    n = (rgbm[..., 3] != 0).sum(1)
+    return int((n == 0).sum()), int((n == 1).sum())
+
+
+def aggregate_ref(x, rgbm, dirs, RN: int, SN: int, dtype=torch.float64, weights=None) -> dict:
+    """The oracle's rows on CPU float32 inputs in the kernels' layout, evaluated in ``dtype``:
+    view_out (P,NV+1,80), ray_out (RN,SN,88), radiance (P,3), srdf (RN,SN)."""
+    P = {k: v.to(dtype) for k, v in (weights or load_weights()).items()}
+    c = lambda t: t.detach().cpu().to(dtype)
+    want = {}
+    with torch.no_grad():
+        radiance, srdf = O.aggregate_tokens(P, c(x), c(rgbm[..., :3]), c(rgbm[..., 3]), c(dirs[..., :3]), RN, SN, want=want)
+    return dict(view_out=want["view_out"], ray_out=want["ray_out"], radiance=radiance, srdf=srdf)
+
+
+def view_ref(x, rgbm, dirs, dtype=torch.float64) -> dict:
+    """The view half at an arbitrary point count (one 'ray' of P samples; the ray half is ignored):
+    token0 (P,80), radiance (P,3)."""
+    r = aggregate_ref(x, rgbm, dirs, 1, x.shape[0], dtype)
+    return dict(token0=r["view_out"][:, 0], radiance=r["radiance"])
+
+
+def errors(got: dict, ref: dict) -> dict:
+    """{name: (helpers.rel_err over the whole tensor, worst row)} for the names of ``ref`` that ``got`` holds"""
+    return {k: (rel_err(got[k].reshape(ref[k].shape), ref[k]), row_err(got[k], ref[k], ROW_FLOORS.get(k, 1e-30)))
+            for k in ref if k in got}
+
+
+# ------------------------------------------------------------------ compositor
+COMPOSITE_SN = (2, 3, 17, 63, 64, 65, 96, 129, 200, 255, 256)      # a lane owns ceil(SN / 64) consecutive samples
+COMPOSITE_VARIANCE = (0.0, 0.3, 0.6, 0.9)                          # inv_s = exp(10 variance): 1 .. 8103
+COMPOSITE_CLIP_SN = (17, 64, 200)
+COMPOSITE_RN = 5
+CLIP_HIGH, CLIP_LOW = 1.5, -1.5                                    # exp(15) > 1e6, exp(-15) < 1e-6: inv_s sits on its clip
+COMPOSITE_FWD = ("weight", "rgb", "depth", "opacity")
+COMPOSITE_BOUNDS = dict(weight=5e-6, rgb=5e-6, depth=5e-6, opacity=5e-6, d_radiance=1e-5, d_srdf=1e-4, d_variance=1e-4)
+DVAR_RESOLVED = 5e-5        # the cap of tests/test_forward_refs.py on the float32 oracle's d_variance
+DVAR_NEGLIGIBLE = 1e-6      # |d_variance| below this share of its float32 resolution scale (dvar_scale): no relative check
+
+
+# The seed of each SN: the first of 7000 + SN + 1000 k at which the float32 ORACLE stays within 0.7 x the caps of
+# tests/test_forward_refs.py at every variance, with a d_variance above its float32 resolution (dvar_scale) up to variance 0.6 for SN >= 63 (searched on
+# the CPU, on the reference alone).  Most draws fail that: at
+# variance 0 and SN >= 200 float32 loses 1e-5 of d_srdf to the cancellation in pc - nc, and at variance 0.9 a draw
+# without a sample inside a sigmoid's transition (|srdf| < 4e-4) has a d_srdf tensor made of the sigmoids' tails alone
+# (1 - nc ~ 1e-8, scale 1e-4), which float32 cannot represent at all: no implementation can be judged against that.
+COMPOSITE_SEEDS = {2: 10002, 3: 8003, 17: 7017, 63: 11063, 64: 8064, 65: 7065, 96: 9096, 129: 10129, 200: 129200,
+                   255: 115255, 256: 189256}
+
+
+@functools.lru_cache(maxsize=None)
+def composite_inputs(SN: int, RN: int = COMPOSITE_RN) -> dict:
+    """Surface crossings in both directions, one zero gap (equal neighbours) on ray 0, random colours and cotangents."""
+    g = torch.Generator().manual_seed(COMPOSITE_SEEDS[SN])
+    r = lambda *s: torch.rand(*s, generator=g)
+    z = torch.sort(r(RN, SN) * 2 + 2, dim=1)[0]
+    j = max(1, SN // 2)
+    z[0, j] = z[0, j - 1]
+    phase = r(RN, 1) * (2 * math.pi)
+    srdf = 0.25 * torch.cos(3 * (z - 2) + phase) + 0.02 * (r(RN, SN) - 0.5)
+    return dict(z=z, srdf=srdf, radiance=r(RN, SN, 3), d_rgb=r(RN, 3), d_depth=r(RN), d_opacity=r(RN), d_weight=r(RN, SN))
+
+
+def composite_ref(c: dict, variance: float, dtype=torch.float64) -> dict:
+    """O.composite and its autograd in ``dtype``; dvar_scale (float64 only): see dvar_scale."""
+    t = {k: v.to(dtype) for k, v in c.items()}
+    srdf, rad = t["srdf"].clone().requires_grad_(True), t["radiance"].clone().requires_grad_(True)
+    var = torch.tensor(variance, dtype=dtype, requires_grad=True)
+    rgb, depth, opacity, w, _ = O.composite(t["z"], rad, srdf, var)
+    ((rgb * t["d_rgb"]).sum() + (depth * t["d_depth"]).sum() + (opacity * t["d_opacity"]).sum() + (w * t["d_weight"]).sum()).backward()
+    out = dict(weight=w.detach(), rgb=rgb.detach(), depth=depth.detach(), opacity=opacity.detach(), d_radiance=rad.grad,
+               d_srdf=srdf.grad, d_variance=float(var.grad))
+    if dtype == torch.float64:
+        out["dvar_scale"], w2 = dvar_scale(c, variance)
+        assert torch.equal(w2, out["weight"])       # the restatement below is the oracle's arithmetic
+    return out
+
+
+def dvar_scale(c: dict, variance: float):
+    """The float32 resolution of d_variance, for judging a value that is all cancellation or underflow.
+    d_variance = 10 inv_s sum_i (g_pc_i s'(prv_i inv_s) prv_i + g_nc_i s'(nxt_i inv_s) nxt_i), g_* the cotangents of the two
+    sigmoids and s' = s (1 - s).  A float32 sigmoid s carries an error of 2^-24 s (relative where it is small, absolute
+    where it has saturated at 1 -- there 1 - s is all error), and so does s': an error of d_variance is measured against
+    10 inv_s sum_i (|g_pc_i prv_i| pc_i + |g_nc_i nxt_i| nc_i), the terms with s in place of s'.  Where samples sit in a
+    sigmoid's transition that is a few times |d_variance| itself.  Where every sample has saturated the true value is e.g.
+    1e-22 or 1e-40, every s' has underflowed in float32, and 0.0 is the right answer.
+    -> (that sum, the weights of this restatement of renderer.py:19-42 with the sigmoids as leaves)."""
+    t = {k: v.double() for k, v in c.items()}
+    z = t["z"]
+    d = z[:, 1:] - z[:, :-1]
+    d = torch.cat([d[:, :1], d, d[:, -1:]], 1)
+    interval = (d[:, :-1] + d[:, 1:]) / 2
+    inv_s = torch.exp(torch.tensor(variance, dtype=torch.float64) * 10.0).clip(1e-6, 1e6)
+    nxt, prv = t["srdf"] + -1.5 * interval * 0.5, t["srdf"] - -1.5 * interval * 0.5
+    pc, nc = torch.sigmoid(prv * inv_s).requires_grad_(True), torch.sigmoid(nxt * inv_s).requires_grad_(True)
+    alpha = ((pc - nc + 1e-5) / (pc + 1e-5)).clip(0.0, 1.0)
+    T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1. - alpha + 1e-7], -1), -1)[:, :-1]
+    w = alpha * T
+    loss = ((t["radiance"] * w[:, :, None]).sum(1) * t["d_rgb"]).sum() + ((w * z).sum(1) * t["d_depth"]).sum() \
+        + (w.sum(1) * t["d_opacity"]).sum() + (w * t["d_weight"]).sum()
+    loss.backward()
+    return float(10.0 * inv_s * ((pc.grad * prv * pc).abs().sum() + (nc.grad * nxt * nc).abs().sum()).detach()), w.detach()
+
+
+@functools.lru_cache(maxsize=None)
+def composite_refs(SN: int, variance: float):
+    """(float64, float32) composite_ref of composite_inputs(SN): evaluated once, shared, left unchanged"""
+    c = composite_inputs(SN)
+    return composite_ref(c, variance), composite_ref(c, variance, torch.float32)
+
+
+def composite_errors(got: dict, ref: dict) -> dict:
+    """helpers.rel_err per forward tensor, helpers.grad_rel_err's form (scale floor 1e-5) for the two gradient tensors,
+    d_variance relative to the true value (None where that is exactly zero; whether it is asserted: dvar_live)."""
+    from helpers import grad_rel_err
+
+    e = {k: rel_err(got[k].reshape(ref[k].shape), ref[k]) for k in COMPOSITE_FWD if k in got}
+    for k in ("d_radiance", "d_srdf"):
+        if k in got:
+            e[k] = grad_rel_err(got[k].reshape(ref[k].shape), ref[k])
+    if "d_variance" in got:
+        e["d_variance"] = abs(float(got["d_variance"]) - ref["d_variance"]) / abs(ref["d_variance"]) if ref["d_variance"] != 0.0 else None
+    return e
+
+
+def dvar_live(ref64: dict, ref32: dict) -> bool:
+    """Whether d_variance of this case is compared RELATIVE to its float64 value: it is above float32's worst-case
+    resolution (DVAR_NEGLIGIBLE x dvar_scale), or -- that scale being an upper bound that random signs undercut by
+    orders of magnitude -- the float32 oracle demonstrably resolves it (within DVAR_RESOLVED).  Otherwise the value is
+    cancellation or underflow, and only |d_variance| < DVAR_NEGLIGIBLE x dvar_scale is asked."""
+    d = ref64["d_variance"]
+    if d == 0.0:
+        return False
+    return abs(d) >= DVAR_NEGLIGIBLE * ref64["dvar_scale"] or abs(ref32["d_variance"] - d) <= DVAR_RESOLVED * abs(d)
+
+
+def raw_alpha(c: dict, variance: float, dtype=torch.float32) -> torch.Tensor:
+    """renderer.py:37 before its clip, as the compositor forms it"""
+    z, srdf = c["z"].to(dtype), c["srdf"].to(dtype)
+    d = z[:, 1:] - z[:, :-1]
+    d = torch.cat([d[:, :1], d, d[:, -1:]], 1)
+    interval = (d[:, :-1] + d[:, 1:]) / 2
+    inv_s = torch.exp(torch.tensor(variance, dtype=dtype) * 10.0).clip(1e-6, 1e6)
+    pc, nc = torch.sigmoid((srdf + 0.75 * interval) * inv_s), torch.sigmoid((srdf - 0.75 * interval) * inv_s)
+    return (pc - nc + 1e-5) / (pc + 1e-5)
+
+
+# ------------------------------------------------------------------ importance sampler
+SAMPLER_SHAPES = [(2, 1), (3, 7), (16, 16), (17, 5), (48, 16), (63, 65), (64, 32), (96, 96), (129, 200), (200, 56),
+                  (255, 256), (256, 256)]       # (SN, PN)
+SAMPLER_RN = 9          # two workgroups of four rays and one ray
+SAMPLER_BOUND = 5e-6    # the bound of test_importance_sampler_and_merge
+PATTERNS = ("bump", "zeros", "onehot_first", "onehot_last", "onehot_mid", "zero_run", "z_ties")
+
+
+def onehot_mid_index(SN: int) -> int:
+    return SN // 2
+
+
+@functools.lru_cache(maxsize=None)
+def sampler_inputs(SN: int, PN: int, pattern: str = "bump", RN: int = SAMPLER_RN):
+    """(weight (RN,SN), z (RN,SN) sorted, U2 (PN,RN)).  'bump': 0.8 x a normalised Gaussian bump + a uniform floor of
+    0.2 / SN, which keeps every CDF step away from zero (without it the reference is ill-conditioned: a flat CDF stretch
+    divides by the 1e-6 guard alone).  The other patterns are the edges: all-zero and one-hot weights, a run of zeros
+    in the middle (a flat CDF), equal neighbours among the coarse positions."""
+    g = torch.Generator().manual_seed(9000 + 300 * SN + PN)
+    z = torch.sort(torch.rand(RN, SN, generator=g) * 2 + 2, dim=1)[0]
+    centre = 2.3 + 1.4 * torch.rand(RN, 1, generator=g)
+    U2 = torch.rand(PN, RN, generator=g)
+    b = torch.exp(-0.5 * ((z - centre) / 0.15) ** 2)
+    w = 0.8 * b / b.sum(1, keepdim=True) + 0.2 / SN
+    if pattern == "zeros":
+        w = torch.zeros_like(w)
+    elif pattern.startswith("onehot"):
+        i = dict(onehot_first=0, onehot_last=SN - 1, onehot_mid=onehot_mid_index(SN))[pattern]
+        w = torch.zeros_like(w)
+        w[:, i] = 1.0
+    elif pattern == "zero_run":
+        w[:, SN // 3:max(SN // 3 + 1, 2 * SN // 3)] = 0.0
+    elif pattern == "z_ties":
+        j = max(1, SN // 2)
+        z[:, j] = z[:, j - 1]
+        if SN >= 8:         # ... and a run of three further up
+            z[:, SN - 2] = z[:, SN - 3]
+            z[:, SN - 1] = z[:, SN - 3]
+    else:
+        assert pattern == "bump", pattern
+    return w.contiguous(), z.contiguous(), U2.contiguous()
+
+
+def sampler_ref(w, z, U2, dtype=torch.float64) -> torch.Tensor:
+    """O.importance_sample's sorted fine positions (RN,PN) in ``dtype``"""
+    RN = z.shape[0]
+    with torch.no_grad():
+        return O.importance_sample(torch.zeros(RN, 3, dtype=dtype), torch.ones(RN, 3, dtype=dtype), w.to(dtype), z.to(dtype), U2)[1]
+
+
+def unsorting_permutation(SN: int, keep=()) -> torch.Tensor:
+    """A fixed permutation of the SN coarse slots that leaves the slots ``keep`` where they are"""
+    g = torch.Generator().manual_seed(31 + SN)
+    free = torch.tensor([i for i in range(SN) if i not in keep], dtype=torch.long)
+    perm = torch.arange(SN)
+    if free.numel() >= 2:
+        shuffled = free[torch.randperm(free.numel(), generator=g)]
+        if torch.equal(shuffled, free):
+            shuffled = free.flip(0)
+        perm[free] = shuffled
+    return perm
