@@ -9,7 +9,9 @@
 // products (K = 16 tokens / 16 head dims) stay on the fp32 MFMA:
 //  sweep 1: K^T, V^T tiles ([token][head slot], obtained by swapping the MFMA operands), then
 //           KV_h += K'_h^T V_h as 4 MFMAs per head (k = the tile's 16 tokens); a ones column in a padding
-//           slot of V makes that column of KV_h the K' sum needed for the normaliser.
+//           slot of V makes that column of KV_h the K' sum needed for the normaliser.  The forward-only build
+//           takes TWO column tiles per weight pass, one group of kRt1GroupHeads heads at a time (B_RT1 in its
+//           virtual order); the tape build one tile per pass in the blob's order.
 //  sweep 2: Q, message_h = KV_h^T-chained MFMA with Q'_h (k = head dims: THREE MFMAs per head, the padding
 //           row 3 of the result is Q'.sum K'), merge, LayerNorm, MLP, LayerNorm, residual, DensityMLP.
 // K and V give each head its own 16-column tile with the 11 dims in the slots 4g + r, r < 3 (ufr_layout.h:
@@ -73,9 +75,13 @@ __device__ __forceinline__ void layer_norm88(f32x4 (&tt)[C][6], const WS& ws, in
 }
 
 // 256-thread workgroups = 4 rays (one wave each, one per SIMD), two workgroups per CU; the four waves
-// walk the weight streams B_RT1 / B_RT2 together through LDS (weight_stream_f16.h).  Both sweeps walk ONE 16-token
-// column tile per iteration: sweep 1's two sets of eight head tiles fill the registers, and the kernel is not bound by
-// its weight stream (sweep 2 over two tiles per weight pass was slower: DESIGN.md section 7).
+// walk the weight streams B_RT1 / B_RT2 together through LDS (weight_stream_f16.h).  Sweep 2 walks ONE 16-token column
+// tile per weight pass (two were slower: its cat / hid tiles spill).  Sweep 1 of the forward-only
+// build walks TWO: in the blob's k-step-major order the sixteen head tiles of both column tiles stay live across the three
+// k-steps (256 registers, 30 spilled); consumed head group by head group -- the fetch order of the LDS DMA need not be the
+// blob's -- only 2 x 2 x kRt1GroupHeads accumulator tiles are live and the kernel stays within 208 registers, which keeps a
+// gather wave resident beside two of these waves on a SIMD (tests/test_ray_registers.py).  The tape build keeps one tile
+// per pass: the backward reads its state layout, and the tests compare the two builds bit for bit.
 constexpr int kRtBlock = 256;
 constexpr int kRtMinW = 2;   // waves per SIMD the register budget is sized for
 constexpr int kRtWaves = kRtBlock / 64;
@@ -104,14 +110,14 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : kRtMinW) ray_transformer_
                                                                   int* __restrict__ status, float* __restrict__ tape = nullptr,
                                                                   float* __restrict__ ray_state = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  auto ws = wstream_f16_begin<kRtWaves, LOWP>(packed, smem);
+  auto ws = wstream_f16_begin<kRtWaves, LOWP, false, !TAPE>(packed, smem);   // forward-only: B_RT1 in its head-grouped order
   wstream_f16_prime<B_RT1, kRtWaves>(ws);
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
   const int ray_raw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const bool valid = ray_raw < RN;           // no early exit: every wave meets every chunk barrier
   const int ray = valid ? ray_raw : RN - 1;
   const int n_tiles = SN / 16;
-  const int n_iter = n_tiles;                 // sweep 1: one tile per iteration
+  const int n_iter = n_tiles;                 // sweep 2 (and the tape build's sweep 1): one tile per iteration
   // values / v_length (linear_attention.py:41): a multiply by 1/SN is exact only for power-of-two sample counts;
   // any other total (64 + 32, 48, ...) takes the true division the reference performs
   // the layers' plane / accumulator scales (ufr_layout.h: RayScalar; weight_stream_f16.h: ScalarFile -- this kernel has the
@@ -133,88 +139,174 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : kRtMinW) ray_transformer_
   for (int h = 0; h < 8; ++h) KV[h] = splat4(0.f);
 #pragma unroll
   for (int h = 0; h < (TAPE ? 8 : 1); ++h) KVT[h] = splat4(0.f);
-  for (int it = 0; it < n_iter; ++it) {
-    constexpr int C = 1;
-    const bool wrap = it + 1 < n_iter;
-    const bool slot_ok = head11_slot(j) >= 0;   // column j of a head tile carries a head dim
-    f32x4 x[C][6], kt[C][8], vt[C][8];
-    bool live[C];
+  if constexpr (TAPE) {
+    // the tape build: one tile per weight pass, B_RT1 in blob order (the backward reads this state layout; the tests
+    // compare the forward-only build against it bit for bit)
+    for (int it = 0; it < n_iter; ++it) {
+      constexpr int C = 1;
+      const bool wrap = it + 1 < n_iter;
+      const bool slot_ok = head11_slot(j) >= 0;   // column j of a head tile carries a head dim
+      f32x4 x[C][6], kt[C][8], vt[C][8];
+      bool live[C];
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const int tile = it * C + c;
-      live[c] = tile < n_tiles;
-      const int tl = live[c] ? tile : n_tiles - 1;
-      load_ray_tile(token0, tok_row, order_pe, (size_t)ray * SN + tl * 16, tl * 16, g, j, x[c]);
+      for (int c = 0; c < C; ++c) {
+        const int tile = it * C + c;
+        live[c] = tile < n_tiles;
+        const int tl = live[c] ? tile : n_tiles - 1;
+        load_ray_tile(token0, tok_row, order_pe, (size_t)ray * SN + tl * 16, tl * 16, g, j, x[c]);
 #pragma unroll
-      for (int h = 0; h < 8; ++h) { kt[c][h] = splat4(0.f); vt[c][h] = splat4(0.f); }
-    }
-    {  // swapped operands: kt[h], vt[h] rows = tokens 4g+r, column j = head dim; x is split once per k-step
-      BWords<C> cur;
-      split_units<0, 0, 4 * C>(x, cur, xs_x);
-      static_for<3>([&](auto si) __attribute__((always_inline)) {
-        constexpr int s = decltype(si)::value;
-        BStep b[C];
-        bwords_to_bstep(cur, b);
-        if constexpr (s < 2) {
-          BWords<C> nxt;
-          gemm_f16_panel<M_RT_K, s, C, kRtWaves, true>(ws, b, kt, wrap, [&](auto ti) __attribute__((always_inline)) {
-            constexpr int to = decltype(ti)::value;
-            split_units<s + 1, to * 4 * C / 8, (to + 1) * 4 * C / 8>(x, nxt, xs_x);
-          });
-          gemm_f16_panel<M_RT_V, s, C, kRtWaves, true>(ws, b, vt, wrap);
-          cur = nxt;
-        } else {
-          gemm_f16_panel<M_RT_K, s, C, kRtWaves, true>(ws, b, kt, wrap);
-          gemm_f16_panel<M_RT_V, s, C, kRtWaves, true>(ws, b, vt, wrap);
-        }
-      });
-      probe_gemm(kt, ws);   // raw accumulators: the scale joins elu1 / the division by the sample count
-      probe_gemm(vt, ws);
-    }
-    UFR_RT_PHASE(0)  // sweep 1: token load + K, V GEMMs
-    // KV_h += K'_h^T V_h: the operands of all 32 products first (branch-free: the division by a non-power-of-two sample
-    // count is chosen once per tile, padding slots by selects), then the MFMAs register-major over the heads, so that
-    // consecutive matrix instructions add into different accumulators (a head's own four still run r = 0..3: same bits).
-    // Written per (head, register) this phase compiled into 32 x {exec-masked elu, a uniform branch around an IEEE
-    // division, one MFMA}: 128 branches per tile and nothing for the scheduler to overlap.
-    // ones column -> sum of K'.  The forward-only build puts it into EVERY lane group's padding slot (3, 7, 11, 15): the
-    // normaliser Q'.sum K' then comes out of the message MFMAs in register 3 of every lane group -- no cross-lane exchange
-    // (8 ds_bpermute round trips per tile); the tape build keeps slot 3 alone (the backward reads the state's layout)
-    const float pad_v = (TAPE ? j == 3 : (j & 3) == 3) ? 1.f : 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      float kk[8][4], vv[8][4];
-      if (pow2_len) {
-#pragma unroll
-        for (int h = 0; h < 8; ++h)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) vv[h][r] = vt[c][h][r] * inv_len;
-      } else {
-#pragma unroll
-        for (int h = 0; h < 8; ++h)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) vv[h][r] = vt[c][h][r] / f_len;
+        for (int h = 0; h < 8; ++h) { kt[c][h] = splat4(0.f); vt[c][h] = splat4(0.f); }
       }
-      const bool k_ok = slot_ok && live[c];                                               // padding slots / empty tile contribute nothing
+      {  // swapped operands: kt[h], vt[h] rows = tokens 4g+r, column j = head dim; x is split once per k-step
+        BWords<C> cur;
+        split_units<0, 0, 4 * C>(x, cur, xs_x);
+        static_for<3>([&](auto si) __attribute__((always_inline)) {
+          constexpr int s = decltype(si)::value;
+          BStep b[C];
+          bwords_to_bstep(cur, b);
+          if constexpr (s < 2) {
+            BWords<C> nxt;
+            gemm_f16_panel<M_RT_K, s, C, kRtWaves, true>(ws, b, kt, wrap, [&](auto ti) __attribute__((always_inline)) {
+              constexpr int to = decltype(ti)::value;
+              split_units<s + 1, to * 4 * C / 8, (to + 1) * 4 * C / 8>(x, nxt, xs_x);
+            });
+            gemm_f16_panel<M_RT_V, s, C, kRtWaves, true>(ws, b, vt, wrap);
+            cur = nxt;
+          } else {
+            gemm_f16_panel<M_RT_K, s, C, kRtWaves, true>(ws, b, kt, wrap);
+            gemm_f16_panel<M_RT_V, s, C, kRtWaves, true>(ws, b, vt, wrap);
+          }
+        });
+        probe_gemm(kt, ws);   // raw accumulators: the scale joins elu1 / the division by the sample count
+        probe_gemm(vt, ws);
+      }
+      UFR_RT_PHASE(0)  // sweep 1: token load + K, V GEMMs
+      // KV_h += K'_h^T V_h: the operands of all 32 products first (branch-free: the division by a non-power-of-two sample
+      // count is chosen once per tile, padding slots by selects), then the MFMAs register-major over the heads, so that
+      // consecutive matrix instructions add into different accumulators (a head's own four still run r = 0..3: same bits).
+      // Written per (head, register) this phase compiled into 32 x {exec-masked elu, a uniform branch around an IEEE
+      // division, one MFMA}: 128 branches per tile and nothing for the scheduler to overlap.
+      // ones column -> sum of K'.  The forward-only build puts it into EVERY lane group's padding slot (3, 7, 11, 15): the
+      // normaliser Q'.sum K' then comes out of the message MFMAs in register 3 of every lane group -- no cross-lane exchange
+      // (8 ds_bpermute round trips per tile); the tape build keeps slot 3 alone (the backward reads the state's layout)
+      const float pad_v = (TAPE ? j == 3 : (j & 3) == 3) ? 1.f : 0.f;
 #pragma unroll
-      for (int h = 0; h < 8; ++h)
+      for (int c = 0; c < C; ++c) {
+        float kk[8][4], vv[8][4];
+        if (pow2_len) {
+#pragma unroll
+          for (int h = 0; h < 8; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vv[h][r] = vt[c][h][r] * inv_len;
+        } else {
+#pragma unroll
+          for (int h = 0; h < 8; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vv[h][r] = vt[c][h][r] / f_len;
+        }
+        const bool k_ok = slot_ok && live[c];                                               // padding slots / empty tile contribute nothing
+#pragma unroll
+        for (int h = 0; h < 8; ++h)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float e = elu1_acc(kt[c][h][r], k_dsc, k_l2e);
+            kk[h][r] = k_ok ? e : 0.f;
+            vv[h][r] = slot_ok ? vv[h][r] : pad_v;
+          }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float e = elu1_acc(kt[c][h][r], k_dsc, k_l2e);
-          kk[h][r] = k_ok ? e : 0.f;
-          vv[h][r] = slot_ok ? vv[h][r] : pad_v;
-        }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int h = 0; h < 8; ++h) {
-          KV[h] = mfma16(kk[h][r], vv[h][r], KV[h]);
-          if constexpr (TAPE) KVT[h] = mfma16(vv[h][r], kk[h][r], KVT[h]);   // [V slot][K slot]: the A operand of d Q' = KV d acc
+          for (int h = 0; h < 8; ++h) {
+            KV[h] = mfma16(kk[h][r], vv[h][r], KV[h]);
+            if constexpr (TAPE) KVT[h] = mfma16(vv[h][r], kk[h][r], KVT[h]);   // [V slot][K slot]: the A operand of d Q' = KV d acc
+          }
         }
       }
+      wstream_f16_finish<B_RT1, kRtWaves>(ws, wrap);
+      UFR_RT_PHASE(1)  // sweep 1: KV accumulation (fp32 MFMA)
     }
-    wstream_f16_finish<B_RT1, kRtWaves>(ws, wrap);
-    UFR_RT_PHASE(1)  // sweep 1: KV accumulation (fp32 MFMA)
+  } else {
+    // Forward-only: TWO column tiles per weight pass, so a weight fragment read from LDS feeds six MFMAs instead of three
+    // and the workgroup streams B_RT1 once per pair of tiles.  The pass walks the stream head group by head group
+    // (ufr_layout_f16.h: f16_rt1_virtual_to_blob): only one group's K and V accumulators of both tiles are live at a time
+    // (2 C kRt1GroupHeads accumulator tiles), where the blob's k-step-major order held all sixteen head tiles of both column tiles
+    // across the three k-steps and spilled.  Every accumulator still sees the tape build's operation sequence: k-steps 0, 1,
+    // 2 with the products lo.hi, hi.lo, hi.hi, then KV_h += tile by tile, r = 0..3 -- the same bits.
+    // x is split once per pass for all three k-steps (3 BWords<C>; x is dead after that) and reused by K, V and every group.
+    const bool slot_ok = head11_slot(j) >= 0;   // column j of a head tile carries a head dim
+    // ones column -> sum of K', in EVERY lane group's padding slot (3, 7, 11, 15): the normaliser Q'.sum K' then comes out
+    // of the message MFMAs in register 3 of every lane group -- no cross-lane exchange (8 ds_bpermute round trips per tile)
+    const float pad_v = (j & 3) == 3 ? 1.f : 0.f;
+    auto pass = [&](auto cc, int tile0, bool wrap) __attribute__((always_inline)) {
+      constexpr int C = decltype(cc)::value, G = kRt1GroupHeads;
+      BWords<C> bw[3];
+      {
+        f32x4 x[C][6];
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+          load_ray_tile(token0, tok_row, order_pe, (size_t)ray * SN + (tile0 + c) * 16, (tile0 + c) * 16, g, j, x[c]);
+        static_for<3>([&](auto si) __attribute__((always_inline)) {
+          constexpr int s = decltype(si)::value;
+          split_units<s, 0, 4 * C>(x, bw[s], xs_x);
+        });
+      }
+      static_for<kRt1Heads / G>([&](auto gi) __attribute__((always_inline)) {
+        constexpr int H0 = decltype(gi)::value * G;
+        f32x4 kt[C][G], vt[C][G];   // swapped operands: rows = tokens 4g+r, column j = head dim
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+#pragma unroll
+          for (int h = 0; h < G; ++h) { kt[c][h] = splat4(0.f); vt[c][h] = splat4(0.f); }
+        static_for<3>([&](auto si) __attribute__((always_inline)) {
+          constexpr int s = decltype(si)::value;
+          BStep b[C];
+          bwords_to_bstep(bw[s], b);
+          gemm_f16_panel<M_RT_K, s, C, kRtWaves, true, -1, H0, G>(ws, b, kt, wrap);
+          gemm_f16_panel<M_RT_V, s, C, kRtWaves, true, -1, H0, G>(ws, b, vt, wrap);
+        });
+        if constexpr (H0 == 0) {   // head 0's accumulators, as in the tape build
+          probe_gemm(kt, ws);      // raw accumulators: the scale joins elu1 / the division by the sample count
+          probe_gemm(vt, ws);
+        }
+        UFR_RT_PHASE(0)  // sweep 1: token load + K, V GEMMs
+        // KV_h += K'_h^T V_h: the operands first (branch-free: the division by a non-power-of-two sample count is chosen
+        // once per tile, padding slots by selects), then the MFMAs register-major over the group's heads, so that
+        // consecutive matrix instructions add into different accumulators (a head's own run tile by tile, r = 0..3)
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          float kk[G][4], vv[G][4];
+          if (pow2_len) {
+#pragma unroll
+            for (int h = 0; h < G; ++h)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) vv[h][r] = vt[c][h][r] * inv_len;
+          } else {
+#pragma unroll
+            for (int h = 0; h < G; ++h)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) vv[h][r] = vt[c][h][r] / f_len;
+          }
+#pragma unroll
+          for (int h = 0; h < G; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const float e = elu1_acc(kt[c][h][r], k_dsc, k_l2e);
+              kk[h][r] = slot_ok ? e : 0.f;                                                  // padding slots contribute nothing
+              vv[h][r] = slot_ok ? vv[h][r] : pad_v;
+            }
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int h = 0; h < G; ++h) KV[H0 + h] = mfma16(kk[h][r], vv[h][r], KV[H0 + h]);
+        }
+        UFR_RT_PHASE(1)  // sweep 1: KV accumulation (fp32 MFMA)
+      });
+      wstream_f16_finish<B_RT1, kRtWaves>(ws, wrap);
+    };
+    // an odd tile count ends with a pass over ONE tile: the dead partner's MFMAs are not run (a multiply by zero could turn
+    // -0 into +0 or make NaN of a non-finite row); the single pass meets the same chunk barriers
+    for (int it = 0; it < n_tiles / 2; ++it) pass(std::integral_constant<int, 2>{}, 2 * it, 2 * it + 2 < n_tiles);
+    if (n_tiles & 1) pass(std::integral_constant<int, 1>{}, n_tiles - 1, false);
   }
 
   if constexpr (TAPE) {

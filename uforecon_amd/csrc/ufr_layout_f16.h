@@ -30,7 +30,8 @@
 // A PANEL is one k-step (32 input features) of one matrix: all its out tiles x 3 planes, stored in
 // consumption order; a STREAM is the sequence of panels a kernel phase walks:
 //   B_VT   view transformer  q0 k0 q1 k1 q2 k2 | v | merge | mlp0 | mlp2 | rw0 rw2 rw4
-//   B_RT1  ray transformer sweep 1  k0 v0 k1 v1 k2 v2          (swapped operands)
+//   B_RT1  ray transformer sweep 1  k0 v0 k1 v1 k2 v2          (swapped operands; the forward-only kernel FETCHES it head
+//          group by head group -- f16_rt1_virtual_to_blob below -- the blob keeps this order)
 //   B_RT2  ray transformer sweep 2  q | merge | mlp0 | mlp2 | dm0 dm2 dm4
 #pragma once
 #include "ufr_layout.h"
@@ -174,6 +175,59 @@ __host__ __device__ constexpr int f16_stream_base_frags(int S) {   // first frag
   for (int j = 0; j < S; ++j) o += f16_stream_chunks(j) * kF16ChunkFrags;
   return o;
 }
+// A stream's tail padding (the rest of its last real chunk and the chunks that round it up to the ring depth) is
+// never read, so the forward kernels do not fetch it (weight_stream_f16.h: wstream_f16_fetch skips a piece that lies
+// wholly beyond the stream's fragments).  The backward streams keep fetching whole chunks.
+__host__ __device__ constexpr bool f16_stream_skips_padding(int S) { return S < B_COUNT; }
+
+// VIRTUAL consumption order of B_RT1 (forward-only ray transformer): the kernel walks sweep 1 head group by head
+// group -- for each group of kRt1GroupHeads out tiles:  k s0 | v s0 | k s1 | v s1 | k s2 | v s2, restricted to the group's
+// out tiles -- while the blob keeps the k-step-major panel order above.  The LDS ring is filled and read in virtual
+// order; only the global offset of a DMA piece goes through this map.  A group's fragments of one panel (heads x planes)
+// are contiguous in the blob, so every aligned run of 4 virtual fragments (one piece of each of the 4 fetching waves)
+// is 4 consecutive blob fragments.
+// Groups of 2 heads: 194 VGPRs in the fp32-mode kernel (32 live K / V accumulator registers for two column tiles).  Groups
+// of 4 (64) compile to 218 without spills, which evicts the gather wave that shares the SIMD: measured slower in the frame
+// than groups of 2 and no faster than one tile per pass.
+constexpr int kRt1GroupHeads = 2;
+constexpr int kRt1Heads = 8;
+constexpr int kRt1GroupFrags = 6 * kRt1GroupHeads * kPlanes;   // a group's six panel slices
+__host__ __device__ constexpr int f16_rt1_virtual_to_blob(int v) {
+  const int run = kRt1GroupHeads * kPlanes;
+  const int gr = v / kRt1GroupFrags, r = v % kRt1GroupFrags, panel = r / run, q = r % run;
+  return panel * (kRt1Heads * kPlanes) + gr * run + q;
+}
+// first virtual fragment of (panel pi, out tile to) -- the inverse of the map above
+__host__ __device__ constexpr int f16_rt1_virtual_start(int pi, int to) {
+  return (to / kRt1GroupHeads) * kRt1GroupFrags + pi * (kRt1GroupHeads * kPlanes) + (to % kRt1GroupHeads) * kPlanes;
+}
+__host__ __device__ constexpr bool f16_rt1_map_ok() {
+  if (kRt1Heads % kRt1GroupHeads != 0 || (kRt1GroupHeads * kPlanes) % 4 != 0) return false;
+  if (mat_desc(M_RT_K).n_out != kRt1Heads || mat_desc(M_RT_V).n_out != kRt1Heads) return false;
+  if (f16_stream_frags(B_RT1) != 6 * kRt1Heads * kPlanes) return false;
+  bool seen[6 * kRt1Heads * kPlanes] = {};
+  for (int v = 0; v < f16_stream_frags(B_RT1); ++v) {
+    const int b = f16_rt1_virtual_to_blob(v);
+    if (b < 0 || b >= f16_stream_frags(B_RT1) || seen[b]) return false;            // a permutation of the stream
+    seen[b] = true;
+    if (v % 4 != 0 && b != f16_rt1_virtual_to_blob(v - 1) + 1) return false;       // piece groups stay contiguous
+  }
+  for (int pi = 0; pi < 6; ++pi)
+    for (int to = 0; to < kRt1Heads; ++to)
+      for (int p = 0; p < kPlanes; ++p)
+        if (f16_rt1_virtual_to_blob(f16_rt1_virtual_start(pi, to) + p) != f16_panel_start(B_RT1, pi) + to * kPlanes + p) return false;
+  return true;
+}
+static_assert(f16_rt1_map_ok(), "B_RT1's virtual order must permute the stream and keep every 4-fragment piece group contiguous");
+// blob fragment of consumption-order fragment v of stream S; VORDER: the kernel walks B_RT1 in the virtual order
+__host__ __device__ constexpr int f16_fetch_frag(int S, int v, bool vorder) {
+  return (vorder && S == B_RT1) ? f16_rt1_virtual_to_blob(v) : v;
+}
+// first consumption-order fragment of out tile `to` of panel pi of stream S
+__host__ __device__ constexpr int f16_stage_frag(int S, int pi, int to, bool vorder) {
+  return (vorder && S == B_RT1) ? f16_rt1_virtual_start(pi, to) : f16_panel_start(S, pi) + to * kPlanes;
+}
+
 constexpr int kF16FragsPadded = f16_stream_base_frags(B_COUNT);
 constexpr int kF16Halfwords = kF16FragsPadded * 512;                  // fp16 elements in the region
 constexpr int kF16Bytes = kF16FragsPadded * 1024;

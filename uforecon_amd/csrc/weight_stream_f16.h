@@ -53,10 +53,12 @@ __device__ __forceinline__ void split_pair_bf16(float a, float b, unsigned& h, u
 
 // LOWP: the reduced-precision mode (ufr_set_matrix_precision): one 16-bit plane per operand, one MFMA per product
 // BF16: the stream holds bf16 planes (ufr_layout_f16.h: B_VTB ...), the activations are split with split_pair_bf16
-template <bool LOWP, bool BF16 = false>
+// VORDER: B_RT1 is fetched and walked in its virtual, head-grouped order (ufr_layout_f16.h: f16_rt1_virtual_to_blob)
+template <bool LOWP, bool BF16 = false, bool VORDER = false>
 struct WStreamF16T {
   static constexpr bool lowp = LOWP;
   static constexpr bool bf16 = BF16;
+  static constexpr bool vorder = VORDER;
   const char* src;     // fp16 plane region of the packed blob (global, wave-uniform)
   char* ring;          // LDS: the ring of kF16Slots chunk slots
   unsigned ring_lds;   // ... as an LDS byte address (scalar)
@@ -69,9 +71,9 @@ struct WStreamF16T {
 };
 
 typedef WStreamF16T<false> WStreamF16;
-template <int NWAVES, bool LOWP = false, bool BF16 = false>
-__device__ __forceinline__ WStreamF16T<LOWP, BF16> wstream_f16_begin(const float* __restrict__ packed, char* smem) {
-  WStreamF16T<LOWP, BF16> ws;
+template <int NWAVES, bool LOWP = false, bool BF16 = false, bool VORDER = false>
+__device__ __forceinline__ WStreamF16T<LOWP, BF16, VORDER> wstream_f16_begin(const float* __restrict__ packed, char* smem) {
+  WStreamF16T<LOWP, BF16, VORDER> ws;
   ws.lane = threadIdx.x & 63;
   ws.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   ws.bad_in = ws.bad_out = 0ull;
@@ -120,19 +122,40 @@ __device__ __forceinline__ void lds_dma_piece(const i32x4& rsrc, unsigned lds_wa
                : "memory", "scc");
 }
 
+// piece k of chunk CHK (fragments CHK * kF16ChunkFrags + k * NWAVES + wave) is issued unless the stream skips its padding
+// and the piece lies wholly beyond the stream's fragments; the real fragment count of such a stream is a multiple of
+// NWAVES, so a piece is all weights or all padding and the skip is the same compile-time decision in every wave
+template <int S, int NWAVES>
+__host__ __device__ constexpr bool f16_piece_issued(int chk, int k) {
+  return !f16_stream_skips_padding(S) || chk * kF16ChunkFrags + k * NWAVES < f16_stream_frags(S);
+}
+template <int S, int NWAVES>
+__host__ __device__ constexpr int f16_chunk_pieces(int chk) {   // pieces each wave issues for chunk chk
+  int n = 0;
+  for (int k = 0; k < kF16ChunkFrags / NWAVES; ++k) n += f16_piece_issued<S, NWAVES>(chk, k) ? 1 : 0;
+  return n;
+}
+
 // fetch pieces [P0, P1) of this wave's share of chunk CHK of stream S into the chunk's ring slot (a piece = one
-// 1 KiB LDS-DMA wave instruction; the wave's share is every NWAVES-th fragment)
+// 1 KiB LDS-DMA wave instruction; the wave's share is every NWAVES-th fragment).  The ring holds the chunk in
+// CONSUMPTION order; the global offset of a piece comes from f16_fetch_frag (the blob order, except for B_RT1 under VORDER)
 template <int S, int NWAVES, int CHK, int P0 = 0, int P1 = kF16ChunkFrags / NWAVES, class WS>
 __device__ __forceinline__ void wstream_f16_fetch(const WS& ws) {
   static_assert(kF16ChunkFrags % NWAVES == 0, "chunk must split evenly over the fetching waves");
+  static_assert(!f16_stream_skips_padding(S) || f16_stream_frags(S) % NWAVES == 0, "a piece must be all weights or all padding");
   if constexpr (P1 > P0) {
-    constexpr size_t goff = ((size_t)f16_stream_base_frags(S) + (size_t)CHK * kF16ChunkFrags) * 1024;
+    constexpr size_t gbase = (size_t)f16_stream_base_frags(S) * 1024;
     constexpr int soff = (CHK % kF16Slots) * (kF16ChunkFrags * 1024);
     const unsigned lane_off = ws.lane * 16;
-    static_assert(goff + (size_t)kF16ChunkFrags * 1024 < (1ull << 31), "buffer offsets are 32-bit");
+    static_assert(gbase + (size_t)f16_stream_chunks(S) * kF16ChunkFrags * 1024 < (1ull << 31), "buffer offsets are 32-bit");
     static_for<P1 - P0>([&](auto ki) __attribute__((always_inline)) {
       constexpr unsigned k = P0 + decltype(ki)::value;
-      lds_dma_piece<(unsigned)goff + k * NWAVES * 1024u, (unsigned)soff + k * NWAVES * 1024u>(ws.rsrc, ws.lds_wave, lane_off);
+      if constexpr (f16_piece_issued<S, NWAVES>(CHK, k)) {
+        constexpr int v0 = CHK * kF16ChunkFrags + k * NWAVES;   // wave w takes fragment v0 + w (rsrc is shifted by w KiB)
+        constexpr int b0 = f16_fetch_frag(S, v0, WS::vorder);
+        static_assert(f16_fetch_frag(S, v0 + NWAVES - 1, WS::vorder) == b0 + NWAVES - 1, "a piece group must be contiguous in the blob");
+        lds_dma_piece<(unsigned)(gbase + (size_t)b0 * 1024), (unsigned)soff + k * NWAVES * 1024u>(ws.rsrc, ws.lds_wave, lane_off);
+      }
     });
   }
 }
@@ -142,17 +165,28 @@ __device__ __forceinline__ void wstream_f16_fetch(const WS& ws) {
 // be outstanding when chunk CHK must have landed.
 template <int S, int NWAVES, int CHK, class WS>
 __device__ __forceinline__ void wstream_f16_barrier(const WS& ws, bool wrap) {
-  constexpr int per_chunk = kF16ChunkFrags / NWAVES, ahead = kF16Slots - 1, n_chunks = f16_stream_chunks(S);
-  constexpr int younger = (kF16Slots - 2) * per_chunk;
+  constexpr int n_chunks = f16_stream_chunks(S);
+  // pieces of the younger chunks this wave ACTUALLY issued (padding pieces are not: f16_piece_issued).  Too large a
+  // count here is a silent race -- a fragment read before it has landed; too small only waits longer.
+  constexpr int younger_pass = [] {      // ... of this pass: issued unconditionally
+    int n = 0;
+    for (int i = 1; i <= kF16Slots - 2; ++i)
+      if (CHK + i < n_chunks) n += f16_chunk_pieces<S, NWAVES>(CHK + i);
+    return n;
+  }();
+  constexpr int younger_wrap = [] {      // ... wrap-around fetches of the next pass: issued only if wrap
+    int n = 0;
+    for (int i = 1; i <= kF16Slots - 2; ++i)
+      if (CHK + i >= n_chunks) n += f16_chunk_pieces<S, NWAVES>((CHK + i) % n_chunks);
+    return n;
+  }();
   // lgkmcnt(0): this wave's reads of the chunk whose slot is refilled next have returned (the stages are read
   // kF16Depth ahead, across the chunk boundary: the previous chunk's last stages now live in registers)
-  if constexpr (younger == 0) {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  } else if constexpr (CHK + ahead <= n_chunks) {          // every younger fetch was issued unconditionally
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(younger) : "memory");
-  } else {                                                 // the younger fetches were wrap-around ones
-    if (wrap) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(younger) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  if constexpr (younger_wrap == 0) {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(younger_pass) : "memory");
+  } else {
+    if (wrap) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(younger_pass + younger_wrap) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(younger_pass) : "memory");
   }
   __syncthreads();
 }
@@ -284,23 +318,27 @@ struct NoHook {
 };
 // STREAM: the stream the panel is read from (default: the matrix's own; the ray transformer's k / v panels also sit in the
 // backward stream B_RTB2).  The planes' type -- fp16 with scales, or bf16 -- is the matrix's (f16_mat_is_bf16).
-template <int M, int S, int C, int NWAVES, bool SWAP = false, int STREAM = -1, class Hook = NoHook, class WS = WStreamF16>
-__device__ __forceinline__ void gemm_f16_panel(WS& ws, const BStep (&b)[C], f32x4 (&out)[C][mat_desc(M).n_out],
+// [T0, T0 + NT): the out tiles walked, out[c][0..NT) their accumulators (default: the whole panel).  A slice is what a
+// kernel walks under a virtual consumption order (WS::vorder, B_RT1: one head group's tiles); stage and chunk indices
+// below are consumption-order indices either way (f16_stage_frag), which is also the order the ring is filled in.
+template <int M, int S, int C, int NWAVES, bool SWAP = false, int STREAM = -1, int T0 = 0, int NT = mat_desc(M).n_out, class Hook = NoHook, class WS = WStreamF16>
+__device__ __forceinline__ void gemm_f16_panel(WS& ws, const BStep (&b)[C], f32x4 (&out)[C][NT],
                                               bool wrap, Hook&& hook = NoHook{}) {
   constexpr bool LOWP = WS::lowp;
   constexpr bool BF = f16_mat_is_bf16(M);
   constexpr int n_planes = LOWP ? 1 : kPlanes, n_products = LOWP ? 1 : kProducts;
-  constexpr int n_out = mat_desc(M).n_out, ST = STREAM >= 0 ? STREAM : f16_mat_stream(M);
+  constexpr int ST = STREAM >= 0 ? STREAM : f16_mat_stream(M);
   static_assert(f16_panel_index(M, S, ST) >= 0, "not a panel of the stream");
-  constexpr int F0 = f16_panel_start(ST, f16_panel_index(M, S, ST));
+  static_assert(T0 >= 0 && NT >= 1 && T0 + NT <= mat_desc(M).n_out, "out tile range");
+  constexpr int PI = f16_panel_index(M, S, ST);
   const f16x8* lds = reinterpret_cast<const f16x8*>(ws.ring) + ws.lane;
   // inside a GEMM panel the wave wins issue arbitration over a partner that is in a VALU-only phase (measured: view
   // transformer -1.7 %, ray transformer -1.4 % alone, 0.1 % on the whole frame with the gather beside them; priority 3
   // no better, the inverse scheme no effect)
   __builtin_amdgcn_s_setprio(kSetprio);
-  static_for<n_out>([&](auto ti) __attribute__((always_inline)) {
+  static_for<NT>([&](auto ti) __attribute__((always_inline)) {
     constexpr int to = decltype(ti)::value;
-    constexpr int f = F0 + to * kPlanes;                 // first of the stage's plane fragments
+    constexpr int f = f16_stage_frag(ST, PI, T0 + to, WS::vorder);   // first of the stage's plane fragments
     constexpr int sidx = f / kPlanes, n_stages = f16_stream_frags(ST) / kPlanes;
     __builtin_amdgcn_sched_barrier(0);
     // stage s of the pass is read from LDS while stage s - kF16Depth computes; a chunk is opened (hand-off barrier)
