@@ -45,16 +45,19 @@ def test_single_layer_gradients(mode, cin, cout):
         assert _rel(d_in2, cl(x.grad) + extra) < 2e-5
 
 
-# volumes large enough for the matrix-core weight-gradient kernels (conv3d.hip launch_wgrad_t: >= 100 000 voxel pairs for
-# the 16-channel tiles, >= 500 000 for the 8-channel layers); widths that are not whole segments / not multiples of four
+# the volumes of the full-resolution (8-channel) and half-resolution (16..64-channel) layers: 1e5 .. 5e5 voxel pairs per
+# weight, on the plane weight-gradient kernels (conv3d_wgrad_planes.hip) like every shape of the U-Nets; widths that are not
+# whole bricks
 @pytest.mark.parametrize("mode,cin,cout,dims", [
     (ops.CONV3D_S1, 16, 16, (16, 64, 104)), (ops.CONV3D_S1, 32, 32, (16, 64, 104)), (ops.CONV3D_S1, 64, 64, (16, 64, 104)),
     (ops.CONV3D_S2, 16, 32, (32, 128, 208)), (ops.CONV3D_S2, 32, 64, (32, 128, 208)),
     (ops.CONV3D_T2, 32, 16, (16, 64, 104)), (ops.CONV3D_T2, 64, 32, (16, 64, 104)),
     (ops.CONV3D_S1, 8, 8, (16, 128, 250)), (ops.CONV3D_S2, 8, 16, (32, 256, 500)), (ops.CONV3D_T2, 16, 8, (16, 128, 250))])
 def test_weight_gradients_at_matrix_core_sizes(mode, cin, cout, dims):
-    """ufr_conv3d_bwd_weight where it runs on the fp32 MFMA kernels, against torch's autograd of the same convolution (two
-    fp32 sums of 1e5 .. 5e5 terms in different orders: 1e-4 of the tensor's scale)."""
+    """ufr_conv3d_bwd_weight on full-resolution and half-resolution volumes, where it runs on the 16-bit matrix-core plane
+    kernels (conv3d_wgrad_planes.hip; bricks cut off at the volume's edge), against torch's autograd of the same convolution
+    (two fp32 sums of 1e5 .. 5e5 terms in different orders: 1e-4 of the tensor's scale).  (The name is kept so that the ids
+    of its cases stay the same; the fp32 matrix-core kernels it was written for are gone.)"""
     g = torch.Generator().manual_seed(cin * 100 + cout + mode)
     D, H, W = dims
     x = torch.randn(1, cin, D, H, W, generator=g).to(DEV)

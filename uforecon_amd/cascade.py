@@ -25,7 +25,8 @@ Align_Corners_Range = False      # TransMVSNet.py:21
 
 class Conv3d(nn.Module):
     """Parameters of conv + BatchNorm (+ ReLU) (module.py:110-143): `conv.weight`, `bn.*`.  Executed fused by
-    `unet3d.cost_reg_net` (one ufr_conv3d launch per block); the block has no forward of its own."""
+    `unet3d.cost_reg_net`: one launch per block, ufr_conv3d_planes (the 16-bit plane kernels) by default and ufr_conv3d (fp32) for the
+    shapes they do not have; the block has no forward of its own."""
 
     def __init__(self, in_channels, out_channels, stride=1, transposed=False):
         super().__init__()

@@ -460,7 +460,6 @@ struct WgradArgs {
   int B, Dp, Hp, Wp, Dq, Hq, Wq;
   long long n_p;     // B Dp Hp Wp
   int vox_per_block;
-  int seg, nseg;      // the matrix-core kernels: a wave's unit = seg voxels of a row, nseg of them per row
 };
 
 namespace {
@@ -650,278 +649,8 @@ __global__ void __launch_bounds__(256) channel_sum_kernel(const float* __restric
   }
 }
 
-// ---- weight gradients on the matrix cores (round 5): dW_k[a][b] = sum over voxel pairs of TP[p][a] TQ[q_k(p)][b] IS a
-// matrix product with the VOXELS as the k axis -- v_mfma_f32_16x16x4_f32 takes four voxel pairs per instruction, exact fp32.
-// Lane (i, kk) supplies TP[p0 + kk][a0 + i] as the A operand and TQ[q_k(p0 + kk)][b0 + i] as the B operand (a wave-load =
-// four 64-byte channel runs); the accumulator tiles (rows a, columns b) of NT consecutive taps stay in registers for the
-// whole launch, TP is read once per NT taps and the neighbours TQ[q_k] of consecutive taps hit in the L1.  No LDS stage, no
-// barrier in the loop.
-//
-// What bounds these kernels is the address arithmetic around each 32-cycle MFMA, so the work unit is a ROW SEGMENT: a wave
-// takes (b, z, y) of the P grid and `seg` consecutive x.  Everything that depends on the row -- the neighbour rows' byte
-// offsets, whether z + dz / y + dy leave the volume -- is wave-uniform and computed once per unit; per step of four voxels a
-// tap costs one add.  Loads go through BUFFER descriptors: an operand that does not exist (a neighbour outside the volume,
-// a voxel past the segment) gets an offset past the descriptor's extent and the hardware returns 0 -- no branch, no select,
-// nothing for the compiler to sink a load under (with `ok ? p[i] : 0` it moved each load into a divergent block with its
-// own wait: one memory round trip per tap).  Two operand sets are in flight: the loads of the next step are issued before
-// the MFMAs of the current one.  The launcher keeps both tensors below 2^30 bytes (else: the VALU kernels above).
-constexpr unsigned kWgOut = 0x80000000u;     // a lane's "no such voxel"; stays out of range after adding a row offset < 2^30
-constexpr unsigned kWgOutRow = 0x40000000u;  // a row's "no such row"; pushes every lane offset (< 2^30, or kWgOut) out of range
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg_rsrc(const float* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float wg_load(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0));
-}
-
-// unit u -> row (b, z, y) of the P grid and the x range [xs, xe) of its segment (all wave-uniform)
-struct WgradUnit {
-  int b, z, y, xs, xe;
-};
-__device__ __forceinline__ WgradUnit wgrad_unit(const WgradArgs& a, unsigned u) {
-  WgradUnit w;
-  // (segment-major: the four waves of a block take the same segment of four consecutive rows y, and share the rows
-  // y - 1 .. y + 4 of the fine grid in the L1)
-  const unsigned rows = (unsigned)(a.B * a.Dp * a.Hp);
-  const unsigned sg = u / rows;
-  unsigned r = u % rows;
-  w.y = (int)(r % (unsigned)a.Hp);
-  r /= (unsigned)a.Hp;
-  w.z = (int)(r % (unsigned)a.Dp);
-  w.b = (int)(r / (unsigned)a.Dp);
-  w.xs = (int)sg * a.seg;
-  w.xe = w.xs + a.seg < a.Wp ? w.xs + a.seg : a.Wp;
-  return w;
-}
-
-template <int CA, int CB, int S, int NT>
-__global__ void __launch_bounds__(256) conv3d_wgrad_mfma_kernel(WgradArgs a) {
-  static_assert(CA % 16 == 0 && CB % 16 == 0 && 27 % NT == 0, "whole 16-channel tiles, whole tap groups");
-  constexpr int NA = CA / 16, NB = CB / 16;
-  __shared__ __attribute__((aligned(16))) f32x4 red[NT * NA * NB][64];
-  const int k0 = blockIdx.y * NT;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
-  f32x4 acc[NT][NA][NB];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int ta = 0; ta < NA; ++ta)
-#pragma unroll
-      for (int tb = 0; tb < NB; ++tb) acc[t][ta][tb] = splat4(0.f);
-  const __amdgpu_buffer_rsrc_t rp = wg_rsrc(a.tp, (unsigned)a.n_p * CA * 4u);
-  const __amdgpu_buffer_rsrc_t rq = wg_rsrc(a.tq, (unsigned)(a.B * a.Dq * a.Hq * a.Wq) * CB * 4u);
-  struct Operands {
-    float ap[NA], bq[NT][NB];
-  };
-  const unsigned units = (unsigned)(a.B * a.Dp * a.Hp) * (unsigned)a.nseg;
-  for (unsigned u = blockIdx.x * 4 + wave; u < units; u += gridDim.x * 4) {
-    const WgradUnit w = wgrad_unit(a, u);
-    const unsigned prow = (unsigned)((w.b * a.Dp + w.z) * a.Hp + w.y) * (unsigned)a.Wp;      // voxel index of the P row
-    unsigned qrow[NT];                                                                       // byte offset of tap t's Q row
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int k = k0 + t, qz = w.z * S + k / 9 - 1, qy = w.y * S + (k / 3) % 3 - 1;
-      const bool ok = (unsigned)qz < (unsigned)a.Dq && (unsigned)qy < (unsigned)a.Hq;
-      qrow[t] = ok ? (unsigned)((w.b * a.Dq + qz) * a.Hq + qy) * (unsigned)a.Wq * (CB * 4u) : kWgOutRow;
-    }
-    auto load = [&](int x0, Operands& o) {
-      const int x = x0 + kk;
-      const bool okp = x < w.xe;
-      const unsigned poff = okp ? ((prow + (unsigned)x) * CA + i) * 4u : kWgOut;
-#pragma unroll
-      for (int ta = 0; ta < NA; ++ta) o.ap[ta] = wg_load(rp, poff + 64u * ta);
-      unsigned qx[3];                                  // the lane's byte offset within a Q row, per dx
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        const int xq = x * S + d - 1;
-        qx[d] = (okp && (unsigned)xq < (unsigned)a.Wq) ? ((unsigned)xq * CB + i) * 4u : kWgOut;
-      }
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        // (k0 is a multiple of 3 unless NT = 1, where the tap's dx is a wave-uniform pick)
-        const unsigned qxt = NT % 3 == 0 ? qx[t % 3] : (k0 % 3 == 0 ? qx[0] : k0 % 3 == 1 ? qx[1] : qx[2]);
-        const unsigned qoff = qxt + qrow[t];
-#pragma unroll
-        for (int tb = 0; tb < NB; ++tb) o.bq[t][tb] = wg_load(rq, qoff + 64u * tb);
-      }
-    };
-    auto contract = [&](const Operands& o) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int ta = 0; ta < NA; ++ta)
-#pragma unroll
-          for (int tb = 0; tb < NB; ++tb) acc[t][ta][tb] = mfma16(o.ap[ta], o.bq[t][tb], acc[t][ta][tb]);
-    };
-    Operands A, B;
-    load(w.xs, A);
-    for (int x0 = w.xs; x0 < w.xe; x0 += 8) {      // (a set past the end is zeros: at most one idle contraction)
-      load(x0 + 4, B);
-      contract(A);
-      load(x0 + 8, A);
-      contract(B);
-    }
-  }
-  // the four waves' partial tiles -> wave 0 (three rounds through one tile set of LDS), then one atomic per value
-  for (int w = 1; w < 4; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int ta = 0; ta < NA; ++ta)
-#pragma unroll
-          for (int tb = 0; tb < NB; ++tb) red[(t * NA + ta) * NB + tb][lane] = acc[t][ta][tb];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int ta = 0; ta < NA; ++ta)
-#pragma unroll
-          for (int tb = 0; tb < NB; ++tb) acc[t][ta][tb] += red[(t * NA + ta) * NB + tb][lane];
-    }
-  }
-  if (wave == 0) {     // lane (g, j): rows a = 16 ta + 4 g + r, column b = 16 tb + j
-    const int g = lane >> 4, j = lane & 15;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int ta = 0; ta < NA; ++ta)
-#pragma unroll
-        for (int tb = 0; tb < NB; ++tb)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x = acc[t][ta][tb][r];
-            if (x != 0.f) atomicAdd(a.dw + ((size_t)(16 * ta + 4 * g + r) * CB + 16 * tb + j) * 27 + k0 + t, x);
-          }
-  }
-}
-
-// ... and the layers with 8 channels on the fine side (the 8 x 8 head at full resolution, 16 x 8 of conv1 / conv11): TWO taps
-// share an instruction -- columns (t, b) = 2 taps x 8 channels, rows a (8 of 16 used for CA = 8); the 27 taps are 14
-// instructions per four voxel pairs, TP[p] is loaded once for all of them.  The lane's tap of pair m is 2 m + h (h = the
-// lane's column half), so the row offsets are per lane here (14 registers per unit); which of its taps look left / right
-// of x is a per-lane constant bit mask, and a step turns "x - 1 / x + 1 leaves the row" into the set of pairs to blank.
-template <int CA, int S>
-__global__ void __launch_bounds__(256) conv3d_wgrad_mfma8_kernel(WgradArgs a) {
-  static_assert(CA == 8 || CA == 16, "rows");
-  constexpr int CB = 8, NP = 14;                       // tap pairs (2 m, 2 m + 1); the last one is tap 26 alone
-  __shared__ __attribute__((aligned(16))) f32x4 red[NP][64];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4, h = i >> 3;
-  f32x4 acc[NP];
-#pragma unroll
-  for (int m = 0; m < NP; ++m) acc[m] = splat4(0.f);
-  const __amdgpu_buffer_rsrc_t rp = wg_rsrc(a.tp, (unsigned)a.n_p * CA * 4u);
-  const __amdgpu_buffer_rsrc_t rq = wg_rsrc(a.tq, (unsigned)(a.B * a.Dq * a.Hq * a.Wq) * CB * 4u);
-  // bit m of mdx[d]: this lane's tap of pair m has dx = d - 1
-  unsigned mdx[3] = {0u, 0u, 0u};
-#pragma unroll
-  for (int m = 0; m < NP; ++m) {
-    const int k = 2 * m + h;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) mdx[d] |= (k % 3 == d ? 1u : 0u) << m;
-  }
-  struct Operands {
-    float ap, bq[NP];
-  };
-  const unsigned units = (unsigned)(a.B * a.Dp * a.Hp) * (unsigned)a.nseg;
-  for (unsigned u = blockIdx.x * 4 + wave; u < units; u += gridDim.x * 4) {
-    const WgradUnit w = wgrad_unit(a, u);
-    const unsigned prow = (unsigned)((w.b * a.Dp + w.z) * a.Hp + w.y) * (unsigned)a.Wp;
-    // byte offset of (the lane's tap of pair m, channel i & 7) for the voxel x = 0 of the row; "negative" values wrap and come
-    // back in range when x is added, or are blanked because x - 1 is outside
-    unsigned qrow[NP];
-#pragma unroll
-    for (int m = 0; m < NP; ++m) {
-      const int k = 2 * m + h, qz = w.z * S + k / 9 - 1, qy = w.y * S + (k / 3) % 3 - 1, dx = k % 3 - 1;
-      const bool ok = k < 27 && (unsigned)qz < (unsigned)a.Dq && (unsigned)qy < (unsigned)a.Hq;
-      qrow[m] = ok ? ((unsigned)((w.b * a.Dq + qz) * a.Hq + qy) * (unsigned)a.Wq + (unsigned)(kk * S + dx)) * (CB * 4u) + (unsigned)(i & 7) * 4u
-                   : kWgOut;
-    }
-    auto load = [&](int x0, Operands& o) {
-      const int x = x0 + kk;
-      const bool okp = x < w.xe;
-      o.ap = wg_load(rp, (okp && i < CA) ? ((prow + (unsigned)x) * CA + i) * 4u : kWgOut);
-      unsigned blank = 0u;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) blank |= (okp && (unsigned)(x * S + d - 1) < (unsigned)a.Wq) ? 0u : mdx[d];
-      const unsigned xb = (unsigned)x0 * (S * CB * 4u);       // wave-uniform
-#pragma unroll
-      for (int m = 0; m < NP; ++m) o.bq[m] = wg_load(rq, ((blank >> m) & 1u) ? kWgOut : qrow[m] + xb);
-    };
-    auto contract = [&](const Operands& o) {
-#pragma unroll
-      for (int m = 0; m < NP; ++m) acc[m] = mfma16(o.ap, o.bq[m], acc[m]);
-    };
-    Operands A, B;
-    load(w.xs, A);
-    for (int x0 = w.xs; x0 < w.xe; x0 += 8) {
-      load(x0 + 4, B);
-      contract(A);
-      load(x0 + 8, A);
-      contract(B);
-    }
-  }
-  for (int w = 1; w < 4; ++w) {
-    __syncthreads();
-    if (wave == w) {
-#pragma unroll
-      for (int m = 0; m < NP; ++m) red[m][lane] = acc[m];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int m = 0; m < NP; ++m) acc[m] += red[m][lane];
-    }
-  }
-  if (wave == 0) {     // lane (g, j): rows a = 4 g + r, column j = (tap 2 m + (j >> 3), b = j & 7)
-    const int g = lane >> 4, j = lane & 15;
-#pragma unroll
-    for (int m = 0; m < NP; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int aa = 4 * g + r, k = 2 * m + (j >> 3);
-        const float x = acc[m][r];
-        if (aa < CA && k < 27 && x != 0.f) atomicAdd(a.dw + ((size_t)aa * CB + (j & 7)) * 27 + k, x);
-      }
-  }
-}
-
-constexpr int kWgNtSmall = 9, kWgNtMid = 3;   // taps per pass of the matrix-core kernel (small / mid channel products)
-constexpr int kWgWaves = 4096;    // waves in flight per launch: 4 per SIMD
-constexpr int kWgWaves8 = 3072;   // ... 3 per SIMD at the 8-channel kernel's ~150 registers
 template <int CA, int CB, int S>
 hipError_t launch_wgrad_t(WgradArgs a, hipStream_t s) {
-  // (the matrix-core kernels address both tensors with byte offsets below kWgOutRow)
-  const bool small = a.n_p * CA * 4 < (1ll << 30) && (long long)a.B * a.Dq * a.Hq * a.Wq * CB * 4 < (1ll << 30);
-  constexpr bool kPair = CA % 16 == 0 && CB % 16 == 0, kEight = CB == 8 && (CA == 8 || CA == 16);
-  if constexpr (kPair || kEight) {
-    // measured per layer at the three stages' sizes (tools/dev/conv3d_bwd_probe.py): below these volumes the per-unit setup and the
-    // closing reduction outweigh the contraction, and the VALU kernels below win
-    const bool large = a.n_p >= (kPair ? 100000 : 500000);
-    if (small && large) {
-      // units: whole rows, halved until there are a few per wave slot (never below 32 voxels = 8 steps)
-      const long long rows = (long long)a.B * a.Dp * a.Hp;
-      a.seg = (a.Wp + 3) / 4 * 4;
-      while (rows * ((a.Wp + a.seg - 1) / a.seg) < 4 * kWgWaves && a.seg > 32) a.seg = (a.seg / 2 + 3) / 4 * 4;
-      a.nseg = (a.Wp + a.seg - 1) / a.seg;
-      const long long units = rows * a.nseg;
-      if constexpr (kPair) {
-        constexpr int NT = CA * CB <= 256 ? kWgNtSmall : CA * CB <= 1024 ? kWgNtMid : 1;   // 4 NT (CA/16) (CB/16) accumulator registers
-        long long blocks = kWgWaves / 4 * NT / 27;
-        if (blocks < 16) blocks = 16;
-        if (blocks > (units + 3) / 4) blocks = (units + 3) / 4;
-        hipLaunchKernelGGL((conv3d_wgrad_mfma_kernel<CA, CB, S, NT>), dim3((unsigned)blocks, 27 / NT), dim3(256), 0, s, a);
-      } else {
-        long long blocks = kWgWaves8 / 4;       // exactly the resident waves: the units are dealt round-robin
-        if (blocks > (units + 3) / 4) blocks = (units + 3) / 4;
-        hipLaunchKernelGGL((conv3d_wgrad_mfma8_kernel<CA, S>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-      }
-      return hipGetLastError();
-    }
-  }
   if constexpr (CB <= 8 && CA * CB <= 128) {
     // CAG coarse-side channels per thread (CAG CB <= 64), the groups on blockIdx.y; NT taps per pass (NT CAG CB <= 192), the
     // passes on blockIdx.z
@@ -953,7 +682,7 @@ hipError_t launch_wgrad_t(WgradArgs a, hipStream_t s) {
 hipError_t launch_conv3d_bwd_weight(const float* in, const float* d_out, float* d_weight, float* d_bias, int B, int D, int H, int W,
                                     int cin, int cout, int mode, hipStream_t s) {
   WgradArgs a;
-  a.dw = d_weight; a.B = B; a.vox_per_block = 0; a.seg = 0; a.nseg = 0;
+  a.dw = d_weight; a.B = B; a.vox_per_block = 0;
   int ca, cb, S;
   long long n_out;
   if (mode == kConvS1) {
@@ -968,8 +697,13 @@ hipError_t launch_conv3d_bwd_weight(const float* in, const float* d_out, float* 
   }
   a.n_p = (long long)B * a.Dp * a.Hp * a.Wp;
   if (a.n_p >= (1ll << 31) - 65536 || n_out >= (1ll << 40)) return hipErrorInvalidValue;     // the kernels index voxels with 32 bits
-  // round 6: the 16-bit matrix-core kernels (conv3d_wgrad_planes.hip) where they have the shape; they take the bias gradient
-  // along when TP is d_out (the convolutions).  The fp32 kernels take the shapes they do not have.
+  // Who takes what.  The 16-bit plane kernels (conv3d_wgrad_planes.hip) take every (ca, cb, S) of the U-Nets -- their table
+  // lists the same nine triples as UFR_WG_CASE below -- and the bias gradient along with it when TP is d_out (the
+  // convolutions); the transposed layers' bias gradient is channel_sum_kernel's.  They answer hipErrorInvalidValue only
+  // where a tensor is 2^31 bytes or more PER BATCH ELEMENT (their 31-bit buffer offsets; their brick count cannot overflow
+  // with n_p < 2^31), and only there the fp32 VALU kernels above run.  The fp32 matrix-core weight-gradient kernels that
+  // stood between the two wanted both WHOLE tensors below 2^30 bytes, which the plane kernels always accept: they could not
+  // be reached and were removed.
   const bool bias_rides = d_bias != nullptr && mode != kDeconvS2;
   hipError_t e = launch_conv3d_wgrad_planes(a.tp, a.tq, a.dw, bias_rides ? d_bias : nullptr, B, a.Dp, a.Hp, a.Wp, a.Dq, a.Hq, a.Wq, ca, cb, S, s);
   if (e == hipSuccess) {

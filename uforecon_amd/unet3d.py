@@ -1,4 +1,6 @@
-"""The two 3-D U-Nets of the frustum construction on the HIP convolution kernel (csrc/conv3d.hip, `ufr_conv3d`):
+"""The two 3-D U-Nets of the frustum construction on the HIP convolution kernels: the 16-bit plane kernels (csrc/conv3d_planes.hip,
+`ufr_conv3d_planes`) wherever they have the layer's shape -- every layer but conv0, whose input has one channel -- and the fp32 kernels
+(csrc/conv3d.hip, `ufr_conv3d`) for the rest; `_layer` is the one place that decides.
 
   cost_reg_net         CostRegNet.forward        code1/encoder_utils/fmt/module.py:469-500
   cost_reg_net_weight  CostRegNetWeight.forward  code1/encoder_utils/fmt/module.py:502-543 (via MVSVolume, feature_volume.py:114-121)
@@ -72,82 +74,38 @@ class _Bounds:
             self._b[id(t)] = (t, bound)
 
 
-def _s1(t, weight, planes: bool, bounds: "_Bounds" = None, **kw):
-    """One stride-1 layer: on the 16-bit matrix cores (ufr_conv3d_planes: fp16 plane products, fp32 accumulate, the input
-    brick staged through LDS -- 2 .. 5 x the fp32 kernels, csrc/conv3d_planes.hip) when `planes` and the kernel family has
-    the layer, else the fp32 kernel.  The planes' scale comes from the input's |max| (`_Bounds`).  Returns what ops.conv3d
-    returns."""
-    cin = t.shape[-1]
-    flip = kw.pop("flip", False)
-    w2 = kw.get("weight2")
-    cout = weight.shape[1] if flip else weight.shape[0]
-    if planes and ops.conv3d_planes_supported(cin, cout, 0 if w2 is None else w2.shape[0], S1):
-        b = bounds if bounds is not None else _Bounds()
-        r = ops.conv3d_planes(t, b.of(t), weight, flip=flip, want_absmax=(b.slot(t) if bounds is not None and not kw.get("out_ncdhw") else False), **kw)
+# what a layer's data gradient executes: the stride-1 convolution with mirrored taps, and the strided pair each other's twin
+_ADJOINT = {S1: S1, S2: T2, T2: S2}
+
+
+def _layer(t, weight, mode, bounds: _Bounds, d_in_shape=None, **kw):
+    """One layer of either U-Net -- or, with ``d_in_shape`` = the shape of the layer's input, the layer's DATA GRADIENT
+    (``t`` = d_out, ``skip`` = a gradient to accumulate); ``weight`` is the layer's forward weight in both cases.
+    On the 16-bit matrix cores (ufr_conv3d_planes: fp16 plane products, fp32 accumulate, the input brick staged through LDS
+    -- 2 .. 5 x the fp32 kernels, csrc/conv3d_planes.hip) where the kernel family has the shape, else on the fp32 kernels.
+    The planes' scale comes from the input's |max|: ``bounds`` hands it from layer to layer.  A second head (``weight2``)
+    returns ``(out, out2)``, everything else the output."""
+    grad = d_in_shape is not None
+    run = _ADJOINT[mode] if grad else mode                      # the convolution the kernel executes
+    cout = weight.shape[1] if (mode == T2) != grad else weight.shape[0]      # (a transposed weight and a gradient each swap the roles)
+    w2, ncdhw = kw.get("weight2"), kw.get("out_ncdhw", False)
+    # (a stride-2 layer's gradient is the transposed kernel's output only where the input was exactly twice d_out)
+    fits = not (grad and mode == S2) or tuple(d_in_shape[1:4]) == tuple(2 * n for n in t.shape[1:4])
+    if fits and ops.conv3d_planes_supported(t.shape[-1], cout, 0 if w2 is None else w2.shape[0], run):
+        r = ops.conv3d_planes(t, bounds.of(t), weight, flip=grad and mode == S1, want_absmax=False if ncdhw else bounds.slot(t),
+                              mode=run, **kw)
         if w2 is not None:
             return r[0], r[1]
-        b.put(r[0], r[1])
+        bounds.put(r[0], r[1])
         return r[0]
-    if flip:
-        return ops.conv3d_bwd_data(t, weight, S1, (*t.shape[:4], cout), accumulate=kw.get("skip"))
-    if planes and bounds is not None and cout <= 16 and w2 is None and not kw.get("out_ncdhw"):
+    if grad:
+        return ops.conv3d_bwd_data(t, weight, mode, d_in_shape, accumulate=kw.get("skip"))
+    if mode == S1 and cout <= 16 and w2 is None and not ncdhw:
         # an fp32-kernel layer in front of plane layers (conv0): its store takes the bound the next layer wants
         out, omax = ops.conv3d(t, weight, S1, want_absmax=bounds.slot(t), **kw)
         bounds.put(out, omax)
         return out
-    return ops.conv3d(t, weight, S1, **kw)
-
-
-def _s2(t, weight, planes: bool, bounds: "_Bounds" = None, **kw):
-    """One stride-2 layer (conv1 / conv3 / conv5), the same way.  ``weight`` (cout, cin, 3,3,3)."""
-    if planes and ops.conv3d_planes_supported(t.shape[-1], weight.shape[0], 0, S2):
-        b = bounds if bounds is not None else _Bounds()
-        out, omax = ops.conv3d_planes(t, b.of(t), weight, want_absmax=(b.slot(t) if bounds is not None else False), mode=S2, **kw)
-        b.put(out, omax)
-        return out
-    return ops.conv3d(t, weight, S2, **kw)
-
-
-def _t2(t, weight, planes: bool, bounds: "_Bounds" = None, **kw):
-    """One transposed stride-2 layer (conv7 / conv9 / conv11); ``weight`` (cin, cout, 3,3,3)."""
-    if planes and ops.conv3d_planes_supported(t.shape[-1], weight.shape[1], 0, T2):
-        b = bounds if bounds is not None else _Bounds()
-        out, omax = ops.conv3d_planes(t, b.of(t), weight, want_absmax=(b.slot(t) if bounds is not None else False), mode=T2, **kw)
-        b.put(out, omax)
-        return out
-    return ops.conv3d(t, weight, T2, **kw)
-
-
-def _layer(t, weight, mode, planes: bool, bounds: "_Bounds" = None, **kw):
-    if mode == S1:
-        return _s1(t, weight, planes, bounds, **kw)
-    if mode == S2:
-        return _s2(t, weight, planes, bounds, **kw)
-    return _t2(t, weight, planes, bounds, **kw)
-
-
-def _s2_bwd_data(d_out, weight, in_shape, accumulate=None, bounds: "_Bounds" = None):
-    """Data gradient of a stride-2 layer = the transposed stride-2 convolution of d_out with the layer's forward weight
-    (cout, cin, 3,3,3) read as a transposed-convolution weight (its layout as it stands)."""
-    cout, cin = weight.shape[0], weight.shape[1]
-    if ops.conv3d_planes_supported(cout, cin, 0, T2) and tuple(in_shape[1:4]) == tuple(2 * n for n in d_out.shape[1:4]):
-        b = bounds if bounds is not None else _Bounds()
-        out, omax = ops.conv3d_planes(d_out, b.of(d_out), weight, skip=accumulate, want_absmax=(b.slot(d_out) if bounds is not None else False), mode=T2)
-        b.put(out, omax)
-        return out
-    return ops.conv3d_bwd_data(d_out, weight, S2, in_shape, accumulate=accumulate)
-
-
-def _t2_bwd_data(d_out, weight, in_shape, accumulate=None, bounds: "_Bounds" = None):
-    """Data gradient of a transposed stride-2 layer = the stride-2 convolution of d_out with the layer's forward weight
-    (cin, cout, 3,3,3) read as a convolution weight (rows = cin): on the plane kernels where they have the shape."""
-    cin, cout = weight.shape[0], weight.shape[1]
-    if ops.conv3d_planes_supported(cout, cin, 0, S2):
-        b = bounds if bounds is not None else _Bounds()
-        out, omax = ops.conv3d_planes(d_out, b.of(d_out), weight, skip=accumulate, want_absmax=(b.slot(d_out) if bounds is not None else False), mode=S2)
-        b.put(out, omax)
-        return out
-    return ops.conv3d_bwd_data(d_out, weight, T2, in_shape, accumulate=accumulate)
+    return ops.conv3d(t, weight, mode, **kw)
 
 
 def _unet(x_cl, layer):
@@ -163,7 +121,7 @@ def _unet(x_cl, layer):
 
 
 @torch.no_grad()
-def cost_reg_net(m, x: torch.Tensor, planes: bool = True) -> torch.Tensor:
+def cost_reg_net(m, x: torch.Tensor) -> torch.Tensor:
     """(B,1,D,H,W) similarity volume -> (B,1,D,H,W) cost volume.  Every inner layer = convolution + BatchNorm (eval mode,
     folded to one fma after the sum) + ReLU in one kernel."""
     if m.training:
@@ -174,10 +132,10 @@ def cost_reg_net(m, x: torch.Tensor, planes: bool = True) -> torch.Tensor:
     def layer(name, t, mode, skip):
         blk = getattr(m, name)
         scale, shift = _bn_fold(blk.bn)
-        return _layer(t, blk.conv.weight, mode, planes, bounds, bn_scale=scale, bn_shift=shift, relu=True, skip=skip)
+        return _layer(t, blk.conv.weight, mode, bounds, bn_scale=scale, bn_shift=shift, relu=True, skip=skip)
 
     x = _unet(_input_cl(x), layer)
-    return _s1(x, m.prob.weight, planes, bounds, out_ncdhw=True)
+    return _layer(x, m.prob.weight, S1, bounds, out_ncdhw=True)
 
 
 def _needs_grad(m, x: torch.Tensor) -> bool:
@@ -211,10 +169,10 @@ class CostRegNetWeightFn(torch.autograd.Function):
 
         def layer(name, t, mode, skip):
             acts["in." + name] = t
-            return _layer(t, P[name + ".weight"], mode, True, bounds, bias=P[name + ".bias"], skip=skip)
+            return _layer(t, P[name + ".weight"], mode, bounds, bias=P[name + ".bias"], skip=skip)
 
         y = _unet(x_cl, layer)
-        feat, wsig = _s1(y, P["features.weight"], True, bounds, out_ncdhw=True, weight2=P["weights.weight"])
+        feat, wsig = _layer(y, P["features.weight"], S1, bounds, out_ncdhw=True, weight2=P["weights.weight"])
         ctx.acts, ctx.y = acts, y
         # the parameters through save_for_backward: an in-place update between this forward and its backward (an optimizer
         # step in between) is then an error, not a backward on new weights with old activations
@@ -246,7 +204,7 @@ class CostRegNetWeightFn(torch.autograd.Function):
         # the 1-channel head's adjoint on the fp32 kernel, then the 8-channel one on the matrix cores with the sum fused
         bounds = _Bounds()
         d_y = ops.conv3d_bwd_data(d_w, P["weights.weight"], S1, tuple(y.shape))
-        d_y = _s1(d_f, P["features.weight"], True, bounds, flip=True, skip=d_y)
+        d_y = _layer(d_f, P["features.weight"], S1, bounds, d_in_shape=tuple(y.shape), skip=d_y)
 
         def back(name, mode, d_out, accumulate=None, need_data=True):
             t = acts["in." + name]
@@ -254,13 +212,9 @@ class CostRegNetWeightFn(torch.autograd.Function):
                                                                                    out=(gview[name + ".weight"], gview[name + ".bias"]))
             if not need_data:
                 return None
-            if mode == S1 and t.shape[-1] > 1:
-                return _s1(d_out, P[name + ".weight"], True, bounds, flip=True, skip=accumulate)
-            if mode == T2:
-                return _t2_bwd_data(d_out, P[name + ".weight"], tuple(t.shape), accumulate, bounds)
-            if mode == S2:
-                return _s2_bwd_data(d_out, P[name + ".weight"], tuple(t.shape), accumulate, bounds)
-            return ops.conv3d_bwd_data(d_out, P[name + ".weight"], mode, tuple(t.shape), accumulate=accumulate)
+            if mode == S1 and t.shape[-1] == 1:      # conv0: the 1-channel d_in comes from the fp32 kernel
+                return ops.conv3d_bwd_data(d_out, P[name + ".weight"], S1, tuple(t.shape), accumulate=accumulate)
+            return _layer(d_out, P[name + ".weight"], mode, bounds, d_in_shape=tuple(t.shape), skip=accumulate)
 
         # y = c0 + conv11(x9), x9 = c2 + conv9(x7), x7 = c4 + conv7(x6), x6 = conv6(conv5(c4)), c4 = conv4(conv3(c2)), ...
         d_x9 = back("conv11", T2, d_y)
@@ -292,12 +246,12 @@ def cost_reg_net_weight(m, x: torch.Tensor):
         return _cost_reg_net_weight_hip(m, x)
 
 
-def _cost_reg_net_weight_hip(m, x: torch.Tensor, planes: bool = True):
+def _cost_reg_net_weight_hip(m, x: torch.Tensor):
     bounds = _Bounds()
 
     def layer(name, t, mode, skip):
         conv = getattr(m, name)
-        return _layer(t, conv.weight, mode, planes, bounds, bias=conv.bias, skip=skip)
+        return _layer(t, conv.weight, mode, bounds, bias=conv.bias, skip=skip)
 
     x = _unet(_input_cl(x), layer)
-    return _s1(x, m.features.weight, planes, bounds, out_ncdhw=True, weight2=m.weights.weight)
+    return _layer(x, m.features.weight, S1, bounds, out_ncdhw=True, weight2=m.weights.weight)
