@@ -32,7 +32,7 @@ enum ufr_status {
 
 /* Version of this header's ABI (argument lists, struct layouts, packed-blob layout).  ufr_version() returns the value
  * the library was built with: a binding must refuse a library whose version differs (uforecon_amd/_lib.py does). */
-#define UFR_ABI_VERSION 505
+#define UFR_ABI_VERSION 506
 
 #define UFR_MAX_VIEWS 7
 #define UFR_NUM_STAGES 3
@@ -604,6 +604,45 @@ size_t ufr_points_nn_dist_workspace_bytes(int64_t nq);
 int ufr_points_nn_dist(const double* query, int64_t nq, const double* ref, const int64_t* ref_keys, int64_t nr,
                        const double* origin, double cell, double max_dist, double* dist, double* mean_out, void* workspace,
                        size_t workspace_bytes, ufr_stream stream);
+
+/* ---- depth-map fusion (ABI 506) ------------------------------------------------------------------------------
+ * The device side of code1/encoder_utils/depth_fusion.py (MVSNet-style geometric-consistency filtering of rendered depth
+ * maps into a point cloud); uforecon_amd/depth_fusion.py is the caller that strings these together.
+ *
+ * ufr_depth_consistency: reproject_with_depth + check_geometric_consistency (:35-90) of one reference view against its S
+ *   source views (1 <= S <= UFR_DEPTH_MAX_SOURCES), and the accumulation of filter_depth (:176-192).  ref_depth (H,W) fp32
+ *   (device); src_depth: HOST array of S device pointers, map s being (src_hw[2s], src_hw[2s+1]) fp32 -- sizes need not
+ *   equal the reference's; src_hw: host int32[2S].  mats: DEVICE table of S records of UFR_DEPTH_PAIR_DOUBLES fp64, the
+ *   row-major matrices the caller forms with the reference's own numpy expressions in the dtypes its inputs have, then
+ *   widens: inv(K_ref) 3x3 | E_src inv(E_ref) 4x4 | K_src 3x3 | inv(K_src) 3x3 | E_ref inv(E_src) 4x4 | K_ref 3x3.
+ *   All arithmetic is fp64, narrowed to fp32 where numpy narrows (x_src, y_src, the sampled depth, depth_reprojected,
+ *   x / y_reprojected, depth_diff, relative_depth_diff); relative_depth_diff < (float)geo_depth_thres is an fp32 comparison
+ *   (numpy 2), dist < geo_pixel_thres an fp64 one.  The source depth is sampled as cv2.remap(INTER_LINEAR, constant border
+ *   0) does, restated in csrc/depth_fusion.hip (1/32-pixel coordinates; not compared with a real OpenCV); a non-finite or
+ *   far-away coordinate samples 0, and no input makes the kernel read outside a depth map.
+ *   Outputs (device, (H,W)): mask_sum int32 = the number of consistent sources; mask uint8 = mask_sum >= geo_mask_thres;
+ *   depth_avg fp64 = (fp32 sum of the consistent depth_reprojected in source order + ref_depth) / (mask_sum + 1);
+ *   pair_masks (S,H,W) uint8, nullable: the per-pair masks.  Does not synchronise.
+ * ufr_depth_points_*: the valid pixels (mask != 0) of one reference view as points, in row-major pixel order (:202-214).
+ *   Two calls with the same mask, H, W and workspace (>= ufr_depth_points_workspace_bytes(H, W), device):
+ *     ufr_depth_points_count: *n_host = N, the number of valid pixels.  SYNCHRONISES the stream.
+ *     ufr_depth_points_emit: xyz (N,3) fp32 = (inv_e [inv_k (x, y, 1) depth_avg ; 1])[:3] in fp64, narrowed; rgb (N,3)
+ *       uint8 = color (H,W,3) uint8 at the pixel.  depth_avg (H,W) fp64, color: device; inv_k (3x3), inv_e (4x4): host,
+ *       row-major fp64.  capacity: the rows of xyz and rgb; capacity < N is an error (the count is read back from the
+ *       workspace: SYNCHRONISES the stream), nothing beyond N is written.  xyz / rgb are nullable when N = 0, which is
+ *       legal and writes nothing.  No atomics: the output is deterministic.
+ * H, W >= 1 and H * W < 2^31 throughout.                                                                            */
+#define UFR_DEPTH_MAX_SOURCES 64
+#define UFR_DEPTH_PAIR_DOUBLES 68
+int ufr_depth_consistency(const float* ref_depth, int32_t H, int32_t W, const float* const* src_depth, const int32_t* src_hw,
+                          const double* mats, int32_t S, double geo_pixel_thres, double geo_depth_thres, int32_t geo_mask_thres,
+                          int32_t* mask_sum, uint8_t* mask, double* depth_avg, uint8_t* pair_masks, ufr_stream stream);
+size_t ufr_depth_points_workspace_bytes(int32_t H, int32_t W);
+int ufr_depth_points_count(const uint8_t* mask, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, int64_t* n_host,
+                           ufr_stream stream);
+int ufr_depth_points_emit(const uint8_t* mask, const double* depth_avg, const uint8_t* color, int32_t H, int32_t W,
+                          const double* inv_k, const double* inv_e, void* workspace, size_t workspace_bytes, float* xyz,
+                          uint8_t* rgb, int64_t capacity, ufr_stream stream);
 
 /* Pixel-wise view weights of the first cascade stage and the weighted aggregate (DepthNet.forward,
  * code1/encoder_utils/fmt/TransMVSNet.py:80-97 with PixelwiseNet :23-41), one pass over the similarity volume:

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # UFR_LIB selects an alternative in-tree build (A/B kernel variants during development)
 LIB_PATH = os.environ.get("UFR_LIB") or os.path.join(HERE, "lib", "libufr.so")
 
-ABI_VERSION = 505   # = UFR_ABI_VERSION of include/ufr.h; load() refuses a library built against another header
+ABI_VERSION = 506   # = UFR_ABI_VERSION of include/ufr.h; load() refuses a library built against another header
 MAX_VIEWS = 7
 NUM_STAGES = 3
 TOKEN_DIM = 80
@@ -142,6 +142,11 @@ SIGNATURES = {
     "ufr_points_thin": (C.c_int, [vp, vp, vp, i64, C.c_double, vp, vp, sz, C.POINTER(i32), vp]),
     "ufr_points_nn_dist_workspace_bytes": (sz, [i64]),
     "ufr_points_nn_dist": (C.c_int, [vp, i64, vp, vp, i64, C.POINTER(C.c_double), C.c_double, C.c_double, vp, vp, vp, sz, vp]),
+    "ufr_depth_consistency": (C.c_int, [vp, i32, i32, C.POINTER(vp), C.POINTER(i32), vp, i32, C.c_double, C.c_double, i32,
+                                        vp, vp, vp, vp, vp]),
+    "ufr_depth_points_workspace_bytes": (sz, [i32, i32]),
+    "ufr_depth_points_count": (C.c_int, [vp, i32, i32, vp, sz, C.POINTER(i64), vp]),
+    "ufr_depth_points_emit": (C.c_int, [vp, vp, vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, sz, vp, vp, i64, vp]),
     "ufr_pixelwise_view_weights": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ufr_deform_conv2d_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ufr_deform_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),

@@ -1510,6 +1510,103 @@ int ufr_pixelwise_view_weights(const float* similarity, const float* params, flo
   return UFR_OK;
 }
 
+// ------------------------------------------------------------------ depth-map fusion
+namespace {
+struct DepthPointsWorkspace {   // [block sums int64 | block offsets int64 | total int64]
+  long long *block_tot, *block_off, *total;
+  size_t bytes;
+  DepthPointsWorkspace(void* base, long long n) {
+    const size_t blocks = (size_t)depth_points_blocks(n);
+    char* b = static_cast<char*>(base);
+    size_t off = 0;
+    block_tot = reinterpret_cast<long long*>(b + off);
+    off += align_up(blocks * sizeof(long long));
+    block_off = reinterpret_cast<long long*>(b + off);
+    off += align_up(blocks * sizeof(long long));
+    total = reinterpret_cast<long long*>(b + off);
+    off += align_up(sizeof(long long));
+    bytes = off;
+  }
+};
+
+int depth_image_check(const char* who, int32_t H, int32_t W) {
+  UFR_REQUIRE(H >= 1 && W >= 1, "%s: image %dx%d (H and W must be >= 1)", who, H, W);
+  UFR_REQUIRE((long long)H * W < (1ll << 31), "%s: image %dx%d has 2^31 pixels or more", who, H, W);
+  return UFR_OK;
+}
+
+int depth_points_check(const char* who, const uint8_t* mask, int32_t H, int32_t W, void* ws, size_t ws_bytes) {
+  UFR_REQUIRE(mask && ws, "%s: null argument", who);
+  if (int rc = depth_image_check(who, H, W)) return rc;
+  const size_t need = DepthPointsWorkspace(nullptr, (long long)H * W).bytes;
+  if (ws_bytes < need) return fail(UFR_ERR_WORKSPACE, "%s: workspace %zu bytes, needs %zu", who, ws_bytes, need);
+  return UFR_OK;
+}
+}  // namespace
+
+int ufr_depth_consistency(const float* ref_depth, int32_t H, int32_t W, const float* const* src_depth, const int32_t* src_hw,
+                          const double* mats, int32_t S, double geo_pixel_thres, double geo_depth_thres, int32_t geo_mask_thres,
+                          int32_t* mask_sum, uint8_t* mask, double* depth_avg, uint8_t* pair_masks, ufr_stream stream) {
+  const char* who = "ufr_depth_consistency";
+  UFR_REQUIRE(ref_depth && src_depth && src_hw && mats && mask_sum && mask && depth_avg, "%s: null argument", who);
+  if (int rc = depth_image_check(who, H, W)) return rc;
+  UFR_REQUIRE(S >= 1 && S <= UFR_DEPTH_MAX_SOURCES, "%s: S %d (must be 1 .. %d)", who, S, UFR_DEPTH_MAX_SOURCES);
+  for (int k = 0; k < S; ++k) {
+    UFR_REQUIRE(src_depth[k], "%s: null argument (source %d)", who, k);
+    UFR_REQUIRE(src_hw[2 * k] >= 1 && src_hw[2 * k + 1] >= 1 && (long long)src_hw[2 * k] * src_hw[2 * k + 1] < (1ll << 31),
+                "%s: source %d is %dx%d (H and W must be >= 1, fewer than 2^31 pixels)", who, k, src_hw[2 * k], src_hw[2 * k + 1]);
+  }
+  UFR_REQUIRE(!std::isnan(geo_pixel_thres) && !std::isnan(geo_depth_thres), "%s: a threshold is NaN", who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ProfScope p("depth_consistency", s);
+  UFR_HIP(launch_depth_consistency(ref_depth, H, W, src_depth, src_hw, mats, S, geo_pixel_thres, (float)geo_depth_thres,
+                                   geo_mask_thres, mask_sum, mask, depth_avg, pair_masks, s));
+  return UFR_OK;
+}
+
+size_t ufr_depth_points_workspace_bytes(int32_t H, int32_t W) {
+  if (H < 1 || W < 1 || (long long)H * W >= (1ll << 31)) return 0;
+  return DepthPointsWorkspace(nullptr, (long long)H * W).bytes;
+}
+
+int ufr_depth_points_count(const uint8_t* mask, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, int64_t* n_host,
+                           ufr_stream stream) {
+  if (int rc = depth_points_check("ufr_depth_points_count", mask, H, W, workspace, workspace_bytes)) return rc;
+  UFR_REQUIRE(n_host, "ufr_depth_points_count: null argument (n_host)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DepthPointsWorkspace w(workspace, (long long)H * W);
+  {
+    ProfScope p("depth_points_count", s);
+    UFR_HIP(launch_depth_points_count(mask, (long long)H * W, w.block_tot, w.block_off, w.total, s));
+  }
+  long long tot = 0;
+  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  *n_host = (int64_t)tot;
+  return UFR_OK;
+}
+
+int ufr_depth_points_emit(const uint8_t* mask, const double* depth_avg, const uint8_t* color, int32_t H, int32_t W,
+                          const double* inv_k, const double* inv_e, void* workspace, size_t workspace_bytes, float* xyz,
+                          uint8_t* rgb, int64_t capacity, ufr_stream stream) {
+  const char* who = "ufr_depth_points_emit";
+  if (int rc = depth_points_check(who, mask, H, W, workspace, workspace_bytes)) return rc;
+  UFR_REQUIRE(depth_avg && color && inv_k && inv_e, "%s: null argument", who);
+  UFR_REQUIRE(capacity >= 0, "%s: capacity %lld", who, (long long)capacity);
+  UFR_REQUIRE(capacity == 0 || (xyz && rgb), "%s: null argument (xyz / rgb with capacity %lld)", who, (long long)capacity);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DepthPointsWorkspace w(workspace, (long long)H * W);
+  long long tot = 0;
+  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  UFR_REQUIRE(tot >= 0 && tot <= (long long)H * W, "%s: the workspace holds no count (call ufr_depth_points_count first)", who);
+  UFR_REQUIRE(capacity >= tot, "%s: capacity %lld is smaller than the %lld points counted", who, (long long)capacity, tot);
+  if (tot == 0) return UFR_OK;
+  ProfScope p("depth_points_emit", s);
+  UFR_HIP(launch_depth_points_emit(mask, depth_avg, color, H, W, inv_k, inv_e, w.block_off, xyz, rgb, tot, s));
+  return UFR_OK;
+}
+
 // ------------------------------------------------------------------ deformable convolution
 size_t ufr_deform_conv2d_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
   Carver c(nullptr);

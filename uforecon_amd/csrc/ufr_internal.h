@@ -157,6 +157,16 @@ hipError_t launch_thin_round(const double* pts, const long long* keys, const int
 hipError_t launch_nn_dist(const double* query, long long nq, const double* ref, const long long* keys, long long nr,
                           const double* origin, double cell, double max_dist, double* dist, double* block_sum,
                           long long* block_cnt, double* mean_out, hipStream_t s);
+// depth_fusion.hip: geometric-consistency filtering of depth maps and the ordered compaction of the valid pixels (see the file header)
+long long depth_points_blocks(long long n);   // blocks of the compaction kernels: sizes the per-block workspace arrays
+hipError_t launch_depth_consistency(const float* ref, int H, int W, const float* const* src_depth, const int* src_hw,
+                                    const double* mats, int S, double pix_thres, float depth_thres, int mask_thres, int* mask_sum,
+                                    unsigned char* mask, double* depth_avg, unsigned char* pair_masks, hipStream_t s);
+hipError_t launch_depth_points_count(const unsigned char* mask, long long n, long long* block_tot, long long* block_off,
+                                     long long* total, hipStream_t s);
+hipError_t launch_depth_points_emit(const unsigned char* mask, const double* depth_avg, const unsigned char* color, int H, int W,
+                                    const double* inv_k, const double* inv_e, const long long* block_off, float* xyz,
+                                    unsigned char* rgb, long long capacity, hipStream_t s);
 // conv2d.hip: the plain 2-D convolutions of FeatureNet on channel-last tensors, epilogue fused (see the file header)
 struct Conv2dArgs {
   const float* in;      // [B][H][W][CIN] (the stem: planar [B][3][H][W])

@@ -896,6 +896,81 @@ def nn_distance(query: torch.Tensor, ref: torch.Tensor, max_dist: float, return_
     return (dist, sums) if return_sums else dist
 
 
+# ---- depth-map fusion (csrc/depth_fusion.hip; uforecon_amd/depth_fusion.py strings these together)
+DEPTH_MAX_SOURCES = 64     # UFR_DEPTH_MAX_SOURCES of include/ufr.h
+DEPTH_PAIR_DOUBLES = 68    # UFR_DEPTH_PAIR_DOUBLES
+
+
+def depth_consistency(ref_depth: torch.Tensor, src_depths, mats: torch.Tensor, geo_pixel_thres: float = 1,
+                      geo_depth_thres: float = 0.01, geo_mask_thres: int = 2, return_pair_masks: bool = False):
+    """ufr_depth_consistency: one reference view against its S source views.  ``ref_depth`` (H,W) and every entry of
+    ``src_depths`` (its own (Hs,Ws)): CUDA float32, contiguous; ``mats`` (S, 68) CUDA float64, the six host-made matrices
+    of every pair (include/ufr.h).  Returns ``mask_sum`` int32, ``mask`` uint8 and ``depth_avg`` float64, all (H,W), and with
+    ``return_pair_masks`` the (S,H,W) uint8 per-pair masks.  Does not synchronise."""
+    p_ref = _dev(ref_depth, "ref_depth")
+    if ref_depth.dim() != 2:
+        raise UfrError(f"ref_depth: expected shape (H, W), got {tuple(ref_depth.shape)}")
+    src_depths = list(src_depths)
+    S = len(src_depths)
+    if not 1 <= S <= DEPTH_MAX_SOURCES:
+        raise UfrError(f"depth_consistency: {S} source views (must be 1 .. {DEPTH_MAX_SOURCES})")
+    ptrs = (C.c_void_p * S)()
+    hw = (C.c_int32 * (2 * S))()
+    for k, t in enumerate(src_depths):
+        ptrs[k] = _dev(t, f"src_depths[{k}]")
+        if t.dim() != 2:
+            raise UfrError(f"src_depths[{k}]: expected shape (H, W), got {tuple(t.shape)}")
+        hw[2 * k], hw[2 * k + 1] = int(t.shape[0]), int(t.shape[1])
+    p_mats = _dev(mats, "mats", torch.float64)
+    if tuple(mats.shape) != (S, DEPTH_PAIR_DOUBLES):
+        raise UfrError(f"mats: expected shape ({S}, {DEPTH_PAIR_DOUBLES}), got {tuple(mats.shape)}")
+    H, W = int(ref_depth.shape[0]), int(ref_depth.shape[1])
+    dev = ref_depth.device
+    mask_sum = torch.empty((H, W), dtype=torch.int32, device=dev)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    depth_avg = torch.empty((H, W), dtype=torch.float64, device=dev)
+    pair = torch.empty((S, H, W), dtype=torch.uint8, device=dev) if return_pair_masks else None
+    _lib.check(_lib.load().ufr_depth_consistency(p_ref, H, W, ptrs, hw, p_mats, S, float(geo_pixel_thres), float(geo_depth_thres),
+                                                 int(geo_mask_thres), mask_sum.data_ptr(), mask.data_ptr(), depth_avg.data_ptr(),
+                                                 None if pair is None else pair.data_ptr(), _stream()), "ufr_depth_consistency")
+    return (mask_sum, mask, depth_avg, pair) if return_pair_masks else (mask_sum, mask, depth_avg)
+
+
+def depth_points(mask: torch.Tensor, depth_avg: torch.Tensor, color: torch.Tensor, inv_k, inv_e):
+    """ufr_depth_points_*: the pixels with ``mask`` != 0 as points, in row-major pixel order.  ``mask`` (H,W) CUDA uint8,
+    ``depth_avg`` (H,W) CUDA float64, ``color`` (H,W,3) CUDA uint8; ``inv_k`` 3x3 and ``inv_e`` 4x4: host arrays (widened to
+    float64).  Returns ``xyz`` (N,3) float32 and ``rgb`` (N,3) uint8 on the device; N = 0 gives empty tensors.  Synchronises
+    (the count sizes the outputs)."""
+    import numpy as np
+
+    p_mask = _dev(mask, "mask", torch.uint8)
+    p_avg = _dev(depth_avg, "depth_avg", torch.float64)
+    p_col = _dev(color, "color", torch.uint8)
+    if mask.dim() != 2 or depth_avg.shape != mask.shape or tuple(color.shape) != (*mask.shape, 3):
+        raise UfrError(f"depth_points: mask {tuple(mask.shape)}, depth_avg {tuple(depth_avg.shape)}, color {tuple(color.shape)}: "
+                       "expected (H, W), (H, W), (H, W, 3)")
+    ik = np.ascontiguousarray(np.asarray(inv_k, np.float64))
+    ie = np.ascontiguousarray(np.asarray(inv_e, np.float64))
+    if ik.shape != (3, 3) or ie.shape != (4, 4):
+        raise UfrError(f"depth_points: inv_k {ik.shape}, inv_e {ie.shape}: expected (3, 3) and (4, 4)")
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    lib = _lib.load()
+    nbytes = lib.ufr_depth_points_workspace_bytes(H, W)
+    if nbytes == 0:
+        raise UfrError(f"depth_points: image {H}x{W} unsupported (H, W >= 1, fewer than 2^31 pixels)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+    n = C.c_int64(0)
+    _lib.check(lib.ufr_depth_points_count(p_mask, H, W, ws.data_ptr(), nbytes, C.byref(n), _stream()), "ufr_depth_points_count")
+    N = int(n.value)
+    xyz = torch.empty((N, 3), dtype=torch.float32, device=mask.device)
+    rgb = torch.empty((N, 3), dtype=torch.uint8, device=mask.device)
+    dp = C.POINTER(C.c_double)
+    _lib.check(lib.ufr_depth_points_emit(p_mask, p_avg, p_col, H, W, ik.ctypes.data_as(dp), ie.ctypes.data_as(dp), ws.data_ptr(),
+                                         nbytes, xyz.data_ptr() if N else None, rgb.data_ptr() if N else None, N, _stream()),
+               "ufr_depth_points_emit")
+    return xyz, rgb
+
+
 CONV3D_S1, CONV3D_S2, CONV3D_T2 = 0, 1, 2
 
 
