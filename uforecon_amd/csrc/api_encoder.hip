@@ -1,0 +1,257 @@
+// extern "C" surface of libufr.so (include/ufr.h), part 5 of 6: the encoder -- correlation volumes and view weights, the
+// 3-D convolutions of the frustum U-Nets, the 2-D and deformable convolutions of the feature backbone, the FMT layer.
+#include "api_common.h"
+
+using namespace ufr;
+using namespace ufr::api;
+
+namespace {
+// [reference features, channel-last | source features, channel-last]
+struct CorrelateWs { float *ref_cl, *src_cl; };
+CorrelateWs carve_correlate(Carver& c, int C, int H, int W, int NS) {
+  CorrelateWs w;
+  w.ref_cl = c.f32((size_t)H * W * C);
+  w.src_cl = c.f32((size_t)NS * H * W * C);
+  return w;
+}
+
+// [input, channel-last]
+float* carve_deform_conv2d(Carver& c, int B, int C, int H, int W) { return c.f32((size_t)B * H * W * C); }
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------ correlation-volume construction
+size_t ufr_correlate_workspace_bytes(int32_t C, int32_t H, int32_t W, int32_t NS) {
+  return carved_bytes(carve_correlate, C, H, W, NS);
+}
+
+int ufr_frustum_correlate(const float* ref_fea, const float* src_fea, const float* rel_proj, const float* depth_values,
+                          const float* view_weights, int32_t C, int32_t H, int32_t W, int32_t D, int32_t NS,
+                          float* similarity, float* aggregated, void* workspace, size_t workspace_bytes,
+                          ufr_stream stream) {
+  UFR_REQUIRE(ref_fea && src_fea && rel_proj && depth_values && workspace, "ufr_frustum_correlate: null argument");
+  UFR_REQUIRE(similarity || aggregated, "ufr_frustum_correlate: no output requested");
+  UFR_REQUIRE(!aggregated || view_weights, "ufr_frustum_correlate: aggregated output needs view_weights");
+  UFR_REQUIRE(C == 4 || C == 8 || C == 16 || C == 32 || C == 64, "ufr_frustum_correlate: C=%d unsupported (4,8,16,32,64)", C);
+  UFR_REQUIRE(NS >= 1 && NS <= UFR_MAX_VIEWS, "ufr_frustum_correlate: NS=%d unsupported (1..%d)", NS, UFR_MAX_VIEWS);
+  UFR_REQUIRE(H >= 2 && W >= 2 && D >= 1, "ufr_frustum_correlate: H=%d W=%d D=%d", H, W, D);
+  Carver c(workspace);
+  const CorrelateWs w = carve_correlate(c, C, H, W, NS);
+  UFR_CHECK(check_workspace("ufr_frustum_correlate", workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ProfScope p("correlate", s);
+  UFR_HIP(launch_chw_to_hwc(ref_fea, w.ref_cl, 1, C, H * W, s));
+  UFR_HIP(launch_chw_to_hwc(src_fea, w.src_cl, NS, C, H * W, s));
+  UFR_HIP(launch_correlate(w.ref_cl, w.src_cl, rel_proj, NS, depth_values, view_weights, similarity, aggregated, C, H, W, D, s));
+  return UFR_OK;
+}
+
+int ufr_pixelwise_view_weights(const float* similarity, const float* params, float* view_weights, float* aggregated, int32_t NS,
+                               int32_t D, int32_t H, int32_t W, ufr_stream stream) {
+  UFR_REQUIRE(similarity && params && view_weights, "ufr_pixelwise_view_weights: null argument");
+  UFR_REQUIRE(NS >= 1 && NS <= UFR_MAX_VIEWS && D >= 1 && H >= 1 && W >= 1, "ufr_pixelwise_view_weights: NS=%d D=%d H=%d W=%d", NS, D, H, W);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("pixelwise_view_weights", s, launch_pixelwise_weights(similarity, params, view_weights, aggregated, NS, D, H, W, s));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ 3-D convolutions of the frustum U-Nets
+int ufr_conv3d(const float* in, const float* weight, const float* weight2, const float* bias, const float* bn_scale,
+               const float* bn_shift, const float* skip, float* out, float* out2, int32_t B, int32_t D, int32_t H,
+               int32_t W, int32_t cin, int32_t cout, int32_t cout2, int32_t mode, int32_t relu, int32_t out_ncdhw,
+               float* out_absmax, ufr_stream stream) {
+  UFR_REQUIRE(in && weight && out, "ufr_conv3d: null argument");
+  UFR_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "ufr_conv3d: B=%d D=%d H=%d W=%d", B, D, H, W);
+  UFR_CHECK(check_conv3d_mode("ufr_conv3d", mode));
+  UFR_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "ufr_conv3d: bn_scale and bn_shift go together");
+  UFR_REQUIRE(cout2 == 0 || (weight2 && out2 && out_ncdhw && mode == UFR_CONV3D_S1),
+              "ufr_conv3d: a second head needs weight2, out2, out_ncdhw and stride 1");
+  UFR_REQUIRE(out_ncdhw || (cout % 4 == 0 && cout2 == 0), "ufr_conv3d: channel-last outputs need cout %% 4 == 0 (got %d)", cout);
+  UFR_REQUIRE(!skip || !out_ncdhw, "ufr_conv3d: skip is a channel-last tensor; not with out_ncdhw");
+  UFR_REQUIRE((long long)B * D * H * W * (cin > cout ? cin : cout) < (1ll << 40), "ufr_conv3d: volume too large");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ProfScope p("conv3d", s);
+  UFR_REQUIRE(!out_absmax || (!out_ncdhw && cout <= 16), "ufr_conv3d: out_absmax goes with channel-last outputs of at most 16 channels");
+  const hipError_t e = launch_conv3d(in, weight, weight2, bias, bn_scale, bn_shift, skip, out, out2, B, D, H, W, cin, cout,
+                                     cout2, mode, relu, out_ncdhw, s, 0, out_absmax);
+  if (e == hipErrorInvalidValue)
+    return fail(UFR_ERR_ARG, "ufr_conv3d: (cin %d, cout %d+%d, mode %d) is not a layer of CostRegNet / CostRegNetWeight", cin,
+                cout, cout2, mode);
+  UFR_HIP(e);
+  return UFR_OK;
+}
+
+// the stride-1 8 / 16-channel layers on the 16-bit matrix cores (conv3d_planes.hip)
+size_t ufr_conv3d_planes_workspace_bytes(int32_t cin, int32_t cout, int32_t cout2, int32_t mode) {
+  return conv3d_planes_workspace_bytes(cin, cout, cout2, mode);
+}
+
+int ufr_conv3d_planes(const float* in, const float* in_absmax, const float* weight, const float* weight2, const float* bias,
+                      const float* bn_scale, const float* bn_shift, const float* skip, float* out, float* out2,
+                      float* out_absmax, int32_t B, int32_t D, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t cout2,
+                      int32_t mode, int32_t relu, int32_t out_ncdhw, int32_t flip, void* workspace, size_t workspace_bytes, int32_t planes_ready,
+                      ufr_stream stream) {
+  UFR_REQUIRE(in && in_absmax && weight && out && workspace, "ufr_conv3d_planes: null argument");
+  UFR_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "ufr_conv3d_planes: B=%d D=%d H=%d W=%d", B, D, H, W);
+  UFR_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), "ufr_conv3d_planes: bn_scale and bn_shift go together");
+  UFR_REQUIRE(cout2 == 0 || (weight2 && out2 && out_ncdhw && !flip), "ufr_conv3d_planes: a second head needs weight2, out2, out_ncdhw");
+  UFR_REQUIRE(out_ncdhw || (cout % 4 == 0 && cout2 == 0), "ufr_conv3d_planes: channel-last outputs need cout %% 4 == 0 (got %d)", cout);
+  UFR_REQUIRE(!(out_ncdhw && (skip || out_absmax)), "ufr_conv3d_planes: skip / out_absmax go with channel-last outputs");
+  UFR_CHECK(check_conv3d_mode("ufr_conv3d_planes", mode));
+  UFR_REQUIRE(!(mode != UFR_CONV3D_S1 && flip), "ufr_conv3d_planes: flip is the stride-1 data gradient");
+  UFR_REQUIRE(!(mode == UFR_CONV3D_T2 && out_ncdhw), "ufr_conv3d_planes: the transposed layers write channel-last");
+  const size_t need = conv3d_planes_workspace_bytes(cin, cout, cout2, mode);
+  if (!need) return fail(UFR_ERR_ARG, "ufr_conv3d_planes: (cin %d, cout %d+%d, mode %d) is not a layer of this kernel family", cin, cout, cout2, mode);
+  UFR_CHECK(check_workspace("ufr_conv3d_planes", workspace_bytes, need));
+  UFR_REQUIRE((long long)D * H * W * cin * 4 < (1ll << 31), "ufr_conv3d_planes: one batch element reaches 2 GiB");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED(flip ? "conv3d_dgrad" : "conv3d", s, launch_conv3d_planes(in, in_absmax, weight, weight2, bias, bn_scale, bn_shift, skip, out,
+      out2, out_absmax, B, D, H, W, cin, cout, cout2, mode, relu, out_ncdhw, flip, workspace, planes_ready != 0, s));
+  return UFR_OK;
+}
+
+int ufr_absmax(const float* x, size_t n, float* absmax, ufr_stream stream) {
+  UFR_REQUIRE(x && absmax, "ufr_absmax: null argument");
+  UFR_HIP(launch_absmax(x, n, absmax, static_cast<hipStream_t>(stream)));
+  return UFR_OK;
+}
+
+// backward of the plain layers (CostRegNetWeight: the producer the reference trains) -- conv3d.hip, second half
+int ufr_conv3d_bwd_data(const float* d_out, const float* weight, const float* accumulate, float* d_in, int32_t B, int32_t D,
+                        int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t mode, ufr_stream stream) {
+  UFR_REQUIRE(d_out && weight && d_in, "ufr_conv3d_bwd_data: null argument");
+  UFR_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "ufr_conv3d_bwd_data: B=%d D=%d H=%d W=%d", B, D, H, W);
+  UFR_CHECK(check_conv3d_mode("ufr_conv3d_bwd_data", mode));
+  UFR_REQUIRE(mode != UFR_CONV3D_S2 || (D % 2 == 0 && H % 2 == 0 && W % 2 == 0), "ufr_conv3d_bwd_data: stride 2 needs even extents");
+  UFR_REQUIRE(cin == 1 || cin % 4 == 0, "ufr_conv3d_bwd_data: cin=%d", cin);
+  UFR_REQUIRE(!(cin == 1 && accumulate), "ufr_conv3d_bwd_data: no fused addition into a 1-channel gradient");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ProfScope p("conv3d_dgrad", s);
+  const hipError_t e = launch_conv3d_bwd_data(d_out, weight, accumulate, d_in, B, D, H, W, cin, cout, mode, s);
+  if (e == hipErrorInvalidValue)
+    return fail(UFR_ERR_ARG, "ufr_conv3d_bwd_data: (cin %d, cout %d, mode %d) is not a layer of CostRegNetWeight", cin, cout, mode);
+  UFR_HIP(e);
+  return UFR_OK;
+}
+
+int ufr_conv3d_bwd_weight(const float* in, const float* d_out, float* d_weight, float* d_bias, int32_t B, int32_t D, int32_t H,
+                          int32_t W, int32_t cin, int32_t cout, int32_t mode, ufr_stream stream) {
+  UFR_REQUIRE(in && d_out && d_weight, "ufr_conv3d_bwd_weight: null argument");
+  UFR_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "ufr_conv3d_bwd_weight: B=%d D=%d H=%d W=%d", B, D, H, W);
+  UFR_CHECK(check_conv3d_mode("ufr_conv3d_bwd_weight", mode));
+  UFR_REQUIRE(mode != UFR_CONV3D_S2 || (D % 2 == 0 && H % 2 == 0 && W % 2 == 0), "ufr_conv3d_bwd_weight: stride 2 needs even extents");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ProfScope p("conv3d_wgrad", s);
+  const hipError_t e = launch_conv3d_bwd_weight(in, d_out, d_weight, d_bias, B, D, H, W, cin, cout, mode, s);
+  if (e == hipErrorInvalidValue)
+    return fail(UFR_ERR_ARG, "ufr_conv3d_bwd_weight: (cin %d, cout %d, mode %d) is not a layer of CostRegNetWeight", cin, cout, mode);
+  UFR_HIP(e);
+  return UFR_OK;
+}
+
+int ufr_conv3d_bwd_weight_heads(const float* in, const float* d_out, const float* d_out2, float* d_weight, float* d_weight2, int32_t B,
+                                int32_t D, int32_t H, int32_t W, ufr_stream stream) {
+  UFR_REQUIRE(in && d_out && d_out2 && d_weight && d_weight2, "ufr_conv3d_bwd_weight_heads: null argument");
+  UFR_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "ufr_conv3d_bwd_weight_heads: B=%d D=%d H=%d W=%d", B, D, H, W);
+  UFR_REQUIRE((long long)D * H * W * 32 < (1ll << 31), "ufr_conv3d_bwd_weight_heads: one batch element reaches 2 GiB");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("conv3d_wgrad", s, launch_conv3d_wgrad_heads(in, d_out, d_out2, d_weight, d_weight2, B, D, H, W, s));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ deformable convolution
+size_t ufr_deform_conv2d_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+  return carved_bytes(carve_deform_conv2d, B, C, H, W);
+}
+
+int ufr_deform_conv2d(const float* input, const float* offset, const float* mask, const float* weight,
+                      const float* bias, float* output, int32_t B, int32_t C, int32_t Cout, int32_t H, int32_t W,
+                      void* workspace, size_t workspace_bytes, ufr_stream stream) {
+  UFR_REQUIRE(input && offset && weight && output && workspace, "ufr_deform_conv2d: null argument");
+  UFR_REQUIRE(C > 0 && C % 4 == 0 && C <= 32, "ufr_deform_conv2d: C=%d unsupported (multiple of 4, <= 32)", C);
+  UFR_REQUIRE(Cout == 8 || Cout == 16 || Cout == 32, "ufr_deform_conv2d: Cout=%d unsupported (8, 16, 32)", Cout);
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0, "ufr_deform_conv2d: B=%d H=%d W=%d", B, H, W);
+  Carver c(workspace);
+  float* in_cl = carve_deform_conv2d(c, B, C, H, W);
+  UFR_CHECK(check_workspace("ufr_deform_conv2d", workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ProfScope p("deform_conv2d", s);
+  UFR_HIP(launch_chw_to_hwc(input, in_cl, B, C, H * W, s));
+  UFR_HIP(launch_deform_conv3x3(in_cl, offset, mask, weight, bias, output, B, C, Cout, H, W, s));
+  return UFR_OK;
+}
+
+int ufr_deform_conv2d_cl(const float* input_cl, const float* offset_mask, const float* weight, const float* bias,
+                         const float* scale, const float* shift, float* output, int32_t B, int32_t C, int32_t Cout, int32_t H,
+                         int32_t W, int32_t flags, ufr_stream stream) {
+  const float* offset = offset_mask;
+  UFR_REQUIRE(input_cl && offset && weight && output, "ufr_deform_conv2d_cl: null argument");
+  const float* mask = offset_mask + (size_t)18 * H * W;
+  UFR_REQUIRE(C == 32, "ufr_deform_conv2d_cl: C=%d (the channel-last form exists for the 32-channel layers of FeatureNet)", C);
+  UFR_REQUIRE(Cout == 8 || Cout == 16 || Cout == 32, "ufr_deform_conv2d_cl: Cout=%d unsupported (8, 16, 32)", Cout);
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0, "ufr_deform_conv2d_cl: B=%d H=%d W=%d", B, H, W);
+  UFR_REQUIRE((scale == nullptr) == (shift == nullptr), "ufr_deform_conv2d_cl: scale and shift come together");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("deform_conv2d", s, launch_deform_conv3x3(input_cl, offset, mask, weight, bias, output, B, C, Cout, H, W, s,
+      DcnEpilogue{scale, shift, (flags & UFR_CONV2D_RELU) != 0, (flags & UFR_CONV2D_OUT_PLANAR) == 0, 27}));
+  return UFR_OK;
+}
+
+// channel-last pipeline of the feature backbone (conv2d.hip; featurenet.py is the plan)
+int ufr_conv2d(const float* input, const float* weight, const float* scale, const float* shift, const float* skip, float* output,
+               int32_t B, int32_t cin, int32_t cout, int32_t H, int32_t W, int32_t ksize, int32_t stride, int32_t flags,
+               int32_t sigmoid_from, ufr_stream stream) {
+  UFR_REQUIRE(input && weight && output, "ufr_conv2d: null argument");
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && cout > 0 && cout <= 32, "ufr_conv2d: B=%d H=%d W=%d cout=%d", B, H, W, cout);
+  UFR_REQUIRE((ksize == 1 || ksize == 3 || ksize == 5) && (stride == 1 || stride == 2), "ufr_conv2d: ksize=%d stride=%d", ksize, stride);
+  UFR_REQUIRE((unsigned long long)H * W * (cin > 3 ? cin : 4) * 4ull < (1ull << 31), "ufr_conv2d: %d x %d x %d exceeds 2^31 bytes per image", H, W, cin);
+  Conv2dArgs a;
+  a.in = input; a.w = weight; a.scale = scale; a.shift = shift; a.skip = skip; a.out = output;
+  a.B = B; a.H = H; a.W = W; a.cout = cout;
+  a.Ho = (H + 2 * (ksize / 2) - ksize) / stride + 1;
+  a.Wo = (W + 2 * (ksize / 2) - ksize) / stride + 1;
+  a.relu = (flags & UFR_CONV2D_RELU) != 0;
+  a.out_planar = (flags & UFR_CONV2D_OUT_PLANAR) != 0;
+  a.sigmoid_from = sigmoid_from;
+  UFR_REQUIRE(!skip || (a.Ho % 2 == 0 && a.Wo % 2 == 0 && cout % 4 == 0), "ufr_conv2d: the upsampled skip needs even output extents and cout %% 4 == 0");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ProfScope p("conv2d", s);
+  const hipError_t e = launch_conv2d(a, cin, ksize, stride, (flags & UFR_CONV2D_IN_PLANAR) != 0, s);
+  if (e == hipErrorInvalidValue)
+    return fail(UFR_ERR_ARG, "ufr_conv2d: %d -> %d channels, %dx%d, stride %d is not a layer shape of FeatureNet (conv2d.hip)", cin, cout, ksize, ksize, stride);
+  UFR_HIP(e);
+  return UFR_OK;
+}
+
+int ufr_upsample_add(const float* reduced_cl, const float* fine, float* output_cl, int32_t B, int32_t C, int32_t h, int32_t w,
+                     ufr_stream stream) {
+  UFR_REQUIRE(reduced_cl && fine && output_cl, "ufr_upsample_add: null argument");
+  UFR_REQUIRE((C == 8 || C == 16) && B > 0 && h > 0 && w > 0, "ufr_upsample_add: B=%d C=%d h=%d w=%d (C in {8, 16})", B, C, h, w);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("upsample_add", s, launch_upsample_add(reduced_cl, fine, output_cl, B, C, h, w, s));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ feature-matching transformer layer
+size_t ufr_fmt_layer_workspace_bytes(int32_t N, int32_t S) {
+  return align_up((size_t)(N > 0 ? N : 1) * 160 * sizeof(float) * (1 + (size_t)fmt_state_parts(S > 0 ? S : 1)));
+}
+
+int ufr_fmt_layer(const ufr_fmt_layer_weights* w, const float* x, const float* src, int32_t N, int32_t T, int32_t S,
+                  float* out, void* workspace, ufr_stream stream) {
+  static_assert(sizeof(ufr_fmt_layer_weights) == sizeof(FmtWeights), "ufr_fmt_layer_weights layout");
+  UFR_REQUIRE(w && x && out && workspace, "ufr_fmt_layer: null argument");
+  FmtWeights fw;
+  memcpy(&fw, w, sizeof(fw));
+  const float* const* pw = reinterpret_cast<const float* const*>(&fw);
+  for (int i = 0; i < 16; ++i) UFR_REQUIRE(pw[i], "ufr_fmt_layer: weight pointer %d is null", i);
+  if (!src) { src = x; S = T; }
+  UFR_REQUIRE(N > 0 && T > 0 && S > 0, "ufr_fmt_layer: N=%d T=%d S=%d", N, T, S);
+  UFR_REQUIRE(out != x && out != src, "ufr_fmt_layer: out must not alias an input");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("fmt_layer", s, launch_fmt_layer(fw, x, src, N, T, S, out, static_cast<float*>(workspace), s));
+  return UFR_OK;
+}
+
+}  // extern "C"

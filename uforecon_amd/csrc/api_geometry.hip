@@ -1,0 +1,324 @@
+// extern "C" surface of libufr.so (include/ufr.h), part 6 of 6: geometry after the network -- TSDF fusion, marching cubes,
+// the DTU chamfer evaluation and depth-map fusion.  The count / emit pairs synchronise the stream to hand a count to the host.
+#include "api_common.h"
+#include "mcubes_table.h"
+
+using namespace ufr;
+using namespace ufr::api;
+
+namespace {
+
+// ---- marching cubes: [tile sums int32 x2 | tile offsets int64 x2 | totals int64 x2 | index volume int32 per voxel]
+struct McWs { int *tile_counts, *index; long long *tile_off, *totals; };
+McWs carve_mcubes(Carver& c, const int32_t* dim) {
+  const size_t tiles = (size_t)mcubes_tiles(dim), n = (size_t)dim[0] * dim[1] * dim[2];
+  McWs w;
+  w.tile_counts = c.take<int>(tiles * 2);
+  w.tile_off = c.take<long long>(tiles * 2);
+  w.totals = c.take<long long>(2);
+  w.index = c.take<int>(n);
+  return w;
+}
+
+int mc_check(const char* who, const float* vol, const int32_t* dim, void* ws, size_t ws_bytes, McWs* w) {
+  UFR_REQUIRE(vol && dim && ws, "%s: null argument", who);
+  UFR_REQUIRE(dim[0] >= 2 && dim[1] >= 2 && dim[2] >= 2, "%s: volume %dx%dx%d (every dim must be >= 2)", who, dim[0], dim[1], dim[2]);
+  UFR_REQUIRE((long long)dim[0] * dim[1] * dim[2] < (1ll << 31), "%s: volume %dx%dx%d has 2^31 voxels or more", who, dim[0], dim[1],
+              dim[2]);
+  Carver c(ws);
+  *w = carve_mcubes(c, dim);
+  return check_workspace(who, ws_bytes, c.off);
+}
+
+// ---- DTU chamfer evaluation
+constexpr long long kChMax = (1ll << 31) - 1;
+
+int cell_grid_check(const char* who, double cell, const double* origin) {
+  UFR_REQUIRE(cell > 0.0 && std::isfinite(cell) && std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]),
+              "%s: cell %g, origin (%g, %g, %g) (cell must be positive, all finite)", who, cell, origin[0], origin[1], origin[2]);
+  return UFR_OK;
+}
+
+// mesh sampling: [per-triangle offset in its block int64 | block sums int64 | block offsets int64 | total int64]
+struct SampleWs { long long *tri_off, *block_tot, *block_off, *total; };
+SampleWs carve_mesh_sample(Carver& c, long long F) {
+  const size_t blocks = (size_t)chamfer_blocks(F);
+  SampleWs w;
+  w.tri_off = c.take<long long>((size_t)F);
+  w.block_tot = c.take<long long>(blocks);
+  w.block_off = c.take<long long>(blocks);
+  w.total = c.take<long long>(1);
+  return w;
+}
+
+int sample_check(const char* who, const double* verts, const int32_t* faces, int64_t V, int64_t F, double density, void* ws,
+                 size_t ws_bytes, SampleWs* w) {
+  UFR_REQUIRE(verts && faces && ws, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax, "%s: V %lld, F %lld (each must be 1 .. 2^31 - 1)", who, (long long)V,
+              (long long)F);
+  UFR_REQUIRE(density > 0.0 && std::isfinite(density), "%s: density %g (must be positive and finite)", who, density);
+  Carver c(ws);
+  *w = carve_mesh_sample(c, F);
+  return check_workspace(who, ws_bytes, c.off);
+}
+
+// thinning: [undecided count int32]
+int* carve_points_thin(Carver& c) { return c.take<int>(1); }
+
+// nearest neighbours: [block sums fp64 | block counts int64]
+struct NnWs { double* block_sum; long long* block_cnt; };
+NnWs carve_nn_dist(Carver& c, long long nq) {
+  const size_t blocks = (size_t)chamfer_blocks(nq);
+  NnWs w;
+  w.block_sum = c.take<double>(blocks);
+  w.block_cnt = c.take<long long>(blocks);
+  return w;
+}
+
+// ---- depth-map fusion: [block sums int64 | block offsets int64 | total int64]
+struct DepthPointsWs { long long *block_tot, *block_off, *total; };
+DepthPointsWs carve_depth_points(Carver& c, long long n) {
+  const size_t blocks = (size_t)depth_points_blocks(n);
+  DepthPointsWs w;
+  w.block_tot = c.take<long long>(blocks);
+  w.block_off = c.take<long long>(blocks);
+  w.total = c.take<long long>(1);
+  return w;
+}
+
+int depth_image_check(const char* who, int32_t H, int32_t W) {
+  UFR_REQUIRE(H >= 1 && W >= 1, "%s: image %dx%d (H and W must be >= 1)", who, H, W);
+  UFR_REQUIRE((long long)H * W < (1ll << 31), "%s: image %dx%d has 2^31 pixels or more", who, H, W);
+  return UFR_OK;
+}
+
+int depth_points_check(const char* who, const uint8_t* mask, int32_t H, int32_t W, void* ws, size_t ws_bytes, DepthPointsWs* w) {
+  UFR_REQUIRE(mask && ws, "%s: null argument", who);
+  UFR_CHECK(depth_image_check(who, H, W));
+  Carver c(ws);
+  *w = carve_depth_points(c, (long long)H * W);
+  return check_workspace(who, ws_bytes, c.off);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------ TSDF fusion
+int ufr_tsdf_integrate(float* tsdf, float* weight, float* color, const int32_t* dim, const float* origin,
+                       float voxel_size, float trunc_margin, const float* cam_intr, const float* cam_pose,
+                       const float* depth_im, const float* color_im, int32_t im_h, int32_t im_w, float obs_weight,
+                       int32_t integrate_color, ufr_stream stream) {
+  UFR_REQUIRE(tsdf && weight && dim && origin && cam_intr && cam_pose && depth_im, "ufr_tsdf_integrate: null argument");
+  UFR_REQUIRE(dim[0] > 0 && dim[1] > 0 && dim[2] > 0, "ufr_tsdf_integrate: volume %dx%dx%d", dim[0], dim[1], dim[2]);
+  UFR_REQUIRE(im_h > 0 && im_w > 0, "ufr_tsdf_integrate: image %dx%d", im_h, im_w);
+  UFR_REQUIRE(voxel_size > 0.f && trunc_margin > 0.f, "ufr_tsdf_integrate: voxel_size %g, trunc_margin %g", voxel_size, trunc_margin);
+  UFR_REQUIRE(!integrate_color || (color && color_im), "ufr_tsdf_integrate: colour integration needs color and color_im");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("tsdf_integrate", s, launch_tsdf_integrate(tsdf, weight, color, dim, origin, voxel_size, trunc_margin, cam_intr, cam_pose,
+      depth_im, color_im, im_h, im_w, obs_weight, integrate_color, s));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ marching cubes
+size_t ufr_marching_cubes_workspace_bytes(const int32_t* dim) {
+  if (!dim || dim[0] < 2 || dim[1] < 2 || dim[2] < 2 || (long long)dim[0] * dim[1] * dim[2] >= (1ll << 31)) return 0;
+  return carved_bytes(carve_mcubes, dim);
+}
+
+int ufr_marching_cubes_count(const float* vol, const int32_t* dim, float level, void* workspace, size_t workspace_bytes,
+                             int32_t* counts_host, ufr_stream stream) {
+  McWs w;
+  UFR_CHECK(mc_check("ufr_marching_cubes_count", vol, dim, workspace, workspace_bytes, &w));
+  UFR_REQUIRE(counts_host, "ufr_marching_cubes_count: null argument (counts_host)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mcubes_count", s, launch_mcubes_count(vol, dim, level, w.tile_counts, s));
+  UFR_TIMED("mcubes_scan", s, launch_mcubes_scan(w.tile_counts, mcubes_tiles(dim), w.tile_off, w.totals, s));
+  long long tot[2] = {0, 0};
+  UFR_HIP(hipMemcpyAsync(tot, w.totals, sizeof(tot), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  UFR_REQUIRE(tot[0] < (1ll << 31) && tot[1] < (1ll << 31), "ufr_marching_cubes_count: %lld vertices, %lld faces: 2^31 or more",
+              tot[0], tot[1]);
+  counts_host[0] = (int32_t)tot[0];
+  counts_host[1] = (int32_t)tot[1];
+  return UFR_OK;
+}
+
+int ufr_marching_cubes_emit(const float* vol, const int32_t* dim, float level, void* workspace, size_t workspace_bytes,
+                            float* verts, float* normals, int32_t* faces, int32_t n_verts, int32_t n_faces, ufr_stream stream) {
+  McWs w;
+  UFR_CHECK(mc_check("ufr_marching_cubes_emit", vol, dim, workspace, workspace_bytes, &w));
+  UFR_REQUIRE(n_verts >= 0 && n_faces >= 0, "ufr_marching_cubes_emit: n_verts %d, n_faces %d", n_verts, n_faces);
+  UFR_REQUIRE((n_verts == 0 || (verts && normals)) && (n_faces == 0 || faces), "ufr_marching_cubes_emit: null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_verts == 0 && n_faces == 0) return UFR_OK;
+  // the vertices, and the index volume the faces need
+  UFR_TIMED("mcubes_verts", s, launch_mcubes_verts(vol, dim, level, w.tile_off, w.index, verts, normals, n_verts, s));
+  if (n_faces > 0) UFR_TIMED("mcubes_faces", s, launch_mcubes_faces(vol, dim, level, w.tile_off, w.index, faces, n_faces, s));
+  return UFR_OK;
+}
+
+int ufr_marching_cubes_table(int8_t* out, int32_t out_len) {
+  static_assert(sizeof(kMcTable[0]) == UFR_MC_TABLE_ROW, "mcubes_table.h and ufr.h disagree on the row length");
+  UFR_REQUIRE(out, "ufr_marching_cubes_table: null argument");
+  UFR_REQUIRE(out_len >= 256 * UFR_MC_TABLE_ROW, "ufr_marching_cubes_table: out_len %d < %d", out_len, 256 * UFR_MC_TABLE_ROW);
+  memcpy(out, kMcTable, sizeof(kMcTable));
+  return UFR_MC_TABLE_ROW;
+}
+
+// ------------------------------------------------------------------ DTU chamfer evaluation
+size_t ufr_mesh_sample_workspace_bytes(int64_t F) {
+  return (F >= 1 && F <= kChMax) ? carved_bytes(carve_mesh_sample, F) : 0;
+}
+
+int ufr_mesh_sample_count(const double* verts, const int32_t* faces, int64_t V, int64_t F, double density, void* workspace,
+                          size_t workspace_bytes, int64_t* total_host, ufr_stream stream) {
+  SampleWs w;
+  UFR_CHECK(sample_check("ufr_mesh_sample_count", verts, faces, V, F, density, workspace, workspace_bytes, &w));
+  UFR_REQUIRE(total_host, "ufr_mesh_sample_count: null argument (total_host)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_sample_count", s, launch_mesh_sample_count(verts, faces, V, F, density, w.tri_off, w.block_tot, s));
+  UFR_TIMED("mesh_sample_scan", s, launch_mesh_sample_scan(w.block_tot, chamfer_blocks(F), w.block_off, w.total, s));
+  long long tot = 0;
+  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  *total_host = (int64_t)tot;
+  return UFR_OK;
+}
+
+int ufr_mesh_sample_emit(const double* verts, const int32_t* faces, int64_t V, int64_t F, double density, void* workspace,
+                         size_t workspace_bytes, double* out, int64_t capacity, ufr_stream stream) {
+  SampleWs w;
+  UFR_CHECK(sample_check("ufr_mesh_sample_emit", verts, faces, V, F, density, workspace, workspace_bytes, &w));
+  UFR_REQUIRE(capacity >= 0, "ufr_mesh_sample_emit: capacity %lld", (long long)capacity);
+  UFR_REQUIRE(capacity == 0 || out, "ufr_mesh_sample_emit: null argument (out)");
+  if (capacity == 0) return UFR_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_sample_emit", s, launch_mesh_sample_emit(verts, faces, V, F, density, w.tri_off, w.block_off, out, capacity, s));
+  return UFR_OK;
+}
+
+int ufr_points_cell_keys(const double* points, int64_t n, const double* origin, double cell, int64_t* keys, ufr_stream stream) {
+  UFR_REQUIRE(points && origin && keys, "ufr_points_cell_keys: null argument");
+  UFR_REQUIRE(n >= 1 && n <= kChMax, "ufr_points_cell_keys: n %lld (must be 1 .. 2^31 - 1)", (long long)n);
+  UFR_CHECK(cell_grid_check("ufr_points_cell_keys", cell, origin));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("points_cell_keys", s, launch_points_cell_keys(points, n, origin, cell, reinterpret_cast<long long*>(keys), s));
+  return UFR_OK;
+}
+
+size_t ufr_points_thin_workspace_bytes(int64_t n) {
+  return (n >= 1 && n <= kChMax) ? carved_bytes(carve_points_thin) : 0;
+}
+
+int ufr_points_thin(const double* points, const int64_t* keys, const int32_t* rank, int64_t n, double radius, uint8_t* state,
+                    void* workspace, size_t workspace_bytes, int32_t* rounds_host, ufr_stream stream) {
+  UFR_REQUIRE(points && keys && rank && state && workspace, "ufr_points_thin: null argument");
+  UFR_REQUIRE(n >= 1 && n <= kChMax, "ufr_points_thin: n %lld (must be 1 .. 2^31 - 1)", (long long)n);
+  UFR_REQUIRE(radius >= 0.0 && std::isfinite(radius), "ufr_points_thin: radius %g (must be finite and >= 0)", radius);
+  Carver c(workspace);
+  int* undecided = carve_points_thin(c);
+  UFR_CHECK(check_workspace("ufr_points_thin", workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_HIP(hipMemsetAsync(state, 0, (size_t)n, s));
+  long long prev = n;
+  int rounds = 0;
+  while (prev > 0) {       // every round decides at least the earliest undecided point: at most n rounds
+    if (rounds >= n) return fail(UFR_ERR_HIP, "ufr_points_thin: no fixpoint after %d rounds", rounds);
+    int und = 0;
+    UFR_HIP(hipMemsetAsync(undecided, 0, sizeof(int), s));
+    UFR_TIMED("points_thin_round", s, launch_thin_round(points, reinterpret_cast<const long long*>(keys), rank, n, radius, state,
+        undecided, s));
+    UFR_HIP(hipMemcpyAsync(&und, undecided, sizeof(int), hipMemcpyDeviceToHost, s));
+    UFR_HIP(hipStreamSynchronize(s));
+    ++rounds;
+    if (und < 0 || und >= prev)
+      return fail(UFR_ERR_HIP, "ufr_points_thin: round %d left %d of %lld points undecided (rank is not a permutation?)", rounds, und,
+                  prev);
+    prev = und;
+  }
+  if (rounds_host) *rounds_host = rounds;
+  return UFR_OK;
+}
+
+size_t ufr_points_nn_dist_workspace_bytes(int64_t nq) {
+  return (nq >= 1 && nq <= kChMax) ? carved_bytes(carve_nn_dist, nq) : 0;
+}
+
+int ufr_points_nn_dist(const double* query, int64_t nq, const double* ref, const int64_t* ref_keys, int64_t nr,
+                       const double* origin, double cell, double max_dist, double* dist, double* mean_out, void* workspace,
+                       size_t workspace_bytes, ufr_stream stream) {
+  UFR_REQUIRE(query && ref && ref_keys && origin && dist && workspace, "ufr_points_nn_dist: null argument");
+  UFR_REQUIRE(nq >= 1 && nq <= kChMax && nr >= 1 && nr <= kChMax, "ufr_points_nn_dist: nq %lld, nr %lld (each must be 1 .. 2^31 - 1)",
+              (long long)nq, (long long)nr);
+  UFR_CHECK(cell_grid_check("ufr_points_nn_dist", cell, origin));
+  UFR_REQUIRE(max_dist > 0.0 && max_dist < 1e150, "ufr_points_nn_dist: max_dist %g (must be positive, below 1e150)", max_dist);
+  Carver c(workspace);
+  const NnWs w = carve_nn_dist(c, nq);
+  UFR_CHECK(check_workspace("ufr_points_nn_dist", workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("points_nn_dist", s, launch_nn_dist(query, nq, ref, reinterpret_cast<const long long*>(ref_keys), nr, origin, cell, max_dist,
+      dist, w.block_sum, w.block_cnt, mean_out, s));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ depth-map fusion
+int ufr_depth_consistency(const float* ref_depth, int32_t H, int32_t W, const float* const* src_depth, const int32_t* src_hw,
+                          const double* mats, int32_t S, double geo_pixel_thres, double geo_depth_thres, int32_t geo_mask_thres,
+                          int32_t* mask_sum, uint8_t* mask, double* depth_avg, uint8_t* pair_masks, ufr_stream stream) {
+  const char* who = "ufr_depth_consistency";
+  UFR_REQUIRE(ref_depth && src_depth && src_hw && mats && mask_sum && mask && depth_avg, "%s: null argument", who);
+  UFR_CHECK(depth_image_check(who, H, W));
+  UFR_REQUIRE(S >= 1 && S <= UFR_DEPTH_MAX_SOURCES, "%s: S %d (must be 1 .. %d)", who, S, UFR_DEPTH_MAX_SOURCES);
+  for (int k = 0; k < S; ++k) {
+    UFR_REQUIRE(src_depth[k], "%s: null argument (source %d)", who, k);
+    UFR_REQUIRE(src_hw[2 * k] >= 1 && src_hw[2 * k + 1] >= 1 && (long long)src_hw[2 * k] * src_hw[2 * k + 1] < (1ll << 31),
+                "%s: source %d is %dx%d (H and W must be >= 1, fewer than 2^31 pixels)", who, k, src_hw[2 * k], src_hw[2 * k + 1]);
+  }
+  UFR_REQUIRE(!std::isnan(geo_pixel_thres) && !std::isnan(geo_depth_thres), "%s: a threshold is NaN", who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("depth_consistency", s, launch_depth_consistency(ref_depth, H, W, src_depth, src_hw, mats, S, geo_pixel_thres,
+      (float)geo_depth_thres, geo_mask_thres, mask_sum, mask, depth_avg, pair_masks, s));
+  return UFR_OK;
+}
+
+size_t ufr_depth_points_workspace_bytes(int32_t H, int32_t W) {
+  if (H < 1 || W < 1 || (long long)H * W >= (1ll << 31)) return 0;
+  return carved_bytes(carve_depth_points, (long long)H * W);
+}
+
+int ufr_depth_points_count(const uint8_t* mask, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, int64_t* n_host,
+                           ufr_stream stream) {
+  DepthPointsWs w;
+  UFR_CHECK(depth_points_check("ufr_depth_points_count", mask, H, W, workspace, workspace_bytes, &w));
+  UFR_REQUIRE(n_host, "ufr_depth_points_count: null argument (n_host)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("depth_points_count", s, launch_depth_points_count(mask, (long long)H * W, w.block_tot, w.block_off, w.total, s));
+  long long tot = 0;
+  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  *n_host = (int64_t)tot;
+  return UFR_OK;
+}
+
+int ufr_depth_points_emit(const uint8_t* mask, const double* depth_avg, const uint8_t* color, int32_t H, int32_t W,
+                          const double* inv_k, const double* inv_e, void* workspace, size_t workspace_bytes, float* xyz,
+                          uint8_t* rgb, int64_t capacity, ufr_stream stream) {
+  const char* who = "ufr_depth_points_emit";
+  DepthPointsWs w;
+  UFR_CHECK(depth_points_check(who, mask, H, W, workspace, workspace_bytes, &w));
+  UFR_REQUIRE(depth_avg && color && inv_k && inv_e, "%s: null argument", who);
+  UFR_REQUIRE(capacity >= 0, "%s: capacity %lld", who, (long long)capacity);
+  UFR_REQUIRE(capacity == 0 || (xyz && rgb), "%s: null argument (xyz / rgb with capacity %lld)", who, (long long)capacity);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  long long tot = 0;
+  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  UFR_REQUIRE(tot >= 0 && tot <= (long long)H * W, "%s: the workspace holds no count (call ufr_depth_points_count first)", who);
+  UFR_REQUIRE(capacity >= tot, "%s: capacity %lld is smaller than the %lld points counted", who, (long long)capacity, tot);
+  if (tot == 0) return UFR_OK;
+  UFR_TIMED("depth_points_emit", s, launch_depth_points_emit(mask, depth_avg, color, H, W, inv_k, inv_e, w.block_off, xyz, rgb, tot, s));
+  return UFR_OK;
+}
+
+}  // extern "C"

@@ -11,7 +11,7 @@
 //          vertex id into the index volume (workspace, written only where the voxel owns a vertex);
 //   faces  recount cases, block scan + tile offset -> face ids in (cube, table order) order; vertex id of a triangle
 //          edge = index[owner] + popcount(owner's crossing bits below the edge's axis).
-// Every output store is guarded by the caller's capacity.  Volumes hold fewer than 2^31 voxels (ufr_api.hip checks it).
+// Every output store is guarded by the caller's capacity.  Volumes hold fewer than 2^31 voxels (api_geometry.hip checks it).
 #include "mcubes_table.h"
 #include "ufr_internal.h"
 

@@ -1,4 +1,4 @@
-// Packed-weight blob layout shared by the host plan builder (ufr_api.hip) and the MFMA kernels.
+// Packed-weight blob layout shared by the host plan builder (api_weights_frame.hip) and the MFMA kernels.
 //
 // A dense layer  y = W x  (W row-major [out][in], the nn.Linear layout) is executed as chained
 // v_mfma_f32_16x16x4_f32 with the TOKENS as the 16 MFMA columns.  The accumulator tile of one

@@ -80,7 +80,7 @@ class EvalLoop:
         self.dev = next(net.parameters()).device
         self.main = torch.cuda.current_stream(self.dev)
         # the producers' stream at the LOWEST priority the device offers (torch: larger number = lower priority): frame
-        # k+1's encode kernels are dispatched into what frame k's ray kernels (highest priority: csrc/ufr_api.hip
+        # k+1's encode kernels are dispatched into what frame k's ray kernels (highest priority: csrc/api_ray.hip
         # side_pool_get) leave free, instead of taking turns with them
         self.enc_stream = torch.cuda.Stream(self.dev, priority=_lowest_priority()) if overlap else self.main
         # the frustum broadcast of frame k+1 on its OWN process group (= its own communicator and stream under RCCL): on the
