@@ -4,8 +4,10 @@
 //   UFORecon.query_depth_from_volume  code1/model.py:350-390            (3 correlation frustums, AC=True/zeros, 3-D)
 //   RayTransformer.forward            code1/ray_transformer.py:185-281  (dir, 2-D gathers AC=False/zeros, depth PE,
 //                                                                        pre_sim_mlp, token assembly)
-// A block is 64 consecutive points (samples of one ray) x NV views.  Phase A, thread (v, p) = view v of
-// point p: projection, bilinear footprints, the narrow gathers (colour, depth, frustums).  Phase B, the
+// A block is 64 points x NV views: 8 neighbouring rays x 8 consecutive samples where the sample count is a multiple
+// of 8 (neighbouring rays' samples of equal index share voxels, texels and so cache lines; along ONE ray every lane sits
+// in another z-plane of a frustum), 64 consecutive points otherwise (launch_gather).  Phase A, thread (v, p) = view v of
+// local point p: projection, bilinear footprints, the narrow gathers (colour, depth, frustums).  Phase B, the
 // 32-channel gathers, is cooperative: 8 adjacent lanes share one footprint and each takes 4 channels, so
 // one load instruction touches 8 cache lines instead of 64 -- the L1 (TCP) processes about one line per
 // clock and was the kernel's limiter (r2 PMC: TCP busy ~100 %, 3.1e8 line accesses per 524 288 points).
@@ -140,10 +142,13 @@ __device__ __forceinline__ void presim_block(const PreSim& ps, const float* sim,
 // Registers: the second launch bound keeps every instantiation within 96 VGPRs (5 waves per SIMD).  Without it the
 // compiler gave pre_sim_mlp's accumulators 64 AGPRs of their own at NV <= 4: 156-160 registers, 3 waves per SIMD
 // (tests/test_gather_registers.py).
-// NVT: the view count as a compile-time constant (round 5): the item / NV, item / npair divisions and the pair-index walk
-// of the cooperative loops sit in the address chains of the gathers; as run-time values they were 143 32-bit multiplies
-// and two ~20-instruction divisions per item.
+// NVT: the view count as a compile-time constant (round 5): the pair-index walk of the cooperative loops (and, while the
+// items ran point-major, the item / NV and item / npair divisions) sits in the address chains of the gathers; as run-time
+// values they were 143 32-bit multiplies and two ~20-instruction divisions per item.
 constexpr int kGatherMinW = 5;   // waves per SIMD the register budget is sized for
+// the ray-block map's block shape: kBlkRays neighbouring rays x kBlkSamples consecutive samples = 64 points (4 x 16 and
+// 16 x 4 were modelled and measured too: DESIGN.md section 7)
+constexpr int kBlkRays = 8, kBlkSamples = 64 / kBlkRays;
 
 #ifdef UFR_PHASE_TIMING  // development build: cycle counts per phase of every block's wave 0 (tools/bench_kernels.py prints them)
 __device__ unsigned long long g_gather_phase[32];
@@ -160,7 +165,7 @@ __device__ unsigned long long g_gather_phase[32];
 template <int NVT>
 __global__ void __launch_bounds__(64 * NVT, kGatherMinW) gather_kernel(FrameDev f, PreSim ps, const float* __restrict__ ray_o,
                                                       int o_stride, const float* __restrict__ ray_d,
-                                                      const float* __restrict__ zval, int P, int SN,
+                                                      const float* __restrict__ zval, int P, int SN, int SG,
                                                       float* __restrict__ x_tokens, float* __restrict__ x_point,
                                                       float* __restrict__ rgb_out,
                                                       float* __restrict__ dir_out, float* __restrict__ sim8_out,
@@ -191,7 +196,17 @@ __global__ void __launch_bounds__(64 * NVT, kGatherMinW) gather_kernel(FrameDev 
   // instead of eight
   const int nb8 = (int)(gridDim.x / 8) * 8;
   const int blk = (int)blockIdx.x < nb8 ? (int)(blockIdx.x % 8) * (nb8 / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-  const int pidx = blk * 64 + p;
+  // block -> point map.  SG = 0: 64 consecutive points.  SG = SN / kBlkSamples > 0: kBlkRays neighbouring rays x kBlkSamples
+  // consecutive samples, blocks ray-group-major, local point lp = ray (lp % kBlkRays), sample (lp / kBlkRays): lanes that
+  // differ in the ray alone are adjacent and hit the same or the next texel / voxel record, i.e. mostly the same cache line
+  // (DESIGN.md 3.2).  A ray past the last one has pidx >= P in either map.
+  int pbase = blk * 64;
+  if (SG) {
+    const int rg = blk / SG;
+    pbase = (kBlkRays * rg) * SN + kBlkSamples * (blk - rg * SG);
+  }
+  const auto point_of = [=](int lp) { return SG ? pbase + (int)((unsigned)lp % kBlkRays) * SN + (int)((unsigned)lp / kBlkRays) : pbase + lp; };
+  const int pidx = point_of(p);
   const bool active = pidx < P;
   const int pc = active ? pidx : P - 1;
   const int ray = pc / SN;
@@ -272,9 +287,10 @@ __global__ void __launch_bounds__(64 * NVT, kGatherMinW) gather_kernel(FrameDev 
   const __amdgpu_buffer_rsrc_t rfeat = buf_rsrc(f.feat, (unsigned)NV * map_px * 128u);
   const __amdgpu_buffer_rsrc_t rmatch = buf_rsrc(f.match, (unsigned)NV * map_px * (unsigned)f.match_ch * 4u);
   // image features of (point, view) -> token columns 0..31 (ray_transformer.py:222-226)
+  // (items view-major: the eight lane groups of one instruction are eight consecutive local points of ONE view)
   for (int item = grp; item < 64 * NV; item += n_grp) {
-    const int ip = item / NV, iv = item - ip * NV;
-    const int ipidx = blk * 64 + ip;
+    const int iv = item >> 6, ip = item & 63;
+    const int ipidx = point_of(ip);
     if (ipidx < P) {
       const Tap2 t = get_tap(sh_tapF + (iv * 64 + ip) * 8);
       st4(x_tokens + ((size_t)ipidx * NV + iv) * row_cols + 4 * c8,
@@ -285,7 +301,7 @@ __global__ void __launch_bounds__(64 * NVT, kGatherMinW) gather_kernel(FrameDev 
   // lane c8 = channel group gi of model.py:278-280
   if (!sim8_in)
   for (int item = grp; item < 64 * npair; item += n_grp) {
-    const int ip = item / npair, q = item - ip * npair;
+    const int q = item >> 6, ip = item & 63;
     int a = 0, rem = q;
     while (rem >= NV - 1 - a) { rem -= NV - 1 - a; ++a; }
     const int b = a + rem;
@@ -383,26 +399,37 @@ __global__ void __launch_bounds__(64 * NVT, kGatherMinW) gather_kernel(FrameDev 
 
   // ---- token assembly: [feat 32 | vol 24 | sim 16 | depth PE 8] (ray_transformer.py:258-281): the block's sh_out rows,
   // frustum lookup 32..55 | pre_sim_mlp output 56..71, copied by all its threads, consecutive lanes = consecutive 16 bytes
-  const int npts = P - blk * 64 < 64 ? P - blk * 64 : 64;    // the last block may be partial
-  if (x_point) {   // compact layout: once per point; the block's rows are one contiguous piece of x_point
-    float* dst = x_point + (size_t)blk * 64 * kPointCols;
+  // Output order j = 0..63 of the block's points: the consecutive-point map's is the local point itself; the ray-block map walks ray by
+  // ray (j = ray * kBlkSamples + sample), so that kBlkSamples consecutive j are consecutive rows of the output: the
+  // block's rows are kBlkRays contiguous runs (8 x 1 280 bytes of x_point) instead of one piece.  Rays past the last one
+  // come last in that order, so a partial block is j < npts in either map.
+  int npts = P - pbase < 64 ? P - pbase : 64;                 // the last block may be partial
+  if (SG) {
+    const int nrays = (P - pbase + SN - 1) / SN;              // rays of this group that exist (P - pbase > 0: its first ray does)
+    npts = nrays < kBlkRays ? kBlkSamples * nrays : 64;
+  }
+  const auto local_of = [=](int j) { return SG ? (int)((unsigned)j % kBlkSamples) * kBlkRays + (int)((unsigned)j / kBlkSamples) : j; };
+  if (x_point) {   // compact layout: once per point
     for (int i = threadIdx.x; i < npts * 10; i += 64 * NV) {
-      const int ip = i / 10, c = i - ip * 10;
-      st4(dst + 4 * i, ld4(sh_out + ip * out_stride + 4 * c));
+      const int j = i / 10, c = i - j * 10, ip = local_of(j);
+      st4(x_point + (size_t)point_of(ip) * kPointCols + 4 * c, ld4(sh_out + ip * out_stride + 4 * c));
     }
   } else {         // public layout: the per-point columns go into every view's row
     for (int i = threadIdx.x; i < npts * NV * 10; i += 64 * NV) {
-      const int row = i / 10, c = i - row * 10;
-      st4(x_tokens + ((size_t)blk * 64 * NV + row) * UFR_TOKEN_DIM + 32 + 4 * c, ld4(sh_out + (row / NV) * out_stride + 4 * c));
+      const int row = i / 10, c = i - row * 10, j = row / NV, ip = local_of(j);
+      st4(x_tokens + ((size_t)point_of(ip) * NV + (row - j * NV)) * UFR_TOKEN_DIM + 32 + 4 * c, ld4(sh_out + ip * out_stride + 4 * c));
     }
   }
   if (vol24_out)
     for (int i = threadIdx.x; i < npts * 24; i += 64 * NV) {
-      const int ip = i / 24;
-      vol24_out[(size_t)blk * 64 * 24 + i] = sh_out[ip * out_stride + (i - ip * 24)];
+      const int j = i / 24, ip = local_of(j);
+      vol24_out[(size_t)point_of(ip) * 24 + (i - j * 24)] = sh_out[ip * out_stride + (i - j * 24)];
     }
   if (sim8_out)
-    for (int i = threadIdx.x; i < npts * 8; i += 64 * NV) sim8_out[(size_t)blk * 64 * 8 + i] = sh_sim[(i >> 3) * sim_slot + (i & 7)];
+    for (int i = threadIdx.x; i < npts * 8; i += 64 * NV) {
+      const int ip = local_of(i >> 3);
+      sim8_out[(size_t)point_of(ip) * 8 + (i & 7)] = sh_sim[ip * sim_slot + (i & 7)];
+    }
   UFR_G_PHASE(5)  // token assembly
 #ifdef UFR_PHASE_TIMING
   if (threadIdx.x == 0) {
@@ -420,10 +447,13 @@ hipError_t launch_gather(const FrameDev& f, const PreSim& ps, const float* ray_o
   const int npair = NV * (NV - 1) / 2;
   const size_t taps = 2 * (size_t)NV * 64 * 8, volp = (size_t)64 * (NV - 1) * 25, outv = npair * 8 >= 48 ? 0 : 64 * 40;
   size_t lds = sizeof(float) * ((size_t)64 * npair * 8 + std::max(std::max(taps, volp), outv));
+  // ray-block map (8 rays x 8 samples per block) where the sample count allows it; every other shape keeps 64 consecutive points
+  const int SG = (SN % kBlkSamples == 0 && RN >= kBlkRays) ? SN / kBlkSamples : 0;
+  const int blocks = SG ? ((RN + kBlkRays - 1) / kBlkRays) * SG : (P + 63) / 64;
   switch (NV) {
 #define UFR_GATHER_CASE(N)                                                                                                   \
     case N:                                                                                                                  \
-      hipLaunchKernelGGL(gather_kernel<N>, dim3((P + 63) / 64), dim3(64 * N), lds, s, f, ps, ray_o, o_stride, ray_d, z, P, SN, \
+      hipLaunchKernelGGL(gather_kernel<N>, dim3(blocks), dim3(64 * N), lds, s, f, ps, ray_o, o_stride, ray_d, z, P, SN, SG, \
                          x_tokens, x_point, rgb, dir, sim8, vol24, xy, mask_z, vol24_in, sim8_in);                          \
       break;
     UFR_GATHER_CASE(2) UFR_GATHER_CASE(3) UFR_GATHER_CASE(4) UFR_GATHER_CASE(5) UFR_GATHER_CASE(6) UFR_GATHER_CASE(7)
