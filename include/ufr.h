@@ -32,7 +32,7 @@ enum ufr_status {
 
 /* Version of this header's ABI (argument lists, struct layouts, packed-blob layout).  ufr_version() returns the value
  * the library was built with: a binding must refuse a library whose version differs (uforecon_amd/_lib.py does). */
-#define UFR_ABI_VERSION 506
+#define UFR_ABI_VERSION 507
 
 #define UFR_MAX_VIEWS 7
 #define UFR_NUM_STAGES 3
@@ -643,6 +643,63 @@ int ufr_depth_points_count(const uint8_t* mask, int32_t H, int32_t W, void* work
 int ufr_depth_points_emit(const uint8_t* mask, const double* depth_avg, const uint8_t* color, int32_t H, int32_t W,
                           const double* inv_k, const double* inv_e, void* workspace, size_t workspace_bytes, float* xyz,
                           uint8_t* rgb, int64_t capacity, ufr_stream stream);
+
+/* ---- DTU mesh cleaning (ABI 507) ------------------------------------------------------------------------------
+ * The device side of evaluation/clean_mesh.py (mask votes, first-hit faces, small components); uforecon_amd/clean_mesh.py is
+ * the caller that strings these together, tests/clean_mesh_ref.py the numpy statement of every rule below.  verts (V,3) fp64,
+ * faces (F,3) int32, images (H,W) row-major: device.  H, W >= 1, H * W < 2^31; V, F >= 1.
+ *
+ * ufr_mask_half_widths: the rows of cv.getStructuringElement(MORPH_ELLIPSE, (k, k)) as half-widths, k odd, 1 .. UFR_MASK_MAX_KERNEL:
+ *   with r = k / 2, row dy = i - r covers columns -dx .. dx, dx = rint(r * sqrt((r*r - dy*dy) / (r*r))) in fp64, round half to
+ *   even (0 for r = 0).  k = 11: 0 3 4 5 5 5 5 5 4 3 0.  out: HOST int32[k].  No OpenCV was at hand: this table is the rule.
+ * ufr_mask_dilate: cv.dilate(image, that element) of a uint8 image: the maximum over the element centred on the pixel, pixels
+ *   outside the image ignored (OpenCV's default border).  dilated (nullable): the uint8 result; mask (nullable): 1 where the
+ *   result > threshold (the reference: 128), else 0.  Does not synchronise.
+ * ufr_mesh_vertex_votes: clean_points_by_mask (:106-147) without its final comparison.  P: (n_views,3,4) fp32 DEVICE, the
+ *   reference's read_cam_file product K4 @ E; masks (n_views,H,W) uint8 device, non-zero = set.  Per view in fp64 with P widened:
+ *   q = P[:3,:3] x + P[:3,3] (products summed left to right, then the translation), q / q.z, px = rint(q.x), py = rint(q.y)
+ *   (round half to even).  The vertex counts for the view iff -1 <= px <= W-1 and -1 <= py <= H-1 and (px == -1 or py == -1 or
+ *   masks[view][py][px] != 0): the reference's +1 shift into a ones border, asymmetry included.  No z > 0 test, as in the
+ *   reference; q.z = 0 or a non-finite q does not count.  votes (V) int32 = the number of views.  Integer atomics: the same
+ *   bits run after run.  Does not synchronise.
+ * ufr_mesh_first_hit: the face every masked pixel's ray hits first, for one view (clean_mesh_faces_outside_frustum :220-247
+ *   with trimesh's intersects_first).  k_inv 3x3 and c2w 4x4: HOST fp32 row-major, the inverse intrinsics and the pose that
+ *   gen_rays_from_single_image is given.  Ray of pixel (x, y) in fp32, no fused multiply-add, products summed left to right:
+ *   p = k_inv (x, y, 1), v = p / sqrt((p.x*p.x + p.y*p.y) + p.z*p.z), d = c2w[:3,:3] v, o = c2w[:3,3].  Intersection in fp64
+ *   from those values widened: a, b, c = the vertices - o; for each edge the product e = d . (u x v) of its vertex pair taken
+ *   in ascending vertex-index order, negated for the other direction, so both faces of an edge use one number; hit iff the
+ *   three are all >= 0 or all <= 0 (both sides, edges and vertices inclusive) and not all 0; n = (b - a) x (c - a),
+ *   t = (n . a) / (n . d), no hit when n . d = 0 (zero area) or not t > 0.  The first hit is the smallest (float)t, ties to the
+ *   lowest face index (a 64-bit atomic minimum over (float bits of t) << 32 | face: order-independent).  face_id (H,W) int32:
+ *   the face, or -1 where mask is 0 or nothing is hit.  face_hit (F) uint8, nullable: set to 1 for every face in face_id and
+ *   otherwise left alone, so that a caller accumulates over views.  A face with an index outside 0..V-1 is never hit.  Only
+ *   the pixels inside a triangle's projected box (padded by 1/16 pixel) are tested; a triangle with a vertex at camera depth
+ *   <= 0 is tested against the whole image, one wholly behind the camera against none.  workspace >=
+ *   ufr_mesh_first_hit_workspace_bytes(F, H, W) (device).  Does not synchronise.
+ * ufr_mesh_edge_keys: keys (3F) int64: slot 3f + e is edge (faces[f][e], faces[f][(e+1)%3]) as lo << 32 | hi of
+ *   vertex_id[index] (vertex_id (V) int32 >= 0, device, nullable = the index itself: the caller's merge of equal vertices).  A
+ *   face with an index out of range or two equal ids gets the unique negative keys -(slot + 1).  Does not synchronise.
+ * ufr_mesh_face_components: sorted_keys (3F): those keys sorted ascending; order (3F) int64: the slot each came from (what
+ *   torch.sort returns).  Two faces are adjacent iff they share a key that occurs exactly twice (trimesh.face_adjacency).
+ *   labels (F) int32: the lowest face index of the face's component, -1 for a face with no adjacency.  Union-find: rounds of
+ *   hooking (the larger of two roots under the smaller, atomic minimum) and pointer jumping until a round hooks nothing;
+ *   SYNCHRONISES the stream once per round; *rounds_host (nullable) = rounds run, the last, idle one included.  The labels do
+ *   not depend on scheduling.  workspace >= ufr_mesh_face_components_workspace_bytes(F) (device); F <= (2^31 - 1) / 3.   */
+#define UFR_MASK_MAX_KERNEL 127
+#define UFR_MESH_MAX_VIEWS 64
+int ufr_mask_half_widths(int32_t k, int32_t* out);
+int ufr_mask_dilate(const uint8_t* image, int32_t H, int32_t W, int32_t k, int32_t threshold, uint8_t* dilated, uint8_t* mask,
+                    ufr_stream stream);
+int ufr_mesh_vertex_votes(const double* verts, int64_t V, const float* P, const uint8_t* masks, int32_t n_views, int32_t H,
+                          int32_t W, int32_t* votes, ufr_stream stream);
+size_t ufr_mesh_first_hit_workspace_bytes(int64_t F, int32_t H, int32_t W);
+int ufr_mesh_first_hit(const double* verts, const int32_t* faces, int64_t V, int64_t F, const float* k_inv, const float* c2w,
+                       const uint8_t* mask, int32_t H, int32_t W, int32_t* face_id, uint8_t* face_hit, void* workspace,
+                       size_t workspace_bytes, ufr_stream stream);
+int ufr_mesh_edge_keys(const int32_t* faces, const int32_t* vertex_id, int64_t V, int64_t F, int64_t* keys, ufr_stream stream);
+size_t ufr_mesh_face_components_workspace_bytes(int64_t F);
+int ufr_mesh_face_components(const int64_t* sorted_keys, const int64_t* order, int64_t F, int32_t* labels, void* workspace,
+                             size_t workspace_bytes, int32_t* rounds_host, ufr_stream stream);
 
 /* Pixel-wise view weights of the first cascade stage and the weighted aggregate (DepthNet.forward,
  * code1/encoder_utils/fmt/TransMVSNet.py:80-97 with PixelwiseNet :23-41), one pass over the similarity volume:

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # UFR_LIB selects an alternative in-tree build (A/B kernel variants during development)
 LIB_PATH = os.environ.get("UFR_LIB") or os.path.join(HERE, "lib", "libufr.so")
 
-ABI_VERSION = 506   # = UFR_ABI_VERSION of include/ufr.h; load() refuses a library built against another header
+ABI_VERSION = 507   # = UFR_ABI_VERSION of include/ufr.h; load() refuses a library built against another header
 MAX_VIEWS = 7
 NUM_STAGES = 3
 TOKEN_DIM = 80
@@ -147,6 +147,14 @@ SIGNATURES = {
     "ufr_depth_points_workspace_bytes": (sz, [i32, i32]),
     "ufr_depth_points_count": (C.c_int, [vp, i32, i32, vp, sz, C.POINTER(i64), vp]),
     "ufr_depth_points_emit": (C.c_int, [vp, vp, vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, sz, vp, vp, i64, vp]),
+    "ufr_mask_half_widths": (C.c_int, [i32, C.POINTER(i32)]),
+    "ufr_mask_dilate": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp]),
+    "ufr_mesh_vertex_votes": (C.c_int, [vp, i64, vp, vp, i32, i32, i32, vp, vp]),
+    "ufr_mesh_first_hit_workspace_bytes": (sz, [i64, i32, i32]),
+    "ufr_mesh_first_hit": (C.c_int, [vp, vp, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, i32, i32, vp, vp, vp, sz, vp]),
+    "ufr_mesh_edge_keys": (C.c_int, [vp, vp, i64, i64, vp, vp]),
+    "ufr_mesh_face_components_workspace_bytes": (sz, [i64]),
+    "ufr_mesh_face_components": (C.c_int, [vp, vp, i64, vp, vp, sz, C.POINTER(i32), vp]),
     "ufr_pixelwise_view_weights": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ufr_deform_conv2d_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ufr_deform_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),

@@ -1,5 +1,6 @@
 // extern "C" surface of libufr.so (include/ufr.h), part 6 of 6: geometry after the network -- TSDF fusion, marching cubes,
-// the DTU chamfer evaluation and depth-map fusion.  The count / emit pairs synchronise the stream to hand a count to the host.
+// the DTU chamfer evaluation, depth-map fusion and mesh cleaning.  The count / emit pairs synchronise the stream to hand a
+// count to the host; so do the rounds of the two fixpoints (point thinning, face components).
 #include "api_common.h"
 #include "mcubes_table.h"
 
@@ -98,6 +99,41 @@ int depth_points_check(const char* who, const uint8_t* mask, int32_t H, int32_t 
   Carver c(ws);
   *w = carve_depth_points(c, (long long)H * W);
   return check_workspace(who, ws_bytes, c.off);
+}
+
+// ---- mesh cleaning
+// first hit: [key image uint64 per pixel | big-triangle count int32 | big-triangle list int32 per face]
+struct FirstHitWs { unsigned long long* keys; int *big_count, *big_list; };
+FirstHitWs carve_first_hit(Carver& c, long long F, long long pixels) {
+  FirstHitWs w;
+  w.keys = c.take<unsigned long long>((size_t)pixels);
+  w.big_count = c.take<int>(1);
+  w.big_list = c.take<int>((size_t)F);
+  return w;
+}
+
+// components: [pair faces int32 x2 per edge slot | parent int32 per face | adjacency flag uint8 per face | changed int32]
+struct ComponentsWs { int *pair_a, *pair_b, *parent, *changed; unsigned char* has_adj; };
+ComponentsWs carve_components(Carver& c, long long F) {
+  ComponentsWs w;
+  w.pair_a = c.take<int>((size_t)F * 3);
+  w.pair_b = c.take<int>((size_t)F * 3);
+  w.parent = c.take<int>((size_t)F);
+  w.has_adj = c.take<unsigned char>((size_t)F);
+  w.changed = c.take<int>(1);
+  return w;
+}
+
+bool invert3(const double* m, double* o) {
+  const double c0 = m[4] * m[8] - m[5] * m[7], c1 = m[5] * m[6] - m[3] * m[8], c2 = m[3] * m[7] - m[4] * m[6];
+  const double det = m[0] * c0 + m[1] * c1 + m[2] * c2;
+  if (!(det != 0.0) || !std::isfinite(det)) return false;
+  o[0] = c0 / det, o[1] = (m[2] * m[7] - m[1] * m[8]) / det, o[2] = (m[1] * m[5] - m[2] * m[4]) / det;
+  o[3] = c1 / det, o[4] = (m[0] * m[8] - m[2] * m[6]) / det, o[5] = (m[2] * m[3] - m[0] * m[5]) / det;
+  o[6] = c2 / det, o[7] = (m[1] * m[6] - m[0] * m[7]) / det, o[8] = (m[0] * m[4] - m[1] * m[3]) / det;
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(o[i])) return false;
+  return true;
 }
 
 }  // namespace
@@ -318,6 +354,125 @@ int ufr_depth_points_emit(const uint8_t* mask, const double* depth_avg, const ui
   UFR_REQUIRE(capacity >= tot, "%s: capacity %lld is smaller than the %lld points counted", who, (long long)capacity, tot);
   if (tot == 0) return UFR_OK;
   UFR_TIMED("depth_points_emit", s, launch_depth_points_emit(mask, depth_avg, color, H, W, inv_k, inv_e, w.block_off, xyz, rgb, tot, s));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ mesh cleaning
+int ufr_mask_half_widths(int32_t k, int32_t* out) {
+  UFR_REQUIRE(out, "ufr_mask_half_widths: null argument");
+  UFR_REQUIRE(k >= 1 && k <= UFR_MASK_MAX_KERNEL && k % 2 == 1, "ufr_mask_half_widths: k %d (must be odd, 1 .. %d)", k,
+              UFR_MASK_MAX_KERNEL);
+  const int r = k / 2;
+  for (int i = 0; i < k; ++i) {
+    const double dy = (double)(i - r), r2 = (double)r * r;
+    out[i] = r ? (int32_t)rint((double)r * sqrt((r2 - dy * dy) / r2)) : 0;   // rint: round half to even
+  }
+  return UFR_OK;
+}
+
+int ufr_mask_dilate(const uint8_t* image, int32_t H, int32_t W, int32_t k, int32_t threshold, uint8_t* dilated, uint8_t* mask,
+                    ufr_stream stream) {
+  const char* who = "ufr_mask_dilate";
+  UFR_REQUIRE(image && (dilated || mask), "%s: null argument", who);
+  UFR_CHECK(depth_image_check(who, H, W));
+  int32_t hw[UFR_MASK_MAX_KERNEL];
+  UFR_CHECK(ufr_mask_half_widths(k, hw));
+  short hs[UFR_MASK_MAX_KERNEL];
+  for (int i = 0; i < k; ++i) hs[i] = (short)hw[i];
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mask_dilate", s, launch_mask_dilate(image, H, W, k, hs, threshold, dilated, mask, s));
+  return UFR_OK;
+}
+
+int ufr_mesh_vertex_votes(const double* verts, int64_t V, const float* P, const uint8_t* masks, int32_t n_views, int32_t H,
+                          int32_t W, int32_t* votes, ufr_stream stream) {
+  const char* who = "ufr_mesh_vertex_votes";
+  UFR_REQUIRE(verts && P && masks && votes, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax, "%s: V %lld (must be 1 .. 2^31 - 1)", who, (long long)V);
+  UFR_REQUIRE(n_views >= 1 && n_views <= UFR_MESH_MAX_VIEWS, "%s: n_views %d (must be 1 .. %d)", who, n_views, UFR_MESH_MAX_VIEWS);
+  UFR_CHECK(depth_image_check(who, H, W));
+  UFR_REQUIRE((long long)H * W * n_views < (1ll << 31), "%s: %d masks of %dx%d have 2^31 pixels or more", who, n_views, H, W);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_HIP(hipMemsetAsync(votes, 0, (size_t)V * sizeof(int32_t), s));
+  UFR_TIMED("mesh_vertex_votes", s, launch_vertex_votes(verts, V, P, n_views, masks, H, W, votes, s));
+  return UFR_OK;
+}
+
+size_t ufr_mesh_first_hit_workspace_bytes(int64_t F, int32_t H, int32_t W) {
+  if (F < 1 || F > kChMax || H < 1 || W < 1 || (long long)H * W >= (1ll << 31)) return 0;
+  return carved_bytes(carve_first_hit, (long long)F, (long long)H * W);
+}
+
+int ufr_mesh_first_hit(const double* verts, const int32_t* faces, int64_t V, int64_t F, const float* k_inv, const float* c2w,
+                       const uint8_t* mask, int32_t H, int32_t W, int32_t* face_id, uint8_t* face_hit, void* workspace,
+                       size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_mesh_first_hit";
+  UFR_REQUIRE(verts && faces && k_inv && c2w && mask && face_id && workspace, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax, "%s: V %lld, F %lld (each must be 1 .. 2^31 - 1)", who, (long long)V,
+              (long long)F);
+  UFR_CHECK(depth_image_check(who, H, W));
+  Carver c(workspace);
+  const FirstHitWs w = carve_first_hit(c, F, (long long)H * W);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  // the fp64 inverse of the fp32 ray generator: pixel ~ inv(k_inv) inv(R) (X - o)
+  float rot[9], org[3];
+  double ki[9], r[9], kf[9], rw[9], m[9], proj[12];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) rot[3 * i + j] = c2w[4 * i + j], r[3 * i + j] = (double)c2w[4 * i + j], ki[3 * i + j] = (double)k_inv[3 * i + j];
+    org[i] = c2w[4 * i + 3];
+  }
+  UFR_REQUIRE(invert3(ki, kf) && invert3(r, rw), "%s: k_inv or the rotation of c2w is singular or not finite", who);
+  UFR_REQUIRE(std::isfinite(org[0]) && std::isfinite(org[1]) && std::isfinite(org[2]), "%s: the camera centre is not finite", who);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) m[3 * i + j] = kf[3 * i] * rw[j] + kf[3 * i + 1] * rw[3 + j] + kf[3 * i + 2] * rw[6 + j];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) proj[4 * i + j] = m[3 * i + j];
+    proj[4 * i + 3] = -(m[3 * i] * (double)org[0] + m[3 * i + 1] * (double)org[1] + m[3 * i + 2] * (double)org[2]);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_first_hit", s, launch_first_hit(verts, faces, V, F, k_inv, rot, org, proj, mask, H, W, w.keys, w.big_count,
+      w.big_list, face_id, face_hit, s));
+  return UFR_OK;
+}
+
+int ufr_mesh_edge_keys(const int32_t* faces, const int32_t* vertex_id, int64_t V, int64_t F, int64_t* keys, ufr_stream stream) {
+  const char* who = "ufr_mesh_edge_keys";
+  UFR_REQUIRE(faces && keys, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax / 3, "%s: V %lld, F %lld (V must be 1 .. 2^31 - 1, F 1 .. (2^31 - 1) / 3)",
+              who, (long long)V, (long long)F);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_edge_keys", s, launch_edge_keys(faces, vertex_id, V, F, reinterpret_cast<long long*>(keys), s));
+  return UFR_OK;
+}
+
+size_t ufr_mesh_face_components_workspace_bytes(int64_t F) {
+  return (F >= 1 && F <= kChMax / 3) ? carved_bytes(carve_components, (long long)F) : 0;
+}
+
+int ufr_mesh_face_components(const int64_t* sorted_keys, const int64_t* order, int64_t F, int32_t* labels, void* workspace,
+                             size_t workspace_bytes, int32_t* rounds_host, ufr_stream stream) {
+  const char* who = "ufr_mesh_face_components";
+  UFR_REQUIRE(sorted_keys && order && labels && workspace, "%s: null argument", who);
+  UFR_REQUIRE(F >= 1 && F <= kChMax / 3, "%s: F %lld (must be 1 .. (2^31 - 1) / 3)", who, (long long)F);
+  Carver c(workspace);
+  const ComponentsWs w = carve_components(c, F);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_mark_pairs", s, launch_mark_pairs(reinterpret_cast<const long long*>(sorted_keys),
+      reinterpret_cast<const long long*>(order), F, w.pair_a, w.pair_b, w.has_adj, w.parent, s));
+  int rounds = 0;
+  for (;;) {   // a round that hooks lowers some parent, and parents are >= 0: it ends; F + 1 rounds is label propagation's bound
+    if (rounds > F) return fail(UFR_ERR_HIP, "%s: no fixpoint after %d rounds", who, rounds);
+    int changed = 0;
+    UFR_HIP(hipMemsetAsync(w.changed, 0, sizeof(int), s));
+    UFR_TIMED("mesh_component_round", s, launch_component_round(w.pair_a, w.pair_b, F, w.parent, w.changed, s));
+    UFR_HIP(hipMemcpyAsync(&changed, w.changed, sizeof(int), hipMemcpyDeviceToHost, s));
+    UFR_HIP(hipStreamSynchronize(s));
+    ++rounds;
+    if (!changed) break;
+  }
+  UFR_TIMED("mesh_component_labels", s, launch_component_labels(w.parent, w.has_adj, F, labels, s));
+  if (rounds_host) *rounds_host = rounds;
   return UFR_OK;
 }
 

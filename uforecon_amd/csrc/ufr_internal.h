@@ -167,6 +167,20 @@ hipError_t launch_depth_points_count(const unsigned char* mask, long long n, lon
 hipError_t launch_depth_points_emit(const unsigned char* mask, const double* depth_avg, const unsigned char* color, int H, int W,
                                     const double* inv_k, const double* inv_e, const long long* block_off, float* xyz,
                                     unsigned char* rgb, long long capacity, hipStream_t s);
+// mesh_clean.hip: DTU mesh cleaning -- mask dilation, vertex votes, first-hit faces, face components (see the file header)
+hipError_t launch_mask_dilate(const unsigned char* src, int H, int W, int k, const short* half_widths, int thresh,
+                              unsigned char* dilated, unsigned char* mask, hipStream_t s);
+hipError_t launch_vertex_votes(const double* verts, long long V, const float* P, int NV, const unsigned char* masks, int H, int W,
+                               int* votes, hipStream_t s);
+hipError_t launch_first_hit(const double* verts, const int* faces, long long V, long long F, const float* kinv, const float* rot,
+                            const float* org, const double* proj, const unsigned char* mask, int H, int W,
+                            unsigned long long* keys, int* big_count, int* big_list, int* face_id, unsigned char* face_hit,
+                            hipStream_t s);
+hipError_t launch_edge_keys(const int* faces, const int* vid, long long V, long long F, long long* keys, hipStream_t s);
+hipError_t launch_mark_pairs(const long long* keys, const long long* order, long long F, int* pair_a, int* pair_b,
+                             unsigned char* has_adj, int* parent, hipStream_t s);
+hipError_t launch_component_round(const int* pair_a, const int* pair_b, long long F, int* parent, int* changed, hipStream_t s);
+hipError_t launch_component_labels(const int* parent, const unsigned char* has_adj, long long F, int* labels, hipStream_t s);
 // conv2d.hip: the plain 2-D convolutions of FeatureNet on channel-last tensors, epilogue fused (see the file header)
 struct Conv2dArgs {
   const float* in;      // [B][H][W][CIN] (the stem: planar [B][3][H][W])

@@ -971,6 +971,140 @@ def depth_points(mask: torch.Tensor, depth_avg: torch.Tensor, color: torch.Tenso
     return xyz, rgb
 
 
+# ---- DTU mesh cleaning (csrc/mesh_clean.hip; uforecon_amd/clean_mesh.py strings these together)
+MASK_MAX_KERNEL = 127      # UFR_MASK_MAX_KERNEL of include/ufr.h
+MESH_MAX_VIEWS = 64        # UFR_MESH_MAX_VIEWS
+
+
+def _mesh(verts: torch.Tensor, faces: torch.Tensor, who: str):
+    """pointers and sizes of a mesh; raises on a face index outside 0..V-1 (one host synchronisation)"""
+    pv = _points64(verts, "verts")
+    pf = _dev(faces, "faces", torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise UfrError(f"{who}: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
+    return pv, pf, V, F
+
+
+def mask_half_widths(k: int):
+    """ufr_mask_half_widths: the rows of cv.getStructuringElement(MORPH_ELLIPSE, (k, k)) as half-widths (a list of k ints)."""
+    k = int(k)
+    if not (1 <= k <= MASK_MAX_KERNEL and k % 2 == 1):
+        raise UfrError(f"mask_half_widths: k {k} (must be odd, 1 .. {MASK_MAX_KERNEL})")
+    out = (C.c_int32 * k)()
+    _lib.check(_lib.load().ufr_mask_half_widths(k, out), "ufr_mask_half_widths")
+    return list(out)
+
+
+def dilate_mask(image: torch.Tensor, k: int = 11, threshold: int = 128, return_dilated: bool = False):
+    """ufr_mask_dilate: cv.dilate of ``image`` ((H,W) CUDA uint8) with the k x k MORPH_ELLIPSE element, pixels outside the image
+    ignored, then ``> threshold``.  Returns the (H,W) uint8 0/1 mask, with ``return_dilated`` also the dilated uint8 image.
+    Does not synchronise."""
+    p = _dev(image, "image", torch.uint8)
+    if image.dim() != 2 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise UfrError(f"image: expected shape (H, W) with H, W >= 1, got {tuple(image.shape)}")
+    k = int(k)
+    if not (1 <= k <= MASK_MAX_KERNEL and k % 2 == 1):
+        raise UfrError(f"dilate_mask: k {k} (must be odd, 1 .. {MASK_MAX_KERNEL})")
+    H, W = int(image.shape[0]), int(image.shape[1])
+    mask = torch.empty((H, W), dtype=torch.uint8, device=image.device)
+    dil = torch.empty((H, W), dtype=torch.uint8, device=image.device) if return_dilated else None
+    _lib.check(_lib.load().ufr_mask_dilate(p, H, W, k, int(threshold), None if dil is None else dil.data_ptr(), mask.data_ptr(),
+                                           _stream()), "ufr_mask_dilate")
+    return (mask, dil) if return_dilated else mask
+
+
+def mesh_vertex_votes(verts: torch.Tensor, P: torch.Tensor, masks: torch.Tensor) -> torch.Tensor:
+    """ufr_mesh_vertex_votes: in how many views a vertex projects into the mask or onto the reference's ones border
+    (include/ufr.h).  ``verts`` (V,3) CUDA float64, ``P`` (NV,3,4) or (NV,4,4) CUDA float32 (the first three rows are used),
+    ``masks`` (NV,H,W) CUDA uint8.  Returns (V,) int32.  Does not synchronise."""
+    pv = _points64(verts, "verts")
+    if not isinstance(P, torch.Tensor) or P.dim() != 3 or tuple(P.shape[1:]) not in ((3, 4), (4, 4)):
+        raise UfrError(f"P: expected shape (NV, 3, 4) or (NV, 4, 4), got {tuple(getattr(P, 'shape', ()))}")
+    if P.shape[1] == 4:
+        P = P[:, :3].contiguous()
+    pp = _dev(P, "P")
+    pm = _dev(masks, "masks", torch.uint8)
+    NV = int(P.shape[0])
+    if masks.dim() != 3 or masks.shape[0] != NV or masks.shape[1] < 1 or masks.shape[2] < 1:
+        raise UfrError(f"masks: expected shape ({NV}, H, W), got {tuple(masks.shape)}")
+    if not 1 <= NV <= MESH_MAX_VIEWS:
+        raise UfrError(f"mesh_vertex_votes: {NV} views (must be 1 .. {MESH_MAX_VIEWS})")
+    V = int(verts.shape[0])
+    votes = torch.zeros(V, dtype=torch.int32, device=verts.device)
+    if V:
+        _lib.check(_lib.load().ufr_mesh_vertex_votes(pv, V, pp, pm, NV, int(masks.shape[1]), int(masks.shape[2]), votes.data_ptr(),
+                                                     _stream()), "ufr_mesh_vertex_votes")
+    return votes
+
+
+def mesh_first_hit(verts: torch.Tensor, faces: torch.Tensor, k_inv, c2w, mask: torch.Tensor,
+                   face_hit: Optional[torch.Tensor] = None):
+    """ufr_mesh_first_hit: the face that the ray of every pixel with ``mask`` != 0 hits first, for one view.  ``verts`` (V,3)
+    CUDA float64, ``faces`` (F,3) CUDA int32, ``mask`` (H,W) CUDA uint8; ``k_inv`` 3x3 and ``c2w`` 4x4: host arrays, narrowed to
+    float32 (what gen_rays_from_single_image is given).  Returns ``face_id`` (H,W) int32 (-1: no ray or no hit) and ``face_hit``
+    (F,) uint8, in which every hit face is set to 1; pass the previous view's ``face_hit`` to accumulate.  A face index out
+    of range raises.  One host synchronisation (the index check)."""
+    import numpy as np
+
+    pv, pf, V, F = _mesh(verts, faces, "mesh_first_hit")
+    pm = _dev(mask, "mask", torch.uint8)
+    if mask.dim() != 2 or mask.shape[0] < 1 or mask.shape[1] < 1:
+        raise UfrError(f"mask: expected shape (H, W) with H, W >= 1, got {tuple(mask.shape)}")
+    ki = np.ascontiguousarray(np.asarray(k_inv, np.float32))
+    cw = np.ascontiguousarray(np.asarray(c2w, np.float32))
+    if ki.shape != (3, 3) or cw.shape != (4, 4):
+        raise UfrError(f"mesh_first_hit: k_inv {ki.shape}, c2w {cw.shape}: expected (3, 3) and (4, 4)")
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    dev = verts.device
+    if face_hit is None:
+        face_hit = torch.zeros(F, dtype=torch.uint8, device=dev)
+    ph = _dev(face_hit, "face_hit", torch.uint8)
+    if tuple(face_hit.shape) != (F,):
+        raise UfrError(f"face_hit: expected shape ({F},), got {tuple(face_hit.shape)}")
+    face_id = torch.full((H, W), -1, dtype=torch.int32, device=dev)
+    if F == 0:
+        return face_id, face_hit
+    lib = _lib.load()
+    nbytes = lib.ufr_mesh_first_hit_workspace_bytes(F, H, W)
+    if nbytes == 0:
+        raise UfrError(f"mesh_first_hit: F {F}, image {H}x{W} unsupported")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    fp = C.POINTER(C.c_float)
+    _lib.check(lib.ufr_mesh_first_hit(pv, pf, V, F, ki.ctypes.data_as(fp), cw.ctypes.data_as(fp), pm, H, W, face_id.data_ptr(), ph,
+                                      ws.data_ptr(), nbytes, _stream()), "ufr_mesh_first_hit")
+    return face_id, face_hit
+
+
+def mesh_face_components(verts: torch.Tensor, faces: torch.Tensor, return_rounds: bool = False):
+    """Connected components of the faces over trimesh's face adjacency (include/ufr.h, ufr_mesh_edge_keys and
+    ufr_mesh_face_components): vertices with exactly equal coordinates are one vertex (``torch.unique``), two faces are adjacent
+    iff they share an undirected edge that exactly two faces have.  ``verts`` (V,3) CUDA float64, ``faces`` (F,3) CUDA int32.
+    Returns ``labels`` (F,) int32: the lowest face index of the component, -1 for a face without adjacency (a face with two
+    equal vertices has none).  A face index out of range raises.  Synchronises once per union-find round."""
+    pv, pf, V, F = _mesh(verts, faces, "mesh_face_components")
+    dev = verts.device
+    if F == 0:
+        labels = torch.zeros(0, dtype=torch.int32, device=dev)
+        return (labels, 0) if return_rounds else labels
+    vid = torch.unique(verts, dim=0, return_inverse=True)[1].to(torch.int32).contiguous()
+    lib = _lib.load()
+    keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+    _lib.check(lib.ufr_mesh_edge_keys(pf, vid.data_ptr(), V, F, keys.data_ptr(), _stream()), "ufr_mesh_edge_keys")
+    skeys, order = torch.sort(keys)
+    nbytes = lib.ufr_mesh_face_components_workspace_bytes(F)
+    if nbytes == 0:
+        raise UfrError(f"mesh_face_components: {F} faces unsupported")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    labels = torch.empty(F, dtype=torch.int32, device=dev)
+    rounds = C.c_int32(0)
+    _lib.check(lib.ufr_mesh_face_components(skeys.data_ptr(), order.data_ptr(), F, labels.data_ptr(), ws.data_ptr(), nbytes,
+                                            C.byref(rounds), _stream()), "ufr_mesh_face_components")
+    return (labels, int(rounds.value)) if return_rounds else labels
+
+
 CONV3D_S1, CONV3D_S2, CONV3D_T2 = 0, 1, 2
 
 
