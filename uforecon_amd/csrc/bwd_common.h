@@ -1,25 +1,23 @@
-// Building blocks of the backward kernels (config C5: training step through the HIP path).
+// The LDS-tile machinery of presim_bwd.hip, the one backward kernel still built this way (the transformers' backward moved
+// to the register-chained dgrad kernels and wgrad_stream.hip).
 //
-// Design (gfx950): a 256-thread workgroup (one wave per SIMD, one workgroup per CU: every wave owns the full 512-entry
-// register file of its SIMD, which is what the register-resident weight-gradient tiles need) walks
-// tiles of kTT = 32 tokens = kCT = 2 MFMA column tiles (round 2: 16.  The phases of a tile are separated by workgroup
-// barriers and are latency-bound -- LDS round trips, weight loads from L2, shuffles -- so two column tiles per phase
-// nearly halve the per-token cost: one weight fragment feeds two MFMAs, every per-token phase has all 256 threads busy).
+// Design (gfx950): a 256-thread workgroup (one wave per SIMD: every wave owns the full 512-entry register file of its SIMD,
+// which is what the register-resident weight-gradient tiles need) walks tiles of kTT = 32 tokens = kCT = 2 MFMA column
+// tiles.  The phases of a tile are separated by workgroup barriers and are latency-bound -- LDS round trips, weight loads
+// from L2 -- so two column tiles per phase nearly halve the per-token cost: one weight fragment feeds two MFMAs.
 // Every activation of the tile lives in LDS, feature-major [feature][kLD]
 // (kLD = kTT + 1: odd stride -> the three MFMA operand access patterns below are bank-conflict free), in
-// exact fp32; buffers whose live ranges do not overlap share rows (the kernels' row maps).
+// exact fp32; buffers whose live ranges do not overlap share rows (the kernel's row map).
 // All contractions run on v_mfma_f32_16x16x4_f32 (bitwise an fp32 fma chain):
-//   data GEMM      Y[o][t]  = sum_i W[o][i]  X[i][t]    A = weights from global (L1/L2-resident, 0.6 MB),
+//   data GEMM      Y[o][t]  = sum_i W[o][i]  X[i][t]    A = weights from global (L1/L2-resident),
 //   transposed     dX[i][t] = sum_o W[o][i] dY[o][t]     B = activations from LDS, tokens are the 16 columns
 //   weight grad    dW[o][i] = sum_t dY[o][t] X[i][t]     A and B from LDS, k = the tile's 16 tokens
 // Weight gradients accumulate in REGISTERS across the workgroup's persistent tile loop (output tile
 // (s*4 + wave) of the kernel's gradient-tile list lives in accumulator slot s of that wave) and are
-// flushed once per workgroup with float atomics into the reference-layout gradient tensors.  A matrix's tiles are
-// accumulated right after its dY is final (wgrad_range), beside the GEMM that consumes the same dY -- not in one phase at
-// the end of the tile: that is what lets dY / X buffers die early and share LDS rows.
+// flushed once per workgroup with float atomics into the reference-layout gradient tensors.
 #pragma once
 #include "ufr_device.h"
-#include "weight_stream.h"   // static_for
+#include "ufr_internal.h"   // GradPtrs, atomic_add_f32
 
 namespace ufr {
 
@@ -29,10 +27,6 @@ constexpr int kTT = 32;           // tokens per tile
 constexpr int kCT = kTT / 16;     // MFMA column tiles per tile
 constexpr int kLD = kTT + 1;      // LDS row stride (floats)
 static_assert(kTT % 16 == 0 && kBwdThreads % kTT == 0, "tile shape");
-
-struct GradPtrs { float* p[P_COUNT]; };
-
-__device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
 
 // Every LDS / global address of these kernels is a function of the thread index and compile-time constants, i.e.
 // invariant over the persistent tile loop: left alone, LICM precomputes all of them ahead of the loop (several hundred
@@ -188,14 +182,6 @@ __device__ __forceinline__ void gemm_compute(AFrag<IN>& cur, const float* __rest
     }
     if (more) cur = nxt;
   }
-}
-
-// prefetch + compute in one call (phases whose B operand is already published)
-template <int OUT, int IN, bool TRANS, bool LOWP, typename Epi>
-__device__ __forceinline__ void gemm_lds(const float* __restrict__ W, int ldw, const float* X, int wave, int lane,
-                                         Epi epi, int rt_shift = 0) {
-  AFrag<IN> f = gemm_prefetch<OUT, IN, TRANS>(W, ldw, wave, lane, rt_shift);
-  gemm_compute<OUT, IN, TRANS, LOWP>(f, W, ldw, X, wave, lane, epi, rt_shift);
 }
 
 __device__ __forceinline__ void wgrad_flush(f32x4 acc, float* dW, int ldw, int o0, int i0, int OUT, int IN, int lane) {
@@ -378,104 +364,6 @@ __device__ __forceinline__ void wgrad_flush_all(const f32x4 (&acc)[NACC], const 
   }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// LayerNorm over D features of each of the 16 tokens: kTPT consecutive threads per token.
-//   forward : buf[D][kLD] holds the input and receives xhat; out[f] = xhat*gamma + beta (+ res[f] if res); rstd[t]
-//   backward: dout[D][kLD] -> din = rstd*(g - mean(g) - xhat*mean(g*xhat)), g = dout*gamma   (written to din)
-constexpr int kTPT = kBwdThreads / kTT;   // threads per token in the per-token phases
-// thread -> (token, sub): the kTPT threads of a token are adjacent lanes (shuffle reductions).  With 32-token tiles
-// (kTPT = 8) the tokens of a half-wave are 8 apart, so that the 32 lanes of an LDS access [feature sub + kTPT i][token]
-// hit 32 different banks (bank = sub + 8 (token / 8) + const); the plain tid / kTPT map put four tokens of a half-wave on
-// overlapping banks (4-way conflicts in every LayerNorm phase).
-__device__ __forceinline__ void ln_thread_map(int tid, int& tok, int& sub) {
-  if constexpr (kTT == 32 && kBwdThreads == 256) {
-    const int lane = tid & 63, wave = tid >> 6;
-    sub = lane & 7;
-    tok = 8 * ((lane >> 3) & 3) + 2 * wave + (lane >> 5);
-  } else {
-    tok = tid / kTPT;
-    sub = tid % kTPT;
-  }
-}
-template <int D>
-__device__ __forceinline__ void ln_forward(float* buf, float* out, const float* res, const float* __restrict__ gamma,
-                                           const float* __restrict__ beta, float* rstd, int tid) {
-  tid = opaque(tid);
-  int tok, sub;
-  ln_thread_map(tid, tok, sub);
-  // a thread's features stay in registers over the three passes (one LDS read each instead of three)
-  constexpr int NPT = (D + kTPT - 1) / kTPT;
-  float v[NPT];
-#pragma unroll
-  for (int i = 0; i < NPT; ++i) {
-    const int f = sub + i * kTPT;
-    v[i] = f < D ? buf[f * kLD + tok] : 0.f;
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < NPT; ++i)
-    if (sub + i * kTPT < D) s += v[i];
-#pragma unroll
-  for (int d = kTPT / 2; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-  const float mean = s * (1.f / D);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < NPT; ++i)
-    if (sub + i * kTPT < D) {
-      const float c = v[i] - mean;
-      q = fmaf(c, c, q);
-    }
-#pragma unroll
-  for (int d = kTPT / 2; d >= 1; d >>= 1) q += __shfl_xor(q, d);
-  const float rs = 1.f / sqrtf(q * (1.f / D) + 1e-5f);
-  if (sub == 0) rstd[tok] = rs;
-#pragma unroll
-  for (int i = 0; i < NPT; ++i) {
-    const int f = sub + i * kTPT;
-    if (f < D) {
-      const float xh = (v[i] - mean) * rs;
-      buf[f * kLD + tok] = xh;
-      float y = fmaf(xh, gamma[f], beta[f]);
-      if (res) y += res[f * kLD + tok];
-      out[f * kLD + tok] = y;
-    }
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void ln_backward(const float* dout, const float* xhat, const float* __restrict__ gamma,
-                                            const float* rstd, float* din, int tid) {
-  tid = opaque(tid);
-  int tok, sub;
-  ln_thread_map(tid, tok, sub);
-  constexpr int NPT = (D + kTPT - 1) / kTPT;
-  float gg[NPT], xh[NPT];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < NPT; ++i) {
-    const int f = sub + i * kTPT;
-    gg[i] = 0.f;
-    xh[i] = 0.f;
-    if (f < D) {
-      gg[i] = dout[f * kLD + tok] * gamma[f];
-      xh[i] = xhat[f * kLD + tok];
-      s1 += gg[i];
-      s2 = fmaf(gg[i], xh[i], s2);
-    }
-  }
-#pragma unroll
-  for (int d = kTPT / 2; d >= 1; d >>= 1) {
-    s1 += __shfl_xor(s1, d);
-    s2 += __shfl_xor(s2, d);
-  }
-  const float m1 = s1 * (1.f / D), m2 = s2 * (1.f / D), rs = rstd[tok];
-#pragma unroll
-  for (int i = 0; i < NPT; ++i) {
-    const int f = sub + i * kTPT;
-    if (f < D) din[f * kLD + tok] = rs * (gg[i] - m1 - xh[i] * m2);
-  }
-}
-
 // row sums over the tile's tokens: sum_t a[t] * (b ? b[t] : 1).  All 2 kTT operands are requested before the first use
 // (one LDS round trip): written as a running sum inside the callers' thread-range branches, every read was followed by
 // its own s_waitcnt and the "small gradient" sums cost 7 k cycles per tile.  `b == nullptr` lanes read `a` twice and
@@ -498,7 +386,5 @@ __device__ __forceinline__ float row_dot(const float* a, const float* b, int f) 
   }
   return (s[0] + s[1]) + (s[2] + s[3]);
 }
-
-__device__ __forceinline__ float elu1_grad(float x) { return x > 0.f ? 1.f : __expf(x); }
 
 }  // namespace ufr

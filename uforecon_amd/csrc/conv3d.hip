@@ -15,8 +15,8 @@
 //  * a transposed convolution is 8 ordinary convolutions, one per output parity class (pz,py,px), with 1..8 taps each:
 //    blockIdx.y selects the class, so a wave never diverges over taps.
 // The head layers write the reference's (B,C,D,H,W) layout directly (feature frustum 8 channels + sigmoid weight frustum).
+#include "ufr_device.h"
 #include "ufr_internal.h"
-#include "weight_stream.h"   // static_for
 
 namespace ufr {
 

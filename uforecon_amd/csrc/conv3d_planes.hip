@@ -30,7 +30,6 @@
 
 #include "ufr_device.h"
 #include "ufr_internal.h"
-#include "weight_stream.h"   // static_for
 
 namespace ufr {
 

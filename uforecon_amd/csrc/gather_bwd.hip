@@ -19,7 +19,6 @@
 // coalesced pass (volume_unpack_kernel) then writes the reference-layout tensors (NV,8,D,H,W) / (NV,1,D,H,W).
 #include "ufr_internal.h"
 #include "volume_sample.h"
-#include "weight_stream.h"   // static_for
 
 namespace ufr {
 

@@ -16,49 +16,16 @@
 //            d V = d KV_h^T-contract K', d K' = d KV_h V (fp32 MFMAs);  d k, d v -> k^T, v^T -> d x;  d token0 rows out
 // LayerNorm gamma / beta are reduced here (DPP row all-reduce into per-wave LDS accumulators, flushed once); all other
 // parameter gradients are contractions of the tiles.
-#include "bwd_common.h"   // GradPtrs
 #include "bwd_tape.h"
 #include "ufr_internal.h"
-#include "weight_stream_f16.h"
+#include "transformer_tiles.h"
 
 namespace ufr {
 
 constexpr int kRdBlock = 256, kRdWaves = 4;
 constexpr int kRdAccFloats = 4 * 3 * 64;   // per wave: 4 vectors (norm1 / norm2 gamma, beta) x 3 blocks of ten values x 64 lanes
 
-// v[i] <- sum of v[i] over the 16 lanes of the DPP row (view_dgrad.hip: row_allreduce10)
-__device__ __forceinline__ void rd_row_allreduce10(float (&v)[10]) {
-#define UFR_RR_STEP(CTRL)                                                    \
-  "v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %1, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %2, %2, %2 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %3, %3, %3 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %4, %4, %4 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %5, %5, %5 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %6, %6, %6 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %7, %7, %7 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %8, %8, %8 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %9, %9, %9 " CTRL " row_mask:0xf bank_mask:0xf\n\t"
-  asm volatile("s_nop 1\n\t" UFR_RR_STEP("quad_perm:[1,0,3,2]") UFR_RR_STEP("quad_perm:[2,3,0,1]") UFR_RR_STEP("row_half_mirror")
-               UFR_RR_STEP("row_mirror")
-               : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]));
-#undef UFR_RR_STEP
-}
-// acc[64 b] += sum over the 16 token lanes of value 10 b + j of a nat88 vector (6 tiles x 4 registers = 24 values per lane
-// group, the padding ones zero): lane j < 10 keeps the j-th sum of block b
-__device__ __forceinline__ void rd_reduce_acc88(const f32x4 (&t)[6], float* acc, int j) {
-#pragma unroll
-  for (int b = 0; b < 3; ++b) {
-    float v[10];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) v[i] = 10 * b + i < 24 ? t[(10 * b + i) >> 2][(10 * b + i) & 3] : 0.f;
-    rd_row_allreduce10(v);
-    float mine = v[0];
-#pragma unroll
-    for (int i = 1; i < 10; ++i) mine = j == i ? v[i] : mine;
-    acc[64 * b] += mine;
-  }
-}
+// the flush of a reduce_acc_tiles accumulator (transformer_tiles.h) of a nat88 vector: padding registers have no feature
 __device__ __forceinline__ void rd_flush88(const float* acc, float* __restrict__ dst, int g, int j) {
 #pragma unroll
   for (int b = 0; b < 3; ++b) {
@@ -192,8 +159,8 @@ __global__ void __launch_bounds__(kRdBlock, 2) ray_dgrad_kernel(const float* __r
         if (t == 5) { dopre[0][t][2] = 0.f; dopre[0][t][3] = 0.f; }   // nat88 padding: no such feature
         dy_st(DR_OPRE + t, dopre[0][t]);
       }
-      rd_reduce_acc88(dgam, a_n2w, j);
-      rd_reduce_acc88(dout[0], a_n2b, j);
+      reduce_acc_tiles(dgam, a_n2w, j);
+      reduce_acc_tiles(dout[0], a_n2b, j);
     }
 
     // ---------------- MLP backwards (transformer.py:55-56)
@@ -238,8 +205,8 @@ __global__ void __launch_bounds__(kRdBlock, 2) ray_dgrad_kernel(const float* __r
         if (t == 5) { dmpre[0][t][2] = 0.f; dmpre[0][t][3] = 0.f; }
         dy_st(DR_MPRE + t, dmpre[0][t]);
       }
-      rd_reduce_acc88(dgam, a_n1w, j);
-      rd_reduce_acc88(dbet, a_n1b, j);
+      reduce_acc_tiles(dgam, a_n1w, j);
+      reduce_acc_tiles(dbet, a_n1b, j);
     }
     // ---------------- merge backwards: d msg, quad-packed like the message (quad 3h + q: head h, dims 3g + q)
     f32x4 dmsg[C][6];

@@ -20,7 +20,7 @@
 // are permuted at pack time, the kernel only renames registers.  The 88-wide activations use the "nat88" layout.
 #include "bwd_tape.h"
 #include "ufr_internal.h"
-#include "weight_stream_f16.h"
+#include "transformer_tiles.h"
 
 namespace ufr {
 
@@ -33,45 +33,6 @@ __device__ __forceinline__ void load_ray_tile(const float* __restrict__ token0, 
   for (int t = 0; t < 5; ++t) x[t] = ld4(row + 16 * t + 4 * g);
   const float* pe = order_pe + (size_t)(s_base + j) * 8 + 2 * g;  // features 80+2g, 81+2g in registers 0,1
   x[5] = f32x4{pe[0], pe[1], 0.f, 0.f};
-}
-
-// LayerNorm over 88 features in nat88 layout (tile 5: registers 0,1 real)
-// XH / RS (TAPE builds): the normalised input and 1 / sigma of the TRUE values, which the backward needs
-template <int VW, int VB, int C, class WS>
-__device__ __forceinline__ void layer_norm88(f32x4 (&tt)[C][6], const WS& ws, int g, float eps, float asc, f32x4 (*XH)[6] = nullptr, float* RS = nullptr) {
-  // eps = 1e-5 asc^2: raw accumulators (asc times the values), view_transformer.hip layer_norm80
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    f32x4 (&t)[6] = tt[c];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) s += (t[i][0] + t[i][1]) + (t[i][2] + t[i][3]);
-    s += t[5][0] + t[5][1];
-    const float mean = sum_groups(s) * (1.f / 88.f);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (i < 5 || r < 2) {
-          float d = t[i][r] - mean;
-          q = fmaf(d, d, q);
-        }
-      }
-    const float rstd = fast_rsqrt(sum_groups(q) * (1.f / 88.f) + eps);
-    if (RS) RS[c] = rstd * asc;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const f32x4 gw = vec_frag<VW>(ws, i, g), gb = vec_frag<VB>(ws, i, g);  // zero in the padding slots
-      // element by element: f32x4 expressions become packed-f32 VALU, an anti-lever beside MFMAs (view_transformer.hip)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float xh = (t[i][r] - mean) * rstd;
-        if (XH) XH[c][i][r] = (i == 5 && r >= 2) ? 0.f : xh;                  // nat88: registers 2, 3 of tile 5 are padding
-        t[i][r] = xh * gw[r] + gb[r];
-      }
-    }
-  }
 }
 
 // 256-thread workgroups = 4 rays (one wave each, one per SIMD), two workgroups per CU; the four waves
@@ -382,20 +343,17 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : kRtMinW) ray_transformer_
       tape_st(RT_ZS + 1, f32x4{zs_all[4], zs_all[5], zs_all[6], zs_all[7]});
     }
     f32x4 m[C][6];
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-#pragma unroll
-      for (int t = 0; t < 6; ++t) m[c][t] = splat4(0.f);
+    zero_tiles(m);
     gemm_f16<M_RT_MERGE, C, kRtWaves>(ws, msg, m, wrap, sc[RS_M_XS]);
     UFR_RT_PHASE(4)  // merge GEMM
     float rstd1[C] = {}, rstd2[C] = {};
     if constexpr (TAPE) {
       f32x4 xh[C][6];
-      layer_norm88<V_RT_N1W, V_RT_N1B, C>(m, ws, g, sc[RS_EPS1], sc[RS_M_ASC], xh, rstd1);
+      layer_norm_tiles<6, 88, V_RT_N1W, V_RT_N1B>(m, ws, g, sc[RS_EPS1], sc[RS_M_ASC], xh, rstd1);
 #pragma unroll
       for (int t = 0; t < 6; ++t) { tape_st(RT_XH1 + t, xh[0][t]); tape_st(RT_M + t, m[0][t]); }
     } else {
-      layer_norm88<V_RT_N1W, V_RT_N1B, C>(m, ws, g, sc[RS_EPS1], 1.f);
+      layer_norm_tiles<6, 88, V_RT_N1W, V_RT_N1B>(m, ws, g, sc[RS_EPS1], 1.f);
     }
     UFR_RT_PHASE(5)  // LayerNorm 1
 
@@ -432,11 +390,11 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : kRtMinW) ray_transformer_
     UFR_RT_PHASE(7)  // ReLU + MLP2
     if constexpr (TAPE) {
       f32x4 xh[C][6];
-      layer_norm88<V_RT_N2W, V_RT_N2B, C>(o, ws, g, sc[RS_EPS2], sc[RS_MLP2_ASC], xh, rstd2);
+      layer_norm_tiles<6, 88, V_RT_N2W, V_RT_N2B>(o, ws, g, sc[RS_EPS2], sc[RS_MLP2_ASC], xh, rstd2);
 #pragma unroll
       for (int t = 0; t < 6; ++t) tape_st(RT_XH2 + t, xh[0][t]);
     } else {
-      layer_norm88<V_RT_N2W, V_RT_N2B, C>(o, ws, g, sc[RS_EPS2], 1.f);
+      layer_norm_tiles<6, 88, V_RT_N2W, V_RT_N2B>(o, ws, g, sc[RS_EPS2], 1.f);
     }
     UFR_RT_PHASE(8)  // LayerNorm 2
 #pragma unroll
@@ -444,7 +402,7 @@ __global__ void __launch_bounds__(kRtBlock, TAPE ? 2 : kRtMinW) ray_transformer_
 #pragma unroll
       for (int t = 0; t < 6; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[c][t][r] += x[c][t][r];   // scalar adds: no v_pk_add_f32 (layer_norm88)
+        for (int r = 0; r < 4; ++r) o[c][t][r] += x[c][t][r];   // scalar adds: no v_pk_add_f32 (layer_norm_tiles)
       if constexpr (TAPE) {
 #pragma unroll
         for (int t = 0; t < 6; ++t) tape_st(RT_O + t, o[c][t]);

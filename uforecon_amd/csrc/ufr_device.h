@@ -1,7 +1,10 @@
-// Device-side building blocks shared by the gfx950 kernels: MFMA helpers, lane exchange, the
-// three grid_sample conventions of the reference.
+// Device-side building blocks shared by the gfx950 kernels: MFMA helpers, the compile-time loop
+// (static_for), lane exchange, the three grid_sample conventions of the reference.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <utility>
+
 #include "ufr_layout.h"
 
 namespace ufr {
@@ -47,11 +50,15 @@ __device__ __forceinline__ float buf_ld1(__amdgpu_buffer_rsrc_t r, unsigned byte
 }
 __device__ __forceinline__ f32x4 splat4(float v) { return f32x4{v, v, v, v}; }
 
-__host__ __device__ constexpr int in_steps(int cm, int t) {
-  return (cm == COL_NAT88 && t == 5) ? 2
-       : (cm == COL_CAT88 && (t == 5 || t == 11)) ? 2
-       : (cm == COL_RW0 && t == 5) ? 1
-       : 4;
+// compile-time loop: f(std::integral_constant<int, i>) for i in [0, N) -- every layout number
+// must be a constant expression (the optimiser does not fold the constexpr table walks on its own)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
 }
 
 // ---- lane exchange among the L tokens of one point (tokens of a point are adjacent columns)
@@ -132,13 +139,6 @@ __device__ __forceinline__ void axpy10_rot4(float (&acc)[10], float w, const flo
 // x*log2(e) (rel. error ~|x| 2^-24, i.e. < 1e-6 for the |x| < 16 that matter) instead of the
 // 15-instruction ocml expf -- 80 of them per view-transformer iteration.
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x + 1.f : __expf(x); }
-// elu(s a) + 1 for a power-of-two s (a raw accumulator of the split-precision GEMMs): bit-identical to elu1(s * a), the
-// scale rides on the fma / on the exponent's log2(e) multiply
-template <int LOG2S>
-__device__ __forceinline__ float elu1_scaled(float a) {
-  constexpr float s = LOG2S >= 0 ? (float)(1u << (LOG2S >= 0 ? LOG2S : 0)) : 1.f / (float)(1u << (LOG2S < 0 ? -LOG2S : 0));
-  return a > 0.f ? __builtin_fmaf(a, s, 1.f) : __builtin_amdgcn_exp2f((0x1.715476p+0f * s) * a);
-}
 
 // sum over the 4 lane groups (lanes l, l^16, l^32, l^48)
 __device__ __forceinline__ float sum_groups(float x) {

@@ -95,7 +95,9 @@ hipError_t launch_composite_bwd(const float* z, const float* radiance, const int
                                 const float* variance, int RN, int SN, const float* d_rgb, const float* d_depth,
                                 const float* d_opacity, const float* d_weight, float* d_radiance, float* d_srdf,
                                 float* d_variance, hipStream_t s);
-struct GradPtrs;
+// one gradient tensor per parameter, in the reference layout (= ufr_raw_grads); the backward kernels add into them
+struct GradPtrs { float* p[P_COUNT]; };
+__device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
 // The streaming view-transformer backward (round 4; bwd_tape.h): the forward again with a tape, the data-gradient chain,
 // the weight-gradient contraction.  tape: view_tape_blocks(P, NV) blocks of TV_COUNT tiles; dbuf: as many blocks of DV_COUNT.
 int view_tape_blocks(int P, int NV);

@@ -11,7 +11,7 @@
 //
 // Fragments are stored in CONSUMPTION ORDER, one contiguous STREAM per kernel sweep, so a workgroup
 // can pull them through LDS in fixed-size chunks with lane-linear LDS-DMA (global_load_lds) and all
-// its waves read each fragment from LDS instead of L2 (weight_stream.h).
+// its waves read each fragment from LDS instead of L2 (weight_stream_f16.h).
 #pragma once
 #include <stdint.h>
 
@@ -197,24 +197,11 @@ __host__ __device__ constexpr int stream_base_floats(int s) {
   for (int t = 0; t < s; ++t) o += stream_frags_padded(t) * 256;
   return o;
 }
-// fragment (out tile `to`, in tile `ti`) of a matrix whose stages interleave OT out tiles:
-// order = group-major, then in tile, then the tile inside the group
-__host__ __device__ constexpr int frag_in_mat(int m, int ot, int to, int ti) {
-  const MatDesc d = mat_desc(m);
-  const int gi = to / ot, o = to % ot;
-  const int no = (d.n_out - gi * ot) < ot ? (d.n_out - gi * ot) : ot;
-  return gi * ot * d.n_in + ti * no + o;
-}
 // chunk boundaries (in fragments): nearly equal, multiples of 4 (one quarter per fetching wave; never
 // splits the two fragments of an OT=2 stage)
 __host__ __device__ constexpr int chunk_begin(int s, int c) {
   return c >= stream_chunks(s) ? stream_frags_padded(s)
                                : ((c * stream_frags_padded(s) / stream_chunks(s)) / kFetchSplit) * kFetchSplit;
-}
-__host__ __device__ constexpr int chunk_of(int s, int f) {
-  int c = 0;
-  while (c + 1 < stream_chunks(s) && chunk_begin(s, c + 1) <= f) ++c;
-  return c;
 }
 __host__ __device__ constexpr bool chunks_fit(int s) {
   for (int c = 0; c < stream_chunks(s); ++c)
@@ -277,9 +264,6 @@ __host__ __device__ constexpr int ray_scalars_offset() { return view_scalars_off
 __host__ __device__ constexpr int stats_offset() { return ray_scalars_offset() + kKernelScalars; }
 __host__ __device__ constexpr int vec_region_floats() { return scale_table_offset() + kScaleFloats - vec_region_offset(); }
 __host__ __device__ constexpr int blob_floats() { return scale_table_offset() + kScaleFloats; }
-__host__ __device__ constexpr int mat_offset(int m) {  // first float of matrix m inside the blob
-  return stream_base_floats(mat_stream(m)) + stream_mat_start(mat_stream(m), mat_stream_index(m)) * 256;
-}
 
 // Source of packed float i: parameter id (-1 = zero padding) and flat element index.
 __host__ __device__ inline void plan_entry(int i, int* param, int* elem) {

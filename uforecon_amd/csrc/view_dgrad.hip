@@ -14,53 +14,15 @@
 // per ten values; as tiles through HBM they were a sixth of the three kernels' traffic.
 // Outputs of this kernel itself: the dY tiles and d_pv (P,40) = the gradient w.r.t. the 24 frustum features and the 16
 // pre_sim_mlp outputs of each point, summed over its NV view tokens (gather_bwd.hip consumes it).
-#include "bwd_common.h"   // GradPtrs
 #include "bwd_tape.h"
 #include "ufr_internal.h"
-#include "weight_stream_f16.h"
+#include "transformer_tiles.h"
 
 namespace ufr {
 
 constexpr int kVdBlock = 256, kVdWaves = 4;
 
-// v[i] <- sum of v[i] over the 16 lanes of the DPP row (= the 16 token columns of a lane group), for ten values.  One block
-// of assembly: a DPP read needs two wait states after a VALU write of the same register and the hazard recogniser does not
-// look inside inline assembly -- within the block a register's next read is ten instructions after its write.
-__device__ __forceinline__ void row_allreduce10(float (&v)[10]) {
-#define UFR_RR_STEP(CTRL)                                                    \
-  "v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %1, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %2, %2, %2 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %3, %3, %3 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %4, %4, %4 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %5, %5, %5 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %6, %6, %6 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %7, %7, %7 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %8, %8, %8 " CTRL " row_mask:0xf bank_mask:0xf\n\t"        \
-  "v_add_f32_dpp %9, %9, %9 " CTRL " row_mask:0xf bank_mask:0xf\n\t"
-  asm volatile("s_nop 1\n\t" UFR_RR_STEP("quad_perm:[1,0,3,2]") UFR_RR_STEP("quad_perm:[2,3,0,1]") UFR_RR_STEP("row_half_mirror")
-               UFR_RR_STEP("row_mirror")
-               : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]));
-#undef UFR_RR_STEP
-}
-// acc[b] += sum over the 16 token lanes of value 10 b + j of the 80-feature natural-layout vector t (20 values per lane
-// group: two blocks of ten): after the all-reduce every lane of a row holds all ten sums and lane j < 10 keeps the j-th.
-// Accumulated over the wave's whole persistent loop -- in a private LDS slot per (vector, block, lane): ten more live
-// registers cost this kernel 50..70 spills -- and flushed once (flush80): per iteration the atomics of all waves would
-// queue up on the same 400 addresses (measured: +0.1 ms, more than the tiles had cost).
-__device__ __forceinline__ void reduce_acc80(const f32x4 (&t)[5], float* acc /* LDS: [2][64], this lane's column */, int j) {
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    float v[10];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) v[i] = t[(10 * b + i) >> 2][(10 * b + i) & 3];
-    row_allreduce10(v);
-    float mine = v[0];
-#pragma unroll
-    for (int i = 1; i < 10; ++i) mine = j == i ? v[i] : mine;
-    acc[64 * b] += mine;
-  }
-}
+// the flush of a reduce_acc_tiles accumulator (transformer_tiles.h) of an 80-feature natural-layout vector, once per launch
 __device__ __forceinline__ void flush80(const float* acc, float* __restrict__ dst, int g, int j) {
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
@@ -270,8 +232,8 @@ __global__ void __launch_bounds__(kVdBlock, 2) view_dgrad_kernel(const float* __
 #pragma unroll
         for (int t = 0; t < 5; ++t) { dy_st(DV_SCR + t, c, dy[c][t]); dy_st(DV_OPRE + t, c, dopre[c][t]); }
     }
-    reduce_acc80(dgam, a_n2w, j);       // (idle / padding columns carry zeros)
-    reduce_acc80(dbet, a_n2b, j);
+    reduce_acc_tiles(dgam, a_n2w, j);       // (idle / padding columns carry zeros)
+    reduce_acc_tiles(dbet, a_n2b, j);
 
     // ---------------- MLP backwards (transformer.py:55-56)
     f32x4 dhid[C][10];
@@ -331,8 +293,8 @@ __global__ void __launch_bounds__(kVdBlock, 2) view_dgrad_kernel(const float* __
 #pragma unroll
         for (int t = 0; t < 5; ++t) { dy_st(DV_SCR2 + t, c, dcat[c][t]); dy_st(DV_MPRE + t, c, dmpre[c][t]); }
     }
-    reduce_acc80(dgam, a_n1w, j);
-    reduce_acc80(dbet, a_n1b, j);
+    reduce_acc_tiles(dgam, a_n1w, j);
+    reduce_acc_tiles(dbet, a_n1b, j);
     // ---------------- merge backwards: d msg in the slot layout (lane group g <- heads 2g, 2g+1 of its token)
     f32x4 dmsg[C][5];
 #pragma unroll
@@ -454,7 +416,7 @@ __global__ void __launch_bounds__(kVdBlock, 2) view_dgrad_kernel(const float* __
         if (valid[c] && tv[c] == 0 && (t < 4 || g < 2)) st4(d_pv + (size_t)pidx[c] * 40 + 16 * (t - 2) + 4 * g, sum);
       }
     }
-    reduce_acc80(dtok, a_vtok, j);
+    reduce_acc_tiles(dtok, a_vtok, j);
     wstream_f16_finish<B_VTB, kVdWaves>(ws, wrap);
   }
   flush80(a_n1w, g_n1w, g, j);

@@ -15,64 +15,9 @@
 #include <cstdlib>
 #include "bwd_tape.h"
 #include "ufr_internal.h"
-#include "weight_stream_f16.h"
+#include "transformer_tiles.h"
 
 namespace ufr {
-
-// base + 32-bit element offset, the byte offset computed in 32 bits: the access becomes "scalar base + 32-bit lane
-// offset" (global_load ... v_off, s[base]) with no 64-bit per-lane address to keep alive (the launcher bounds the sizes)
-template <class T>
-__device__ __forceinline__ T* at32(T* base, unsigned elem) {
-  typedef typename std::conditional<std::is_const<T>::value, const char, char>::type B;
-  return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + (elem * (unsigned)sizeof(T)));
-}
-
-template <int C, int N>
-__device__ __forceinline__ void zero_tiles(f32x4 (&t)[C][N]) {
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int i = 0; i < N; ++i) t[c][i] = splat4(0.f);
-}
-
-// LayerNorm over the 80 features of each token: 5 tiles x 4 regs in each of the 4 lane groups.  t holds raw accumulators
-// (asc = 2^(s_M + a_M) times the values; asc = 1: plain values): the normalised value is scale-free once the epsilon carries
-// the square of the scale (eps = 1e-5 asc^2, formed once per launch), and with a power-of-two scale every intermediate is the exact multiple -- bit-identical to
-// descaling first.
-// XH / RS (TAPE builds): the normalised input and 1 / sigma of the TRUE values (asc times the raw one), which the
-// backward needs.
-template <int C, int VW, int VB, class WS>
-__device__ __forceinline__ void layer_norm80(f32x4 (&t)[C][5], const WS& ws, int g, float eps, float asc, f32x4 (*XH)[5] = nullptr, float* RS = nullptr) {
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) s += (t[c][i][0] + t[c][i][1]) + (t[c][i][2] + t[c][i][3]);
-    const float mean = sum_groups(s) * (1.f / 80.f);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float d = t[c][i][r] - mean;
-        q = fmaf(d, d, q);
-      }
-    const float rstd = fast_rsqrt(sum_groups(q) * (1.f / 80.f) + eps);
-    if (RS) RS[c] = rstd * asc;
-    // element by element on purpose: f32x4 expressions become v_pk_mul / v_pk_fma_f32, which cost more beside the
-    // partner wave's MFMAs than the two scalar instructions they replace (MI355X_MICROARCH.md, price of a filler)
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const f32x4 gw = vec_frag<VW>(ws, i, g), gb = vec_frag<VB>(ws, i, g);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float xh = (t[c][i][r] - mean) * rstd;
-        if (XH) XH[c][i][r] = xh;
-        t[c][i][r] = xh * gw[r] + gb[r];
-      }
-    }
-  }
-}
 
 // 256-thread workgroups (one wave per SIMD), two per CU; each streams the layer chain's weight planes
 // through its own ring of three 12 KiB LDS slots (weight_stream_f16.h).
@@ -471,13 +416,13 @@ __global__ void __launch_bounds__(kVtBlock, kVtMinW) view_transformer_kernel(con
     float rstd1[C] = {}, rstd2[C] = {};
     if constexpr (TAPE) {
       f32x4 xh[C][5];
-      layer_norm80<C, V_VT_N1W, V_VT_N1B>(m, ws, g, sc[VS_EPS1], sc[VS_M_ASC], xh, rstd1);
+      layer_norm_tiles<5, 80, V_VT_N1W, V_VT_N1B>(m, ws, g, sc[VS_EPS1], sc[VS_M_ASC], xh, rstd1);
 #pragma unroll
       for (int c = 0; c < C; ++c)
 #pragma unroll
         for (int t = 0; t < 5; ++t) { tape_st(TV_XH1 + t, c, xh[c][t]); tape_st(TV_M + t, c, m[c][t]); }
     } else {
-      layer_norm80<C, V_VT_N1W, V_VT_N1B>(m, ws, g, sc[VS_EPS1], 1.f);
+      layer_norm_tiles<5, 80, V_VT_N1W, V_VT_N1B>(m, ws, g, sc[VS_EPS1], 1.f);
     }
 
     UFR_PHASE(6)  // LN1
@@ -527,13 +472,13 @@ __global__ void __launch_bounds__(kVtBlock, kVtMinW) view_transformer_kernel(con
     UFR_PHASE(8)  // relu + MLP2
     if constexpr (TAPE) {
       f32x4 xh[C][5];
-      layer_norm80<C, V_VT_N2W, V_VT_N2B>(o, ws, g, sc[VS_EPS2], sc[VS_MLP2_ASC], xh, rstd2);
+      layer_norm_tiles<5, 80, V_VT_N2W, V_VT_N2B>(o, ws, g, sc[VS_EPS2], sc[VS_MLP2_ASC], xh, rstd2);
 #pragma unroll
       for (int c = 0; c < C; ++c)
 #pragma unroll
         for (int t = 0; t < 5; ++t) tape_st(TV_XH2 + t, c, xh[c][t]);
     } else {
-      layer_norm80<C, V_VT_N2W, V_VT_N2B>(o, ws, g, sc[VS_EPS2], 1.f);
+      layer_norm_tiles<5, 80, V_VT_N2W, V_VT_N2B>(o, ws, g, sc[VS_EPS2], 1.f);
     }
     // the residual (x stays in registers from the top of the iteration: re-reading the token rows was slower: DESIGN.md section 7)
 #pragma unroll
@@ -541,7 +486,7 @@ __global__ void __launch_bounds__(kVtBlock, kVtMinW) view_transformer_kernel(con
 #pragma unroll
       for (int t = 0; t < 5; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[c][t][r] += x[c][t][r];   // scalar adds: no v_pk_add_f32 (layer_norm80)
+        for (int r = 0; r < 4; ++r) o[c][t][r] += x[c][t][r];   // scalar adds: no v_pk_add_f32 (layer_norm_tiles)
     if constexpr (TAPE) {
 #pragma unroll
       for (int c = 0; c < C; ++c) {

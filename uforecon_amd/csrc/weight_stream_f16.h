@@ -1,10 +1,25 @@
 // fp16x3 split-precision GEMM core on the 16-bit matrix cores, fed by an LDS weight stream
-// (layout and arithmetic: ufr_layout_f16.h; streaming scheme: weight_stream.h).
+// (layout and arithmetic: ufr_layout_f16.h).
+//
+// The streaming scheme.  Every wave of a workgroup walks the same static sequence of 1 KiB operand fragments.  Instead of
+// each wave pulling its own copy from L2 (measured: 81-84 % of the MFMA rate at 2 waves/SIMD because 256 CUs x 8 waves
+// hammer the same L2 lines), the workgroup stages the stream through LDS in chunks:
+//
+//   chunk c -> LDS slot c % slots, fetched with lane-linear LDS-DMA (no VGPRs: lds_dma_piece), each wave issuing its share
+//   of a later chunk right after the barrier that opens the current one.  One barrier per chunk: it proves (a) every
+//   wave's share of chunk c has landed (each waits vmcnt first) and (b) every wave is done reading the chunk whose slot
+//   the next fetch overwrites.
+//
+// All positions (fragment index, chunk, slot, LDS offset) are compile-time constants of the fully unrolled layer chain;
+// only the fragments move: LDS -> registers -> MFMA.
+// (The first version of the kernels streamed fp32 A-fragments for v_mfma_f32_16x16x4_f32 through the same scheme;
+// ufr_layout.h still describes that fragment order -- the CPU layout tests use it -- but the kernels now read only the
+// vector fragments of that region.)
 #pragma once
 #include <type_traits>
 
+#include "ufr_device.h"
 #include "ufr_layout_f16.h"
-#include "weight_stream.h"
 
 namespace ufr {
 
@@ -14,6 +29,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+constexpr int kVecBytes = vec_region_floats() * 4;       // bias / LayerNorm / view-token fragments, resident in LDS
 constexpr int kF16RingBytes = kF16Slots * kF16ChunkFrags * 1024;  // the ring: kF16Slots (3) slots of kF16ChunkFrags (12) KiB
 constexpr int kF16LdsBytes = kF16RingBytes + kVecBytes;
 
@@ -293,9 +311,6 @@ __device__ __forceinline__ ScalarFile<LOCAL> scalar_file(const WS& ws) {
   return ScalarFile<LOCAL>{reinterpret_cast<const float*>(ws.vecs)[base + (ws.lane & (kKernelScalars - 1))]};
 }
 
-__device__ __forceinline__ f32x4 mfma_f16(const f16x8& a, const f16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 // the operands' 16-bit words are fp16 (BF = false) or bf16 (BF = true); same lane layout, same rate
 template <bool BF>
 __device__ __forceinline__ f32x4 mfma_planes(const f16x8& a, const f16x8& b, const f32x4& c) {
@@ -422,7 +437,6 @@ __device__ __forceinline__ void bwords_to_bstep(const BWords<C>& bw, BStep (&b)[
 __device__ __forceinline__ float elu1_acc(float a, float dsc, float dsc_l2e) {
   return a > 0.f ? __builtin_fmaf(a, dsc, 1.f) : __builtin_amdgcn_exp2f(dsc_l2e * a);
 }
-constexpr float kLog2e = 0x1.715476p+0f;
 
 // out += 2^(s_M + a_M) W_M x in over all k-steps of M, probed for the range (probe_gemm); the output stays a RAW
 // accumulator.  in[c][0..NIN) are the producer's fp32 tiles and m the multiplier that turns them into the planes'

@@ -17,7 +17,6 @@
 // merge, the four quadrants of mlp0, ... -- for a contiguous range of token blocks, and flushes them once with float atomics
 // into the reference-layout gradient tensors (undoing the row maps of ufr_layout.h).
 #include <cstdlib>
-#include "bwd_common.h"     // GradPtrs, atomic_add_f32
 #include "bwd_tape.h"
 #include "ufr_internal.h"
 #include "weight_stream_f16.h"   // f16x8 / bf16x8, mfma_planes
