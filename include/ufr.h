@@ -701,6 +701,53 @@ size_t ufr_mesh_face_components_workspace_bytes(int64_t F);
 int ufr_mesh_face_components(const int64_t* sorted_keys, const int64_t* order, int64_t F, int32_t* labels, void* workspace,
                              size_t workspace_bytes, int32_t* rounds_host, ufr_stream stream);
 
+/* ---- mesh rendering (ABI 507, additive) -----------------------------------------------------------------------
+ * The device side of render_trajectory_dtu.py / render_trajectory_open3d.py (a fly-through of a reconstructed mesh) without
+ * Open3D, OpenGL or a display; uforecon_amd/render_trajectory.py is the caller, tests/raster_ref.py the numpy statement of
+ * every rule below.  verts (V,3) fp64, faces (F,3) int32, images row-major: device.  H, W >= 1, H * W < 2^31; V, F >= 1.
+ * The same calls give z-depth, face-id and normal maps of a mesh from any camera.
+ *
+ * ufr_raster_vertex_normals: normals (V,3) fp64 = for each vertex the sum of the unnormalised face normals (b - a) x (c - a) of
+ *   the faces that use it (a, b, c in the face's own order, whichever corner the vertex is), divided by the length of the
+ *   sum: area weighting, as Open3D's compute_vertex_normals is remembered to do.  No Open3D was at hand: this rule is the
+ *   specification.  sorted_slots (3F) int64: the corner slots 3f + e stably sorted by their vertex index (what torch.sort with
+ *   stable=True returns as indices); run_starts (V+1) int64: vertex v owns positions run_starts[v] .. run_starts[v+1] - 1.
+ *   A run is summed in ascending position (= ascending slot) order in fp64, each component on its own, by one thread: no
+ *   floating-point atomics, the same bits run after run.  A vertex that no face uses and a vertex whose sum has length 0
+ *   (or is not finite) get (0, 0, 0); a zero-area face adds zero; a face with an index outside 0..V-1, a slot outside
+ *   0..3F-1 and a slot whose corner is not the vertex contribute nothing.  F <= (2^31 - 1) / 3.  Does not synchronise.
+ * ufr_raster_frames: n_frames >= 1 views of the mesh in one call.  k_inv 3x3 (shared) and c2w (n_frames,4,4): HOST fp32
+ *   row-major, with the meaning ufr_mesh_first_hit gives them.  Per frame: (1) that entry point's first hit over EVERY pixel
+ *   (the same kernels through the same launcher, with no mask; the key image is re-initialised for every frame), then (2)
+ *   one thread per pixel shades.  No hit: background, depth 0, face -1, normal 0.  Hit: the ray (fp32) and a, b, c, the ordered
+ *   edge products e_bc, e_ca, e_ab and n (fp64) are formed again with the first hit's expressions, then in fp64
+ *     w = (e_bc, e_ca, e_ab) / ((e_bc + e_ca) + e_ab)  (barycentrics of a, b, c),  t = (n . a) / (n . d),
+ *     shading normal N: smooth = (w_a N_a + w_b N_b) + w_c N_c divided by its length; flat (normals null, or that length
+ *       is not > 0) = n / |n|,
+ *     I = ambient + (1 - ambient) * |N . d|: a headlight with two-sided shading, so the winding does not matter,
+ *     colour = base_color, or with colors ((V,3) uint8, device, nullable) ((w_a C_a + w_b C_b) + w_c C_c) / 255,
+ *     pixel = rint((255 * colour) * I), round half to even, clamped to 0..255.
+ *   normals: (V,3) fp64 device, nullable (what ufr_raster_vertex_normals writes).  base_color: HOST float[3] in 0..1,
+ *   nullable = white (as the reference paints the mesh); background: HOST uint8[3], nullable = 255 255 255; ambient in
+ *   0..1 (the callers' default: 0.25).  Outputs (device, n_frames images): image (H,W,3) uint8; depth (H,W) fp32,
+ *   nullable = (float)(t * v.z) with v the camera-space unit ray: z-depth; face_id (H,W) int32, nullable; normal_map (H,W,3)
+ *   fp32, nullable = R^T N (camera coordinates, R = c2w[:3,:3]), negated when N . d > 0 so that it faces the camera.
+ *   workspace >= ufr_raster_frames_workspace_bytes(F, H, W) (device; 0 for unsupported sizes).  A camera that is singular or
+ *   not finite fails before anything is launched.  Enqueues 2 memsets and 4 kernels per frame and synchronises nowhere.
+ * ufr_raster_downsample: dst (n,H,W,3) uint8 = the mean of the s x s blocks of src (n,s*H,s*W,3) uint8, s in 1..4 (1 copies),
+ *   in integers: with n2 = s*s, q = sum / n2, r = sum % n2 the result is q + 1 iff 2r > n2, or 2r == n2 and q is odd (round
+ *   half to even), else q.  s*H * s*W < 2^31, n*H*W*3 < 2^38.  Does not synchronise.
+ * Every argument error (null pointer, H, W or n_frames < 1, H * W >= 2^31, s outside 1..4, ambient or a base colour outside
+ * 0..1, a workspace that is too small) is UFR_ERR_ARG with the reason in the thread's last-error text.                  */
+int ufr_raster_vertex_normals(const double* verts, const int32_t* faces, int64_t V, int64_t F, const int64_t* sorted_slots,
+                              const int64_t* run_starts, double* normals, ufr_stream stream);
+size_t ufr_raster_frames_workspace_bytes(int64_t F, int32_t H, int32_t W);
+int ufr_raster_frames(const double* verts, const int32_t* faces, int64_t V, int64_t F, const double* normals, const uint8_t* colors,
+                      const float* k_inv, const float* c2w, int32_t n_frames, int32_t H, int32_t W, const float* base_color,
+                      const uint8_t* background, double ambient, uint8_t* image, float* depth, int32_t* face_id, float* normal_map,
+                      void* workspace, size_t workspace_bytes, ufr_stream stream);
+int ufr_raster_downsample(const uint8_t* src, int32_t n, int32_t H, int32_t W, int32_t s, uint8_t* dst, ufr_stream stream);
+
 /* Pixel-wise view weights of the first cascade stage and the weighted aggregate (DepthNet.forward,
  * code1/encoder_utils/fmt/TransMVSNet.py:80-97 with PixelwiseNet :23-41), one pass over the similarity volume:
  *   view_weights[i] = max_d sigmoid(conv2(relu(bn1(conv1(relu(bn0(conv0(similarity[i]))))))))      (1x1x1 convolutions)

@@ -1,6 +1,6 @@
 // extern "C" surface of libufr.so (include/ufr.h), part 6 of 6: geometry after the network -- TSDF fusion, marching cubes,
-// the DTU chamfer evaluation, depth-map fusion and mesh cleaning.  The count / emit pairs synchronise the stream to hand a
-// count to the host; so do the rounds of the two fixpoints (point thinning, face components).
+// the DTU chamfer evaluation, depth-map fusion, mesh cleaning and mesh rendering.  The count / emit pairs synchronise the
+// stream to hand a count to the host; so do the rounds of the two fixpoints (point thinning, face components).
 #include "api_common.h"
 #include "mcubes_table.h"
 
@@ -112,6 +112,15 @@ FirstHitWs carve_first_hit(Carver& c, long long F, long long pixels) {
   return w;
 }
 
+// rendering: [the first hit's workspace | face image int32 per pixel]
+struct RasterFramesWs { FirstHitWs hit; int* face_img; };
+RasterFramesWs carve_raster_frames(Carver& c, long long F, long long pixels) {
+  RasterFramesWs w;
+  w.hit = carve_first_hit(c, F, pixels);
+  w.face_img = c.take<int>((size_t)pixels);
+  return w;
+}
+
 // components: [pair faces int32 x2 per edge slot | parent int32 per face | adjacency flag uint8 per face | changed int32]
 struct ComponentsWs { int *pair_a, *pair_b, *parent, *changed; unsigned char* has_adj; };
 ComponentsWs carve_components(Carver& c, long long F) {
@@ -134,6 +143,24 @@ bool invert3(const double* m, double* o) {
   for (int i = 0; i < 9; ++i)
     if (!std::isfinite(o[i])) return false;
   return true;
+}
+
+// rot, org of a host fp32 c2w, and the fp64 inverse of the fp32 ray generator: pixel ~ inv(k_inv) inv(R) (X - o)
+int hit_camera(const char* who, const float* k_inv, const float* c2w, float* rot, float* org, double* proj) {
+  double ki[9], r[9], kf[9], rw[9], m[9];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) rot[3 * i + j] = c2w[4 * i + j], r[3 * i + j] = (double)c2w[4 * i + j], ki[3 * i + j] = (double)k_inv[3 * i + j];
+    org[i] = c2w[4 * i + 3];
+  }
+  UFR_REQUIRE(invert3(ki, kf) && invert3(r, rw), "%s: k_inv or the rotation of c2w is singular or not finite", who);
+  UFR_REQUIRE(std::isfinite(org[0]) && std::isfinite(org[1]) && std::isfinite(org[2]), "%s: the camera centre is not finite", who);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) m[3 * i + j] = kf[3 * i] * rw[j] + kf[3 * i + 1] * rw[3 + j] + kf[3 * i + 2] * rw[6 + j];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) proj[4 * i + j] = m[3 * i + j];
+    proj[4 * i + 3] = -(m[3 * i] * (double)org[0] + m[3 * i + 1] * (double)org[1] + m[3 * i + 2] * (double)org[2]);
+  }
+  return UFR_OK;
 }
 
 }  // namespace
@@ -414,21 +441,9 @@ int ufr_mesh_first_hit(const double* verts, const int32_t* faces, int64_t V, int
   Carver c(workspace);
   const FirstHitWs w = carve_first_hit(c, F, (long long)H * W);
   UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
-  // the fp64 inverse of the fp32 ray generator: pixel ~ inv(k_inv) inv(R) (X - o)
   float rot[9], org[3];
-  double ki[9], r[9], kf[9], rw[9], m[9], proj[12];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) rot[3 * i + j] = c2w[4 * i + j], r[3 * i + j] = (double)c2w[4 * i + j], ki[3 * i + j] = (double)k_inv[3 * i + j];
-    org[i] = c2w[4 * i + 3];
-  }
-  UFR_REQUIRE(invert3(ki, kf) && invert3(r, rw), "%s: k_inv or the rotation of c2w is singular or not finite", who);
-  UFR_REQUIRE(std::isfinite(org[0]) && std::isfinite(org[1]) && std::isfinite(org[2]), "%s: the camera centre is not finite", who);
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) m[3 * i + j] = kf[3 * i] * rw[j] + kf[3 * i + 1] * rw[3 + j] + kf[3 * i + 2] * rw[6 + j];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) proj[4 * i + j] = m[3 * i + j];
-    proj[4 * i + 3] = -(m[3 * i] * (double)org[0] + m[3 * i + 1] * (double)org[1] + m[3 * i + 2] * (double)org[2]);
-  }
+  double proj[12];
+  UFR_CHECK(hit_camera(who, k_inv, c2w, rot, org, proj));
   hipStream_t s = static_cast<hipStream_t>(stream);
   UFR_TIMED("mesh_first_hit", s, launch_first_hit(verts, faces, V, F, k_inv, rot, org, proj, mask, H, W, w.keys, w.big_count,
       w.big_list, face_id, face_hit, s));
@@ -473,6 +488,74 @@ int ufr_mesh_face_components(const int64_t* sorted_keys, const int64_t* order, i
   }
   UFR_TIMED("mesh_component_labels", s, launch_component_labels(w.parent, w.has_adj, F, labels, s));
   if (rounds_host) *rounds_host = rounds;
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ mesh rendering
+int ufr_raster_vertex_normals(const double* verts, const int32_t* faces, int64_t V, int64_t F, const int64_t* sorted_slots,
+                              const int64_t* run_starts, double* normals, ufr_stream stream) {
+  const char* who = "ufr_raster_vertex_normals";
+  UFR_REQUIRE(verts && faces && sorted_slots && run_starts && normals, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax / 3, "%s: V %lld, F %lld (V must be 1 .. 2^31 - 1, F 1 .. (2^31 - 1) / 3)",
+              who, (long long)V, (long long)F);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("raster_vertex_normals", s, launch_raster_vertex_normals(verts, faces, V, F, reinterpret_cast<const long long*>(sorted_slots),
+      reinterpret_cast<const long long*>(run_starts), normals, s));
+  return UFR_OK;
+}
+
+size_t ufr_raster_frames_workspace_bytes(int64_t F, int32_t H, int32_t W) {
+  if (F < 1 || F > kChMax || H < 1 || W < 1 || (long long)H * W >= (1ll << 31)) return 0;
+  return carved_bytes(carve_raster_frames, (long long)F, (long long)H * W);
+}
+
+int ufr_raster_frames(const double* verts, const int32_t* faces, int64_t V, int64_t F, const double* normals, const uint8_t* colors,
+                      const float* k_inv, const float* c2w, int32_t n_frames, int32_t H, int32_t W, const float* base_color,
+                      const uint8_t* background, double ambient, uint8_t* image, float* depth, int32_t* face_id, float* normal_map,
+                      void* workspace, size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_raster_frames";
+  UFR_REQUIRE(verts && faces && k_inv && c2w && image && workspace, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax, "%s: V %lld, F %lld (each must be 1 .. 2^31 - 1)", who, (long long)V,
+              (long long)F);
+  UFR_REQUIRE(n_frames >= 1, "%s: n_frames %d (must be >= 1)", who, n_frames);
+  UFR_CHECK(depth_image_check(who, H, W));
+  UFR_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "%s: ambient %g (must be 0 .. 1)", who, ambient);
+  double base[3] = {1.0, 1.0, 1.0};
+  unsigned char bg[3] = {255, 255, 255};
+  for (int k = 0; k < 3; ++k) {
+    if (base_color) base[k] = (double)base_color[k];
+    if (background) bg[k] = background[k];
+    UFR_REQUIRE(base[k] >= 0.0 && base[k] <= 1.0, "%s: base colour %g (must be 0 .. 1)", who, base[k]);
+  }
+  Carver c(workspace);
+  const RasterFramesWs w = carve_raster_frames(c, F, (long long)H * W);
+  UFR_REQUIRE(workspace_bytes >= c.off, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, c.off);
+  float rot[9], org[3];
+  double proj[12];
+  for (int32_t i = 0; i < n_frames; ++i) UFR_CHECK(hit_camera(who, k_inv, c2w + 16 * (size_t)i, rot, org, proj));   // all, before any launch
+  const size_t px = (size_t)H * W;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int32_t i = 0; i < n_frames; ++i) {   // launches only: the cameras travel as kernel arguments, nothing waits for a frame
+    UFR_CHECK(hit_camera(who, k_inv, c2w + 16 * (size_t)i, rot, org, proj));
+    UFR_TIMED("raster_first_hit", s, launch_first_hit(verts, faces, V, F, k_inv, rot, org, proj, nullptr, H, W, w.hit.keys,
+        w.hit.big_count, w.hit.big_list, w.face_img, nullptr, s));
+    UFR_TIMED("raster_shade", s, launch_raster_shade(verts, faces, V, F, normals, colors, k_inv, rot, org, proj, base, ambient, bg,
+        w.face_img, H, W, image + 3 * px * i, depth ? depth + px * i : nullptr, face_id ? face_id + px * i : nullptr,
+        normal_map ? normal_map + 3 * px * i : nullptr, s));
+  }
+  return UFR_OK;
+}
+
+int ufr_raster_downsample(const uint8_t* src, int32_t n, int32_t H, int32_t W, int32_t s, uint8_t* dst, ufr_stream stream) {
+  const char* who = "ufr_raster_downsample";
+  UFR_REQUIRE(src && dst, "%s: null argument", who);
+  UFR_REQUIRE(n >= 1, "%s: n %d (must be >= 1)", who, n);
+  UFR_REQUIRE(s >= 1 && s <= 4, "%s: s %d (must be 1 .. 4)", who, s);
+  UFR_CHECK(depth_image_check(who, H, W));
+  UFR_REQUIRE((long long)H * s * W * s < (1ll << 31), "%s: %dx%d times %d squared has 2^31 pixels or more", who, H, W, s);
+  UFR_REQUIRE((long long)n * H * W * 3 < (1ll << 38), "%s: %d images of %dx%d have 2^38 bytes or more", who, n, H, W);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  UFR_TIMED("raster_downsample", st, launch_raster_downsample(src, n, H, W, s, dst, st));
   return UFR_OK;
 }
 

@@ -21,7 +21,8 @@
 //            t       n = (b - a) x (c - a), t = (n . a) / (n . d); n . d = 0 (zero area, or edge-on) never hits; t > 0 only
 //          and merges (float bits of t) << 32 | face into a 64-bit key image with an atomic minimum: the nearest (float) t wins,
 //          ties go to the lowest face, whatever the order of arrival.  first_hit_resolve turns keys into face ids and sets the
-//          per-face flags (every writer stores the same 1).
+//          per-face flags (every writer stores the same 1).  A null mask means every pixel (the renderer, raster.hip); the ray
+//          and the triangle set-up live in mesh_ray.h, which the shading kernel shares.
 //   face_components edge keys (lo << 32 | hi of the merged vertex ids, a unique negative key per slot of a degenerate face),
 //          sorted by the caller; mark_pairs keeps the runs of exactly two as adjacent face pairs; then rounds of union-find:
 //          hook (per pair, the larger root gets parent = min(parent, smaller root), atomically) and jump (every face to its
@@ -29,6 +30,7 @@
 //
 // Block shape: 256 threads throughout, no LDS.  Every index read from a caller's array is range-checked before it is used.
 #include "ufr_internal.h"
+#include "mesh_ray.h"
 
 #pragma clang fp contract(off)
 
@@ -81,65 +83,6 @@ __global__ void __launch_bounds__(kMcThreads) vertex_votes_kernel(const double* 
 }
 
 // ------------------------------------------------------------------ first hit
-struct HitCam {
-  float kinv[9], rot[9], org[3];
-  double proj[12];   // pixel = proj (X, 1) / its third row: the fp64 inverse of the ray generator
-};
-
-struct Tri {
-  double a[3], b[3], c[3];          // vertices - origin
-  double cbc[3], cca[3], cab[3];    // b x c, c x a, a x b (each formed in ascending index order)
-  double n[3], na;                  // (b - a) x (c - a), n . a
-};
-
-__device__ inline void cross3(const double* u, const double* v, double* o) {
-  o[0] = u[1] * v[2] - u[2] * v[1];
-  o[1] = u[2] * v[0] - u[0] * v[2];
-  o[2] = u[0] * v[1] - u[1] * v[0];
-}
-__device__ inline double dot3(const double* u, const double* v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
-
-// u x v with u the vertex `iu`, v the vertex `iv`: computed for the lower index first, negated when iu > iv
-__device__ inline void cross_ordered(const double* u, int iu, const double* v, int iv, double* o) {
-  if (iu <= iv) {
-    cross3(u, v, o);
-  } else {
-    cross3(v, u, o);
-    o[0] = -o[0];
-    o[1] = -o[1];
-    o[2] = -o[2];
-  }
-}
-
-// loads face f; false when an index is outside 0..V-1
-__device__ inline bool load_tri(const double* __restrict__ verts, const int* __restrict__ faces, long long V, long long f,
-                                const HitCam& cam, Tri* t, double world[9]) {
-  const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-  if (ia < 0 || ib < 0 || ic < 0 || ia >= V || ib >= V || ic >= V) return false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double o = (double)cam.org[k];
-    world[k] = verts[3 * (long long)ia + k];
-    world[3 + k] = verts[3 * (long long)ib + k];
-    world[6 + k] = verts[3 * (long long)ic + k];
-    t->a[k] = world[k] - o;
-    t->b[k] = world[3 + k] - o;
-    t->c[k] = world[6 + k] - o;
-  }
-  cross_ordered(t->b, ib, t->c, ic, t->cbc);
-  cross_ordered(t->c, ic, t->a, ia, t->cca);
-  cross_ordered(t->a, ia, t->b, ib, t->cab);
-  double u[3], v[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    u[k] = t->b[k] - t->a[k];
-    v[k] = t->c[k] - t->a[k];
-  }
-  cross3(u, v, t->n);
-  t->na = dot3(t->n, t->a);
-  return true;
-}
-
 // the pixel box of the triangle's projection, clamped to the image; false: nothing to test
 __device__ inline bool tri_box(const HitCam& cam, const double world[9], int H, int W, int* x0, int* y0, int* x1, int* y1) {
   double xmin = 1e300, xmax = -1e300, ymin = 1e300, ymax = -1e300;
@@ -178,18 +121,9 @@ __device__ inline bool tri_box(const HitCam& cam, const double world[9], int H, 
 // the exact test of pixel (x, y)'s ray against the triangle; merges into the key image on a hit
 __device__ inline void test_pixel(const HitCam& cam, const Tri& t, unsigned int face, int x, int y, int W,
                                   unsigned long long* __restrict__ keys) {
-  const float fx = (float)x, fy = (float)y;
-  const float p0 = (cam.kinv[0] * fx + cam.kinv[1] * fy) + cam.kinv[2] * 1.f;
-  const float p1 = (cam.kinv[3] * fx + cam.kinv[4] * fy) + cam.kinv[5] * 1.f;
-  const float p2 = (cam.kinv[6] * fx + cam.kinv[7] * fy) + cam.kinv[8] * 1.f;
-  // correctly rounded fp32 sqrt and division, through fp64 (53 >= 2 * 24 + 2 bits: the second rounding is innocuous);
-  // __fsqrt_rn is the native approximation unless the rounded OCML operations are compiled in
-  const float len = (float)__dsqrt_rn((double)((p0 * p0 + p1 * p1) + p2 * p2));
-  const float v0 = (float)((double)p0 / (double)len), v1 = (float)((double)p1 / (double)len), v2 = (float)((double)p2 / (double)len);
+  float v[3];
   double d[3];
-  d[0] = (double)((cam.rot[0] * v0 + cam.rot[1] * v1) + cam.rot[2] * v2);
-  d[1] = (double)((cam.rot[3] * v0 + cam.rot[4] * v1) + cam.rot[5] * v2);
-  d[2] = (double)((cam.rot[6] * v0 + cam.rot[7] * v1) + cam.rot[8] * v2);
+  pixel_ray(cam, x, y, v, d);
   const double e0 = dot3(d, t.cbc), e1 = dot3(d, t.cca), e2 = dot3(d, t.cab);
   const bool pos = e0 >= 0.0 && e1 >= 0.0 && e2 >= 0.0, neg = e0 <= 0.0 && e1 <= 0.0 && e2 <= 0.0;
   if (!(pos || neg) || (pos && neg)) return;             // NaN fails both; all zero passes both
@@ -220,7 +154,7 @@ __global__ void __launch_bounds__(kMcThreads) first_hit_small_kernel(const doubl
   }
   for (int y = y0; y <= y1; ++y)
     for (int x = x0; x <= x1; ++x)
-      if (mask[(long long)y * W + x] != 0) test_pixel(cam, t, (unsigned int)f, x, y, W, keys);
+      if (!mask || mask[(long long)y * W + x] != 0) test_pixel(cam, t, (unsigned int)f, x, y, W, keys);
 }
 
 __global__ void __launch_bounds__(kMcThreads) first_hit_big_kernel(const double* __restrict__ verts, const int* __restrict__ faces,
@@ -242,7 +176,7 @@ __global__ void __launch_bounds__(kMcThreads) first_hit_big_kernel(const double*
     const long long area = (long long)bw * (y1 - y0 + 1);
     for (long long j = threadIdx.x; j < area; j += kMcThreads) {
       const int y = y0 + (int)(j / bw), x = x0 + (int)(j % bw);
-      if (mask[(long long)y * W + x] != 0) test_pixel(cam, t, (unsigned int)f, x, y, W, keys);
+      if (!mask || mask[(long long)y * W + x] != 0) test_pixel(cam, t, (unsigned int)f, x, y, W, keys);
     }
   }
 }
@@ -367,10 +301,7 @@ hipError_t launch_first_hit(const double* verts, const int* faces, long long V, 
                             const float* org, const double* proj, const unsigned char* mask, int H, int W,
                             unsigned long long* keys, int* big_count, int* big_list, int* face_id, unsigned char* face_hit,
                             hipStream_t s) {
-  HitCam cam;
-  for (int i = 0; i < 9; ++i) cam.kinv[i] = kinv[i], cam.rot[i] = rot[i];
-  for (int i = 0; i < 3; ++i) cam.org[i] = org[i];
-  for (int i = 0; i < 12; ++i) cam.proj[i] = proj[i];
+  const HitCam cam = make_hit_cam(kinv, rot, org, proj);
   const long long n = (long long)H * W;
   hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)n * sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;

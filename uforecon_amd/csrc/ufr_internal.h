@@ -174,6 +174,8 @@ hipError_t launch_mask_dilate(const unsigned char* src, int H, int W, int k, con
                               unsigned char* dilated, unsigned char* mask, hipStream_t s);
 hipError_t launch_vertex_votes(const double* verts, long long V, const float* P, int NV, const unsigned char* masks, int H, int W,
                                int* votes, hipStream_t s);
+// (the one first hit of the tree: ufr_mesh_first_hit and ufr_raster_frames both come here; mask null = every pixel; the key
+// image is re-initialised by every call)
 hipError_t launch_first_hit(const double* verts, const int* faces, long long V, long long F, const float* kinv, const float* rot,
                             const float* org, const double* proj, const unsigned char* mask, int H, int W,
                             unsigned long long* keys, int* big_count, int* big_list, int* face_id, unsigned char* face_hit,
@@ -183,6 +185,14 @@ hipError_t launch_mark_pairs(const long long* keys, const long long* order, long
                              unsigned char* has_adj, int* parent, hipStream_t s);
 hipError_t launch_component_round(const int* pair_a, const int* pair_b, long long F, int* parent, int* changed, hipStream_t s);
 hipError_t launch_component_labels(const int* parent, const unsigned char* has_adj, long long F, int* labels, hipStream_t s);
+// raster.hip: mesh rendering -- vertex normals, shading of a first-hit face image, box downsampling (see the file header)
+hipError_t launch_raster_vertex_normals(const double* verts, const int* faces, long long V, long long F, const long long* slots,
+                                        const long long* runs, double* normals, hipStream_t s);
+hipError_t launch_raster_shade(const double* verts, const int* faces, long long V, long long F, const double* normals,
+                               const unsigned char* colors, const float* kinv, const float* rot, const float* org,
+                               const double* proj, const double* base, double ambient, const unsigned char* bg, const int* face_img,
+                               int H, int W, unsigned char* image, float* depth, int* face_out, float* normal_out, hipStream_t s);
+hipError_t launch_raster_downsample(const unsigned char* src, long long n, int H, int W, int sf, unsigned char* dst, hipStream_t s);
 // conv2d.hip: the plain 2-D convolutions of FeatureNet on channel-last tensors, epilogue fused (see the file header)
 struct Conv2dArgs {
   const float* in;      // [B][H][W][CIN] (the stem: planar [B][3][H][W])

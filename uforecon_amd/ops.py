@@ -1105,6 +1105,110 @@ def mesh_face_components(verts: torch.Tensor, faces: torch.Tensor, return_rounds
     return (labels, int(rounds.value)) if return_rounds else labels
 
 
+# ---- mesh rendering (csrc/raster.hip; uforecon_amd/render_trajectory.py strings these together)
+def raster_vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """ufr_raster_vertex_normals: area-weighted vertex normals, (V,3) float64 -- the normalised sum of (b - a) x (c - a) over the
+    faces that use the vertex, (0,0,0) for a vertex without faces or with a zero sum.  ``verts`` (V,3) CUDA float64, ``faces``
+    (F,3) CUDA int32.  The corner slots are sorted by vertex here (stable), so the sums do not depend on scheduling.  A face
+    index out of range raises.  One host synchronisation (the index check)."""
+    pv, pf, V, F = _mesh(verts, faces, "raster_vertex_normals")
+    dev = verts.device
+    normals = torch.zeros((V, 3), dtype=torch.float64, device=dev)
+    if V == 0 or F == 0:
+        return normals
+    if 3 * F >= 2 ** 31:
+        raise UfrError(f"raster_vertex_normals: {F} faces: (2^31 - 1) / 3 or more")
+    corner = faces.reshape(-1).to(torch.int64)
+    svert, slots = torch.sort(corner, stable=True)
+    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=dev)).contiguous()
+    _lib.check(_lib.load().ufr_raster_vertex_normals(pv, pf, V, F, slots.contiguous().data_ptr(), runs.data_ptr(), normals.data_ptr(),
+                                                     _stream()), "ufr_raster_vertex_normals")
+    return normals
+
+
+def raster_frames(verts: torch.Tensor, faces: torch.Tensor, k_inv, c2ws, H: int, W: int, normals: Optional[torch.Tensor] = None,
+                  colors: Optional[torch.Tensor] = None, base_color=(1.0, 1.0, 1.0), background=(255, 255, 255),
+                  ambient: float = 0.25, return_depth: bool = False, return_face_ids: bool = False,
+                  return_normals: bool = False, check_indices: bool = True):
+    """ufr_raster_frames: ``n`` shaded views of a mesh in one call (include/ufr.h states every rule).  ``verts`` (V,3) CUDA
+    float64, ``faces`` (F,3) CUDA int32; ``k_inv`` 3x3 and ``c2ws`` (n,4,4): host arrays, narrowed to float32, with the meaning
+    ``mesh_first_hit`` gives them; ``normals`` (V,3) CUDA float64 or None (flat shading); ``colors`` (V,3) CUDA uint8 or None
+    (``base_color``).  Returns a dict: ``image`` (n,H,W,3) uint8, and when asked ``depth`` (n,H,W) float32 z-depth (0: no hit),
+    ``face_id`` (n,H,W) int32 (-1: no hit), ``normal`` (n,H,W,3) float32 in camera coordinates, facing the camera.  One index
+    check (a host synchronisation) per call, none with ``check_indices=False`` (a caller that has checked the mesh already);
+    the frames themselves synchronise nowhere."""
+    import numpy as np
+
+    if check_indices:
+        pv, pf, V, F = _mesh(verts, faces, "raster_frames")
+    else:
+        pv, pf, V, F = _points64(verts, "verts"), _dev(faces, "faces", torch.int32), int(verts.shape[0]), int(faces.shape[0])
+        if faces.dim() != 2 or faces.shape[1] != 3:
+            raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
+    ki = np.ascontiguousarray(np.asarray(k_inv, np.float32))
+    cw = np.ascontiguousarray(np.asarray(c2ws, np.float32))
+    if ki.shape != (3, 3) or cw.ndim != 3 or cw.shape[1:] != (4, 4) or cw.shape[0] < 1:
+        raise UfrError(f"raster_frames: k_inv {ki.shape}, c2ws {cw.shape}: expected (3, 3) and (n, 4, 4) with n >= 1")
+    n, H, W = int(cw.shape[0]), int(H), int(W)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise UfrError(f"raster_frames: image {H}x{W} (H, W >= 1, H * W < 2^31)")
+    if not 0.0 <= float(ambient) <= 1.0:
+        raise UfrError(f"raster_frames: ambient {ambient} (must be 0 .. 1)")
+    base = np.ascontiguousarray(np.asarray(base_color, np.float32).reshape(-1))
+    bg = np.ascontiguousarray(np.asarray(background).reshape(-1))
+    if base.shape != (3,) or not ((base >= 0) & (base <= 1)).all():
+        raise UfrError(f"raster_frames: base_color {base_color!r} (three values in 0 .. 1)")
+    if bg.shape != (3,) or not ((bg >= 0) & (bg <= 255) & (bg == np.rint(bg))).all():
+        raise UfrError(f"raster_frames: background {background!r} (three integers in 0 .. 255)")
+    bg = np.ascontiguousarray(bg.astype(np.uint8))
+    pn = pc = None
+    if normals is not None:
+        pn = _points64(normals, "normals")
+        if normals.shape[0] != V:
+            raise UfrError(f"normals: expected shape ({V}, 3), got {tuple(normals.shape)}")
+    if colors is not None:
+        pc = _dev(colors, "colors", torch.uint8)
+        if tuple(colors.shape) != (V, 3):
+            raise UfrError(f"colors: expected shape ({V}, 3), got {tuple(colors.shape)}")
+    dev = verts.device
+    bgt = torch.from_numpy(bg).to(dev)
+    out = {"image": bgt.expand(n, H, W, 3).contiguous()}
+    if return_depth:
+        out["depth"] = torch.zeros((n, H, W), dtype=torch.float32, device=dev)
+    if return_face_ids:
+        out["face_id"] = torch.full((n, H, W), -1, dtype=torch.int32, device=dev)
+    if return_normals:
+        out["normal"] = torch.zeros((n, H, W, 3), dtype=torch.float32, device=dev)
+    if F == 0 or V == 0:
+        return out
+    lib = _lib.load()
+    nbytes = lib.ufr_raster_frames_workspace_bytes(F, H, W)
+    if nbytes == 0:
+        raise UfrError(f"raster_frames: F {F}, image {H}x{W} unsupported")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    fp, ptr = C.POINTER(C.c_float), lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
+    _lib.check(lib.ufr_raster_frames(pv, pf, V, F, pn, pc, ki.ctypes.data_as(fp), cw.ctypes.data_as(fp), n, H, W, base.ctypes.data_as(fp),
+                                     bg.ctypes.data_as(C.POINTER(C.c_uint8)), float(ambient), out["image"].data_ptr(), ptr("depth"),
+                                     ptr("face_id"), ptr("normal"), ws.data_ptr(), nbytes, _stream()), "ufr_raster_frames")
+    return out
+
+
+def raster_downsample(images: torch.Tensor, s: int) -> torch.Tensor:
+    """ufr_raster_downsample: (n,s*H,s*W,3) CUDA uint8 -> (n,H,W,3) uint8, the mean of every s x s block in integer arithmetic,
+    round half to even; ``s`` in 1..4 (1 copies).  Does not synchronise."""
+    p = _dev(images, "images", torch.uint8)
+    s = int(s)
+    if not 1 <= s <= 4:
+        raise UfrError(f"raster_downsample: s {s} (must be 1 .. 4)")
+    if images.dim() != 4 or images.shape[3] != 3 or images.shape[0] < 1 or images.shape[1] < s or images.shape[2] < s \
+            or images.shape[1] % s or images.shape[2] % s:
+        raise UfrError(f"images: expected shape (n, {s}*H, {s}*W, 3) with n, H, W >= 1, got {tuple(images.shape)}")
+    n, H, W = int(images.shape[0]), int(images.shape[1]) // s, int(images.shape[2]) // s
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=images.device)
+    _lib.check(_lib.load().ufr_raster_downsample(p, n, H, W, s, out.data_ptr(), _stream()), "ufr_raster_downsample")
+    return out
+
+
 CONV3D_S1, CONV3D_S2, CONV3D_T2 = 0, 1, 2
 
 

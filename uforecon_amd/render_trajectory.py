@@ -1,0 +1,319 @@
+"""Mesh fly-through on the GPU: the reference's render_trajectory_dtu.py and render_trajectory_open3d.py, which turn a
+reconstructed mesh into the 240-frame camera sweep of the reference's README, without Open3D, OpenGL or a display.  The camera
+path is numpy float64; every pixel is HIP (csrc/mesh_clean.hip's first hit, then csrc/raster.hip through
+``ops.raster_vertex_normals``, ``ops.raster_frames`` and ``ops.raster_downsample``); include/ufr.h states every rule.
+
+    python -m uforecon_amd.render_trajectory --mesh_dir OUT/mesh/final --root_dir DTU_TEST --out_dir OUT/rendering
+        [--scans ... --views 23 24 23 --num_views 240 --img_wh 800 640 --original_img_wh 1600 1200 --offset_dist 25
+         --supersample 2 --flat --color vertex|uniform --ambient A --format jpg|png --quality 90 --dump_poses DIR]
+
+reads ``<mesh_dir>/scan<N>.ply`` and ``<root_dir>/cameras/<view>_cam.txt`` and writes ``<out_dir>/scan<N>/render_<i>.jpg``.
+
+1. key poses as ``DtuFitSparse.load_scene`` builds ``all_render_w2cs_original``: ``c2w = inv(E)`` in float64, moved by
+   ``offset_dist`` along its own x axis; the path is ``interpolate_trajectory`` of the reference (scipy's ``Slerp`` for the
+   rotation, linear positions), restated here so that scipy is not needed at run time;
+2. intrinsics: the first view's K with row 0 scaled by ``img_w / original_w`` and row 1 by ``img_h / original_h``;
+3. per frame the first hit of every pixel's ray, then shading: a headlight, ``I = ambient + (1 - ambient) |N . d|``, two-sided
+   (marching-cubes meshes come with either winding), smooth (area-weighted vertex normals) or ``--flat``; white like the
+   reference's painted mesh, or the PLY's vertex colours (``--color vertex``);
+4. ``--supersample s`` renders at s x the size and box-filters down.
+
+Differences from the reference, all deliberate: the reference renders through an Open3D ``Visualizer`` window with a light set by
+``render.json`` (not in its tree); the shading here is this module's own rule, not a copy of that window's.  The reference holds
+the key poses in float32; here they stay float64 until the ray generator narrows them.  ``--dump_poses`` writes the Open3D
+pinhole-camera JSON of every frame (the fields the reference fills), so that the path can be replayed where Open3D exists.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+from .clean_mesh import ray_camera, read_cam_file
+from .dtu_eval import DTU_SCANS, read_ply
+
+VIEWS = [23, 24, 23]
+NUM_VIEWS = 240
+IMG_WH = [800, 640]
+ORIGINAL_IMG_WH = [1600, 1200]
+OFFSET_DIST = 25.0
+
+
+# ------------------------------------------------------------------ the camera path
+def _quat_from_matrix(R):
+    """unit quaternion (x, y, z, w) of a rotation matrix, from its largest of trace / diagonal entries (as scipy's from_matrix)"""
+    d = [R[0, 0], R[1, 1], R[2, 2], R[0, 0] + R[1, 1] + R[2, 2]]
+    c = int(np.argmax(d))
+    q = np.empty(4)
+    if c == 3:
+        q[0], q[1], q[2], q[3] = R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1], 1 + d[3]
+    else:
+        i, j, k = c, (c + 1) % 3, (c + 2) % 3
+        q[i] = 1 - d[3] + 2 * R[i, i]
+        q[j] = R[j, i] + R[i, j]
+        q[k] = R[k, i] + R[i, k]
+        q[3] = R[k, j] - R[j, k]
+    return q / np.sqrt(q @ q)
+
+
+def _quat_mul(p, q):
+    """p q, (x, y, z, w)"""
+    return np.array([p[3] * q[0] + q[3] * p[0] + (p[1] * q[2] - p[2] * q[1]),
+                     p[3] * q[1] + q[3] * p[1] + (p[2] * q[0] - p[0] * q[2]),
+                     p[3] * q[2] + q[3] * p[2] + (p[0] * q[1] - p[1] * q[0]),
+                     p[3] * q[3] - (p[0] * q[0] + p[1] * q[1] + p[2] * q[2])])
+
+
+def _rotvec_from_quat(q):
+    """log: the rotation vector of the shorter way round (w >= 0), by series below 1e-3 rad"""
+    if q[3] < 0:
+        q = -q
+    s = np.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2])
+    angle = 2 * np.arctan2(s, q[3])
+    if angle <= 1e-3:
+        a2 = angle * angle
+        scale = 2 + a2 / 12 + 7 * a2 * a2 / 2880
+    else:
+        scale = angle / np.sin(angle / 2)
+    return scale * q[:3]
+
+
+def _quat_from_rotvec(r):
+    """exp"""
+    angle = np.sqrt(r @ r)
+    if angle <= 1e-3:
+        a2 = angle * angle
+        scale = 0.5 - a2 / 48 + a2 * a2 / 3840
+    else:
+        scale = np.sin(angle / 2) / angle
+    return np.array([scale * r[0], scale * r[1], scale * r[2], np.cos(angle / 2)])
+
+
+def _matrix_from_quat(q):
+    x, y, z, w = q
+    x2, y2, z2, w2 = x * x, y * y, z * z, w * w
+    xy, zw, xz, yw, yz, xw = x * y, z * w, x * z, y * w, y * z, x * w
+    return np.array([[x2 - y2 - z2 + w2, 2 * (xy - zw), 2 * (xz + yw)],
+                     [2 * (xy + zw), -x2 + y2 - z2 + w2, 2 * (yz - xw)],
+                     [2 * (xz - yw), 2 * (yz + xw), -x2 - y2 + z2 + w2]])
+
+
+def interpolate_trajectory(w2cs, num_views: int = NUM_VIEWS):
+    """The reference's ``interpolate_trajectory`` (render_trajectory_dtu.py:57-77) in numpy float64: ``w2cs`` (K,4,4), K >= 2 key
+    cameras at times 0..K-1; frame i is at t = i / num_views * (K - 1) (the last key is never reached).  On the segment
+    k = floor(t), alpha = t - k the rotation is ``R_k exp(alpha log(R_k^-1 R_k+1))`` (scipy's ``Slerp``: the shorter way
+    round), the position linear between the two keys.  Returns (num_views,4,4) float64 camera-to-world matrices.  Equal
+    neighbouring keys and a first key equal to the last are fine."""
+    w2cs = np.asarray(w2cs, np.float64)
+    if w2cs.ndim != 3 or w2cs.shape[1:] != (4, 4) or len(w2cs) < 2:
+        raise ValueError(f"interpolate_trajectory: w2cs {w2cs.shape}: expected (K, 4, 4) with K >= 2")
+    num_views = int(num_views)
+    if num_views < 1:
+        raise ValueError(f"interpolate_trajectory: num_views {num_views} (must be >= 1)")
+    c2ws = np.linalg.inv(w2cs)
+    K = len(c2ws)
+    quats = [_quat_from_matrix(c[:3, :3]) for c in c2ws]
+    conj = np.array([-1.0, -1.0, -1.0, 1.0])
+    rotvecs = [_rotvec_from_quat(_quat_mul(quats[k] * conj, quats[k + 1])) for k in range(K - 1)]
+    out = np.empty((num_views, 4, 4))
+    for i in range(num_views):
+        t = float(i) / num_views * (K - 1)
+        k = min(int(np.floor(t)), K - 2)
+        alpha = t - k
+        c2w = np.eye(4)
+        c2w[:3, :3] = _matrix_from_quat(_quat_mul(quats[k], _quat_from_rotvec(alpha * rotvecs[k])))
+        c2w[:3, 3] = c2ws[k, :3, 3] + (c2ws[k + 1, :3, 3] - c2ws[k, :3, 3]) * alpha
+        out[i] = c2w
+    return out
+
+
+def key_poses(root_dir, views=VIEWS, offset_dist=OFFSET_DIST):
+    """(K 3x3 float32 of the first view, w2cs (len(views),4,4) float64): the key cameras as ``DtuFitSparse.load_scene`` builds
+    ``all_render_w2cs_original`` -- c2w = inv(E) in float64, moved by ``offset_dist`` along its own x axis."""
+    w2cs, K0 = [], None
+    for v in views:
+        K, E = read_cam_file(os.path.join(root_dir, "cameras/{:0>8}_cam.txt".format(v)))
+        if K0 is None:
+            K0 = K
+        c2w = np.linalg.inv(E.astype(np.float64))
+        c2w[:3, 3] += c2w[:3, 0] * offset_dist
+        w2cs.append(np.linalg.inv(c2w))
+    return K0, np.stack(w2cs)
+
+
+def scaled_intrinsics(K, img_wh=IMG_WH, original_img_wh=ORIGINAL_IMG_WH):
+    """K (float64) with row 0 multiplied by img_w / original_w and row 1 by img_h / original_h"""
+    K = np.asarray(K, np.float32).astype(np.float64)[:3, :3].copy()
+    K[0] *= img_wh[0] / original_img_wh[0]
+    K[1] *= img_wh[1] / original_img_wh[1]
+    return K
+
+
+def pinhole_json(K, c2w, H, W):
+    """The Open3D PinholeCameraParameters dict of one frame, the fields the reference fills: ``extrinsic`` = the w2c flattened
+    column-major, ``intrinsic.intrinsic_matrix`` column-major, ``width``, ``height``."""
+    w2c = np.linalg.inv(np.asarray(c2w, np.float64))
+    return {"class_name": "PinholeCameraParameters", "extrinsic": w2c.T.reshape(-1).tolist(),
+            "intrinsic": {"height": int(H), "intrinsic_matrix": np.asarray(K, np.float64)[:3, :3].T.reshape(-1).tolist(),
+                          "width": int(W)},
+            "version_major": 1, "version_minor": 0}
+
+
+def load_pinhole_json(path):
+    """(K 3x3, c2w 4x4, H, W) of a file ``pinhole_json`` wrote (the reference's ``load``)"""
+    with open(path) as f:
+        j = json.load(f)
+    w2c = np.array(j["extrinsic"], np.float64).reshape(4, 4).T
+    K = np.array(j["intrinsic"]["intrinsic_matrix"], np.float64).reshape(3, 3).T
+    return K, np.linalg.inv(w2c), int(j["intrinsic"]["height"]), int(j["intrinsic"]["width"])
+
+
+# ------------------------------------------------------------------ rendering
+def supersampled_intrinsics(K, s):
+    """K' = [[s, 0, (s-1)/2], [0, s, (s-1)/2], [0, 0, 1]] K: pixel centres are integers, so pixel x of the small image covers
+    the big image's s x - 1/2 + (1/2 .. s - 1/2), whose centres are s x + 0 .. s - 1"""
+    S = np.array([[s, 0, (s - 1) / 2], [0, s, (s - 1) / 2], [0, 0, 1]], np.float64)
+    return S @ np.asarray(K, np.float64)[:3, :3]
+
+
+def _frames_per_chunk(n, H, W, s, extra_bytes_per_pixel, device):
+    import torch
+
+    per_frame = (s * H) * (s * W) * 3 + H * W * (3 + extra_bytes_per_pixel)
+    free = torch.cuda.mem_get_info(device)[0] if torch.cuda.is_available() else 1 << 30
+    return max(1, min(n, int(free // 4 // per_frame)))   # a quarter of what is free: the allocator and the workspace need room
+
+
+def render_mesh(verts, faces, K, c2ws, H, W, colors=None, smooth=True, ambient=0.25, base_color=(1, 1, 1),
+                background=(255, 255, 255), supersample=1, return_depth=False, return_normals=False, return_face_ids=False,
+                device="cuda"):
+    """Shaded views of a mesh: uint8 (n,H,W,3) images as a numpy array.  ``verts`` (V,3) any float dtype, ``faces`` (F,3)
+    integers, ``K`` 3x3 intrinsics (normalised and inverted as ``clean_mesh.ray_camera`` does), ``c2ws`` (n,4,4) or (4,4)
+    camera-to-world matrices, ``colors`` (V,3) uint8 vertex colours or None (``base_color``, 0..1).  ``smooth``: area-weighted
+    vertex normals, else the face normal.  ``supersample`` s in 1..4 renders at s x the size and box-filters down.  With
+    ``return_depth`` / ``return_normals`` / ``return_face_ids`` a tuple: the images, then float32 (n,H,W) z-depth (0: no hit),
+    float32 (n,H,W,3) camera-space normals facing the camera, int32 (n,H,W) face ids (-1: no hit), in that order -- at
+    ``supersample=1`` only.  The frames are rendered in chunks sized from free device memory; one host synchronisation per
+    chunk, none per frame."""
+    import torch
+
+    from . import ops
+    from ._lib import UfrError
+
+    verts = np.asarray(verts, np.float64).reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 3)
+    c2ws = np.asarray(c2ws, np.float64)
+    if c2ws.ndim == 2:
+        c2ws = c2ws[None]
+    s, H, W = int(supersample), int(H), int(W)
+    extras = [k for k, on in (("depth", return_depth), ("normal", return_normals), ("face_id", return_face_ids)) if on]
+    if not 1 <= s <= 4:
+        raise UfrError(f"render_mesh: supersample {supersample} (must be 1 .. 4)")
+    if extras and s != 1:
+        raise UfrError("render_mesh: depth, normal and face-id maps are only available at supersample=1")
+    if c2ws.ndim != 3 or c2ws.shape[1:] != (4, 4) or len(c2ws) < 1:
+        raise UfrError(f"render_mesh: c2ws {c2ws.shape}: expected (n, 4, 4) with n >= 1")
+    if H < 1 or W < 1:
+        raise UfrError(f"render_mesh: image {H}x{W} (H and W must be >= 1)")
+    V, F = len(verts), len(faces)
+    if F and (V == 0 or faces.min() < 0 or faces.max() >= V):
+        raise UfrError(f"render_mesh: face indices span {faces.min()}..{faces.max()}, the mesh has {V} vertices")
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.shape != (V, 3) or colors.dtype != np.uint8:
+            raise UfrError(f"render_mesh: colors {colors.shape} {colors.dtype}: expected ({V}, 3) uint8")
+    dev = torch.device(device)
+    tv = torch.from_numpy(np.ascontiguousarray(verts)).to(dev)
+    tf = torch.from_numpy(np.ascontiguousarray(faces.astype(np.int32))).to(dev)
+    tc = None if colors is None else torch.from_numpy(np.ascontiguousarray(colors)).to(dev)
+    tn = ops.raster_vertex_normals(tv, tf) if smooth and F else None
+    k_inv = ray_camera(supersampled_intrinsics(K, s).astype(np.float32), np.eye(4, dtype=np.float32))[0]
+    n = len(c2ws)
+    chunk = _frames_per_chunk(n, H, W, s, 4 * return_depth + 12 * return_normals + 4 * return_face_ids, dev)
+    out = {k: [] for k in ["image"] + extras}
+    for i in range(0, n, chunk):
+        r = ops.raster_frames(tv, tf, k_inv, c2ws[i:i + chunk], s * H, s * W, normals=tn, colors=tc, base_color=base_color,
+                              background=background, ambient=ambient, return_depth=return_depth,
+                              return_face_ids=return_face_ids, return_normals=return_normals, check_indices=False)
+        if s > 1:
+            r["image"] = ops.raster_downsample(r["image"], s)
+        for k in out:
+            out[k].append(r[k].cpu().numpy())
+    res = [np.concatenate(out[k]) for k in ["image"] + extras]
+    return res[0] if not extras else tuple(res)
+
+
+# ------------------------------------------------------------------ the command line
+def make_parser():
+    """The reference's constants (render_trajectory_dtu.py:93-107, 134) as defaults."""
+    parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    parser.add_argument("--mesh_dir", type=str, default="./outputs/mesh/final", help="directory of scan<N>.ply")
+    parser.add_argument("--root_dir", type=str, default="./dtu_test", help="dataset (cameras/<view>_cam.txt)")
+    parser.add_argument("--out_dir", type=str, default="./rendering", help="frames go to <out_dir>/scan<N>/")
+    parser.add_argument("--scans", type=int, nargs="+", default=DTU_SCANS, help="scan numbers (default: the 15 DTU test scans)")
+    parser.add_argument("--views", type=int, nargs="+", default=VIEWS, help="key views of the path (the reference: 23 24 23)")
+    parser.add_argument("--num_views", type=int, default=NUM_VIEWS, help="frames of the path")
+    parser.add_argument("--img_wh", type=int, nargs=2, default=IMG_WH, help="rendered width and height")
+    parser.add_argument("--original_img_wh", type=int, nargs=2, default=ORIGINAL_IMG_WH, help="size the camera files' K refers to")
+    parser.add_argument("--offset_dist", type=float, default=OFFSET_DIST, help="sideways shift of the key cameras (mm)")
+    parser.add_argument("--supersample", type=int, default=1, choices=[1, 2, 3, 4])
+    parser.add_argument("--flat", action="store_true", help="face normals instead of smooth vertex normals")
+    parser.add_argument("--color", choices=["vertex", "uniform"], default="uniform", help="vertex: the PLY's red/green/blue")
+    parser.add_argument("--ambient", type=float, default=0.25)
+    parser.add_argument("--format", choices=["jpg", "png"], default="jpg")
+    parser.add_argument("--quality", type=int, default=90, help="JPEG quality")
+    parser.add_argument("--dump_poses", type=str, default=None, help="directory for Open3D pinhole-camera JSON (tmp<i>.json)")
+    return parser
+
+
+def render_scan(mesh_path, root_dir, out_dir, views=VIEWS, num_views=NUM_VIEWS, img_wh=IMG_WH, original_img_wh=ORIGINAL_IMG_WH,
+                offset_dist=OFFSET_DIST, supersample=1, flat=False, color="uniform", ambient=0.25, fmt="jpg", quality=90,
+                dump_poses=None):
+    """One scan: the frames ``<out_dir>/render_<i>.<fmt>`` of ``mesh_path`` along the path through ``views``.  Returns the
+    (num_views,4,4) camera-to-world matrices."""
+    from PIL import Image
+
+    verts, faces, colors = read_ply(mesh_path, with_colors=True)
+    if faces is None:
+        faces = np.zeros((0, 3), np.int32)
+    if len(views) < 2:
+        raise ValueError(f"render_scan: views {views}: at least two key views are needed")
+    K0, w2cs = key_poses(root_dir, views, offset_dist)
+    c2ws = interpolate_trajectory(w2cs, num_views)
+    K = scaled_intrinsics(K0, img_wh, original_img_wh)
+    W, H = int(img_wh[0]), int(img_wh[1])
+    if dump_poses:
+        os.makedirs(dump_poses, exist_ok=True)
+        for i, c2w in enumerate(c2ws):
+            with open(os.path.join(dump_poses, "tmp%d.json" % i), "w") as f:
+                json.dump(pinhole_json(K, c2w, H, W), f, indent=4)
+    images = render_mesh(verts, faces, K, c2ws, H, W, colors=colors if color == "vertex" else None, smooth=not flat,
+                         ambient=ambient, supersample=supersample)
+    os.makedirs(out_dir, exist_ok=True)
+    for i, img in enumerate(images):
+        path = os.path.join(out_dir, "render_%d.%s" % (i, fmt))
+        if fmt == "jpg":
+            Image.fromarray(img).save(path, quality=quality)
+        else:
+            Image.fromarray(img).save(path)
+    return c2ws
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    for scan in args.scans:
+        mesh = os.path.join(args.mesh_dir, "scan%d.ply" % scan)
+        if not os.path.exists(mesh):
+            print("scan%d: no mesh at %s" % (scan, mesh))
+            continue
+        print("rendering scan%d" % scan)
+        render_scan(mesh, args.root_dir, os.path.join(args.out_dir, "scan%d" % scan), args.views, args.num_views, args.img_wh,
+                    args.original_img_wh, args.offset_dist, args.supersample, args.flat, args.color, args.ambient, args.format,
+                    args.quality, args.dump_poses)      # the cameras are the dataset's, not the scan's: one set of poses
+
+
+if __name__ == "__main__":
+    sys.exit(main())
