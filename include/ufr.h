@@ -748,6 +748,31 @@ int ufr_raster_frames(const double* verts, const int32_t* faces, int64_t V, int6
                       void* workspace, size_t workspace_bytes, ufr_stream stream);
 int ufr_raster_downsample(const uint8_t* src, int32_t n, int32_t H, int32_t W, int32_t s, uint8_t* dst, ufr_stream stream);
 
+/* ---- a scan loader's per-pixel work (ABI 507, additive) -----------------------------------------------------
+ * What DtuFitSparse (code1/dataset/dtu_test_sparse.py:247-298, 412-429) computes per pixel; uforecon_amd/dtu_scan.py does the
+ * 4x4 camera arithmetic on the host and calls these two.  Neither synchronises.
+ * ufr_image_resize_u8: src = n interleaved RGB images (n,Hs,Ws,3) uint8, device -> dst (n,3,Ho,Wo) fp32 planes, device:
+ *   each image resized to H x W, cropped, divided by 255.  clip4: HOST int32[4] = columns dropped on the left, rows on the
+ *   top, columns on the right, rows on the bottom (the reference's clip_wh doubled), nullable = none; Ho = H - top - bottom,
+ *   Wo = W - left - right.  The resize is OpenCV's resize() for 8-bit images with INTER_LINEAR, restated (no OpenCV was
+ *   compared): for output index d of an axis with scale = (double)source size / size,
+ *     f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s, weights rint((1.f - f) * 2048.f) and rint(f * 2048.f);
+ *     along x a tap outside the row moves s to the edge and sets f = 0; along y the rows s and s + 1 are clamped to the
+ *     image and the weights stay;  row = S[s] * a0 + S[s + 1] * a1 in int32;
+ *     value = (((b0 * (row0 >> 4)) >> 16) + ((b1 * (row1 >> 4)) >> 16) + 2) >> 2;
+ *   when Hs == 2 H and Ws == 2 W the value is the box mean (s00 + s01 + s10 + s11 + 2) >> 2 instead.  Each output is
+ *   (float)((double)value / 255.0).  Hs * Ws and H * W < 2^31, n * Ho * Wo * 3 < 2^38.
+ * ufr_pixel_rays: dir (3,H*W) fp32, device = unit vectors through the pixel centres of the normalised grid.  m_inv: HOST
+ *   float[16], row-major 4x4; origin: HOST float[3], nullable = 0.  Per pixel (x, y), in double:
+ *     p = (x * 2 / (W - 1) - 1, y * 2 / (H - 1) - 1, 1, 1), v = (m_inv p)[:3] - origin, dir[:, y * W + x] = (float)(v / |v|).
+ *   With m_inv = ref_pose_inv and origin = ray_o this is the batch's ray_d; with the inverse of the normalised intrinsics
+ *   and no origin it is cam_ray_d.  H, W >= 2 (the grid divides by H - 1 and W - 1), H * W < 2^31.
+ * Every argument error (null src, dst, m_inv or dir, a size < 1, H or W < 2 for the rays, a negative clip or one that leaves
+ * nothing) is UFR_ERR_ARG with the reason in the thread's last-error text.                                            */
+int ufr_image_resize_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* clip4, float* dst,
+                        ufr_stream stream);
+int ufr_pixel_rays(const float* m_inv, const float* origin, int32_t H, int32_t W, float* dir, ufr_stream stream);
+
 /* Pixel-wise view weights of the first cascade stage and the weighted aggregate (DepthNet.forward,
  * code1/encoder_utils/fmt/TransMVSNet.py:80-97 with PixelwiseNet :23-41), one pass over the similarity volume:
  *   view_weights[i] = max_d sigmoid(conv2(relu(bn1(conv1(relu(bn0(conv0(similarity[i]))))))))      (1x1x1 convolutions)

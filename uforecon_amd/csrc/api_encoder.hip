@@ -1,5 +1,6 @@
 // extern "C" surface of libufr.so (include/ufr.h), part 5 of 6: the encoder -- correlation volumes and view weights, the
-// 3-D convolutions of the frustum U-Nets, the 2-D and deformable convolutions of the feature backbone, the FMT layer.
+// 3-D convolutions of the frustum U-Nets, the 2-D and deformable convolutions of the feature backbone, the FMT layer, and
+// what a scan loader feeds them (image planes from 8-bit pictures, the per-pixel ray tables).
 #include "api_common.h"
 
 using namespace ufr;
@@ -251,6 +252,38 @@ int ufr_fmt_layer(const ufr_fmt_layer_weights* w, const float* x, const float* s
   UFR_REQUIRE(out != x && out != src, "ufr_fmt_layer: out must not alias an input");
   hipStream_t s = static_cast<hipStream_t>(stream);
   UFR_TIMED("fmt_layer", s, launch_fmt_layer(fw, x, src, N, T, S, out, static_cast<float*>(workspace), s));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ the encoder's inputs: image planes and ray tables
+int ufr_image_resize_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* clip4, float* dst,
+                        ufr_stream stream) {
+  const char* who = "ufr_image_resize_u8";
+  UFR_REQUIRE(src && dst, "%s: null argument", who);
+  UFR_REQUIRE(n >= 1 && Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1, "%s: n %d, source %dx%d, resized %dx%d (each must be >= 1)", who, n, Hs,
+              Ws, H, W);
+  UFR_REQUIRE((long long)Hs * Ws < (1ll << 31) && (long long)H * W < (1ll << 31), "%s: an image of %dx%d or %dx%d has 2^31 pixels or more",
+              who, Hs, Ws, H, W);
+  int clip[4] = {0, 0, 0, 0};   // left, top, right, bottom
+  if (clip4) memcpy(clip, clip4, sizeof(clip));
+  UFR_REQUIRE(clip[0] >= 0 && clip[1] >= 0 && clip[2] >= 0 && clip[3] >= 0, "%s: clip %d %d %d %d (each must be >= 0)", who, clip[0],
+              clip[1], clip[2], clip[3]);
+  const long long Wo = (long long)W - clip[0] - clip[2], Ho = (long long)H - clip[1] - clip[3];
+  UFR_REQUIRE(Wo >= 1 && Ho >= 1, "%s: clip %d %d %d %d leaves nothing of %dx%d", who, clip[0], clip[1], clip[2], clip[3], H, W);
+  UFR_REQUIRE((long long)n * Ho * Wo * 3 < (1ll << 38) && (long long)n * Hs * Ws * 3 < (1ll << 40),
+              "%s: %d images of %dx%d from %dx%d are too many bytes", who, n, H, W, Hs, Ws);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("image_resize_u8", s, launch_image_resize_u8(src, n, Hs, Ws, H, W, clip[0], clip[1], (int)Ho, (int)Wo, dst, s));
+  return UFR_OK;
+}
+
+int ufr_pixel_rays(const float* m_inv, const float* origin, int32_t H, int32_t W, float* dir, ufr_stream stream) {
+  const char* who = "ufr_pixel_rays";
+  UFR_REQUIRE(m_inv && dir, "%s: null argument", who);
+  UFR_REQUIRE(H >= 2 && W >= 2, "%s: image %dx%d (H and W must be >= 2: the pixel grid divides by H - 1 and W - 1)", who, H, W);
+  UFR_REQUIRE((long long)H * W < (1ll << 31), "%s: image %dx%d has 2^31 pixels or more", who, H, W);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("pixel_rays", s, launch_pixel_rays(m_inv, origin, H, W, dir, s));
   return UFR_OK;
 }
 

@@ -193,6 +193,10 @@ hipError_t launch_raster_shade(const double* verts, const int* faces, long long 
                                const double* proj, const double* base, double ambient, const unsigned char* bg, const int* face_img,
                                int H, int W, unsigned char* image, float* depth, int* face_out, float* normal_out, hipStream_t s);
 hipError_t launch_raster_downsample(const unsigned char* src, long long n, int H, int W, int sf, unsigned char* dst, hipStream_t s);
+// frame_input.hip: a scan loader's per-pixel work -- 8-bit images to resized, cropped float planes; ray tables (see the file header)
+hipError_t launch_image_resize_u8(const unsigned char* src, long long n, int Hs, int Ws, int H, int W, int x0, int y0, int Ho, int Wo,
+                                  float* dst, hipStream_t s);
+hipError_t launch_pixel_rays(const float* m_inv, const float* origin, int H, int W, float* dir, hipStream_t s);
 // conv2d.hip: the plain 2-D convolutions of FeatureNet on channel-last tensors, epilogue fused (see the file header)
 struct Conv2dArgs {
   const float* in;      // [B][H][W][CIN] (the stem: planar [B][3][H][W])

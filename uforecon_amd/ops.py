@@ -1209,6 +1209,52 @@ def raster_downsample(images: torch.Tensor, s: int) -> torch.Tensor:
     return out
 
 
+# ---- a scan loader's per-pixel work (csrc/frame_input.hip; uforecon_amd/dtu_scan.py is the caller)
+def image_resize_u8(images: torch.Tensor, H: int, W: int, clip=(0, 0, 0, 0)) -> torch.Tensor:
+    """ufr_image_resize_u8: (n,Hs,Ws,3) CUDA uint8 RGB -> (n,3,Ho,Wo) float32 planes in [0,1]: every image resized to ``H`` x
+    ``W`` with OpenCV's 8-bit bilinear rule as include/ufr.h restates it (the 2x2 box mean when both factors are exactly 2),
+    cropped by ``clip`` = (left, top, right, bottom) and divided by 255.  Does not synchronise."""
+    p = _dev(images, "images", torch.uint8)
+    if images.dim() != 4 or images.shape[3] != 3:
+        raise UfrError(f"images: expected shape (n, Hs, Ws, 3), got {tuple(images.shape)}")
+    clip = [int(c) for c in clip]
+    if len(clip) != 4:
+        raise UfrError(f"image_resize_u8: clip {clip!r} (left, top, right, bottom)")
+    n, Hs, Ws = (int(s) for s in images.shape[:3])
+    H, W = int(H), int(W)
+    Ho, Wo = H - clip[1] - clip[3], W - clip[0] - clip[2]
+    out = torch.empty((n, 3, max(Ho, 0), max(Wo, 0)), dtype=torch.float32, device=images.device)
+    _lib.check(_lib.load().ufr_image_resize_u8(p, n, Hs, Ws, H, W, (C.c_int32 * 4)(*clip), out.data_ptr(), _stream()),
+               "ufr_image_resize_u8")
+    return out
+
+
+def pixel_rays(m_inv, H: int, W: int, origin=None, device="cuda") -> torch.Tensor:
+    """ufr_pixel_rays: (3,H*W) float32 unit vectors on ``device``; ``m_inv`` 4x4 and ``origin`` (3 values or None): host
+    arrays, narrowed to float32.  Per pixel, in float64: p = (2x/(W-1) - 1, 2y/(H-1) - 1, 1, 1), v = (m_inv p)[:3] - origin,
+    v / |v|.  Does not synchronise."""
+    import numpy as np
+
+    m = np.ascontiguousarray(np.asarray(m_inv, np.float32))
+    if m.shape != (4, 4):
+        raise UfrError(f"pixel_rays: m_inv {m.shape}: expected (4, 4)")
+    fp = C.POINTER(C.c_float)
+    po = None
+    if origin is not None:
+        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(-1))
+        if o.shape != (3,):
+            raise UfrError(f"pixel_rays: origin {origin!r} (three values)")
+        po = o.ctypes.data_as(fp)
+    H, W = int(H), int(W)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise UfrError(f"pixel_rays: device {device} (must be a GPU; uforecon_amd.dtu_scan has the host form)")
+    with torch.cuda.device(device):
+        out = torch.empty((3, max(H, 0) * max(W, 0)), dtype=torch.float32, device=device)
+        _lib.check(_lib.load().ufr_pixel_rays(m.ctypes.data_as(fp), po, H, W, out.data_ptr(), _stream()), "ufr_pixel_rays")
+    return out
+
+
 CONV3D_S1, CONV3D_S2, CONV3D_T2 = 0, 1, 2
 
 
