@@ -351,6 +351,27 @@ def test_sample_mesh_equals_restatement_on_marching_cubes_meshes():
         assert got.shape == want.shape and np.array_equal(got, want)
 
 
+def _jittered_grid(n, seed):
+    """an n x n planar grid at unit spacing, every coordinate jittered by up to 0.2, two triangles per cell in shuffled order"""
+    rng = np.random.default_rng(seed)
+    i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    verts = np.stack([i, j, np.zeros_like(i)], -1).reshape(-1, 3) + rng.uniform(-0.2, 0.2, (n * n, 3))
+    a = (i[:-1, :-1] * n + j[:-1, :-1]).reshape(-1)
+    faces = np.concatenate([np.stack([a, a + n, a + 1], 1), np.stack([a + 1, a + n, a + n + 1], 1)])
+    return verts, faces[rng.permutation(len(faces))].astype(np.int32)
+
+
+@pytest.mark.gpu
+def test_sample_mesh_equals_restatement_past_1024_blocks():
+    """more blocks than the totals scan has threads: every scan thread sums several block totals, the last ones none"""
+    verts, faces = _jittered_grid(364, 5)
+    assert len(faces) == 263_538 and -(-len(faces) // 256) > 1024
+    want, info = R.sample_mesh(verts, faces, 0.3, return_counts=True)
+    assert info["per_triangle"].min() == 0 and info["per_triangle"].max() >= 8, info["per_triangle"].max()
+    got = gpu_sample(verts, faces, 0.3)
+    assert got.shape == want.shape and np.array_equal(got, want)
+
+
 @pytest.mark.gpu
 def test_sample_mesh_equals_restatement_on_two_million_points():
     verts, faces = _mc_mesh(96, 40.0, 2.3)

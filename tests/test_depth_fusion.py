@@ -321,7 +321,8 @@ def _points_case(h, w, mode, seed):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("h,w,mode", [(23, 31, "all"), (23, 31, "none"), (70, 90, "random"), (1, 1, "all"), (1, 257, "random")])
+@pytest.mark.parametrize("h,w,mode", [(23, 31, "all"), (23, 31, "none"), (70, 90, "random"), (1, 1, "all"), (1, 257, "random"),
+                                      (512, 512, "random"), (513, 512, "random"), (1, 262400, "random")])   # 1024, 1026, 1025 blocks
 def test_points_are_the_row_major_selection(h, w, mode):
     import torch
 

@@ -9,6 +9,13 @@ using namespace ufr::api;
 
 namespace {
 
+// the counts a scan left in a workspace, on the host: the one synchronisation of a count / emit pair
+int read_counts(long long* host, const long long* dev, int n, hipStream_t s) {
+  UFR_HIP(hipMemcpyAsync(host, dev, n * sizeof(long long), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  return UFR_OK;
+}
+
 // ---- marching cubes: [tile sums int32 x2 | tile offsets int64 x2 | totals int64 x2 | index volume int32 per voxel]
 struct McWs { int *tile_counts, *index; long long *tile_off, *totals; };
 McWs carve_mcubes(Carver& c, const int32_t* dim) {
@@ -198,8 +205,7 @@ int ufr_marching_cubes_count(const float* vol, const int32_t* dim, float level, 
   UFR_TIMED("mcubes_count", s, launch_mcubes_count(vol, dim, level, w.tile_counts, s));
   UFR_TIMED("mcubes_scan", s, launch_mcubes_scan(w.tile_counts, mcubes_tiles(dim), w.tile_off, w.totals, s));
   long long tot[2] = {0, 0};
-  UFR_HIP(hipMemcpyAsync(tot, w.totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-  UFR_HIP(hipStreamSynchronize(s));
+  UFR_CHECK(read_counts(tot, w.totals, 2, s));
   UFR_REQUIRE(tot[0] < (1ll << 31) && tot[1] < (1ll << 31), "ufr_marching_cubes_count: %lld vertices, %lld faces: 2^31 or more",
               tot[0], tot[1]);
   counts_host[0] = (int32_t)tot[0];
@@ -243,8 +249,7 @@ int ufr_mesh_sample_count(const double* verts, const int32_t* faces, int64_t V, 
   UFR_TIMED("mesh_sample_count", s, launch_mesh_sample_count(verts, faces, V, F, density, w.tri_off, w.block_tot, s));
   UFR_TIMED("mesh_sample_scan", s, launch_mesh_sample_scan(w.block_tot, chamfer_blocks(F), w.block_off, w.total, s));
   long long tot = 0;
-  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
-  UFR_HIP(hipStreamSynchronize(s));
+  UFR_CHECK(read_counts(&tot, w.total, 1, s));
   *total_host = (int64_t)tot;
   return UFR_OK;
 }
@@ -358,8 +363,7 @@ int ufr_depth_points_count(const uint8_t* mask, int32_t H, int32_t W, void* work
   hipStream_t s = static_cast<hipStream_t>(stream);
   UFR_TIMED("depth_points_count", s, launch_depth_points_count(mask, (long long)H * W, w.block_tot, w.block_off, w.total, s));
   long long tot = 0;
-  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
-  UFR_HIP(hipStreamSynchronize(s));
+  UFR_CHECK(read_counts(&tot, w.total, 1, s));
   *n_host = (int64_t)tot;
   return UFR_OK;
 }
@@ -375,8 +379,7 @@ int ufr_depth_points_emit(const uint8_t* mask, const double* depth_avg, const ui
   UFR_REQUIRE(capacity == 0 || (xyz && rgb), "%s: null argument (xyz / rgb with capacity %lld)", who, (long long)capacity);
   hipStream_t s = static_cast<hipStream_t>(stream);
   long long tot = 0;
-  UFR_HIP(hipMemcpyAsync(&tot, w.total, sizeof(tot), hipMemcpyDeviceToHost, s));
-  UFR_HIP(hipStreamSynchronize(s));
+  UFR_CHECK(read_counts(&tot, w.total, 1, s));
   UFR_REQUIRE(tot >= 0 && tot <= (long long)H * W, "%s: the workspace holds no count (call ufr_depth_points_count first)", who);
   UFR_REQUIRE(capacity >= tot, "%s: capacity %lld is smaller than the %lld points counted", who, (long long)capacity, tot);
   if (tot == 0) return UFR_OK;

@@ -3,8 +3,8 @@
 //
 //   mesh_sample_count / _scan / _emit   points on every triangle at the given density (dtu_eval.py:68-91): one thread per
 //          triangle counts its samples (the count of a row i is found in O(1) from the monotone test a + b < 1, then
-//          corrected with that very test), a block scan + one scan block give every triangle its offset, and the same
-//          thread emits its points in (i, j) order.  The count / scan / emit shape of mcubes.hip.
+//          corrected with that very test), the scans of compact.h give every triangle its offset, and the same thread
+//          emits its points in (i, j) order.
 //   points_cell_keys   Morton key (21 bits per axis) of the grid cell of every point; the caller sorts by it.
 //   thin_round   one round of the thinning fixpoint (dtu_eval.py:105-115): an undecided point looks at the earlier points
 //          within r in its 27 cells; removed if one of them is kept, kept if all of them are removed.  A decision reads only
@@ -18,6 +18,7 @@
 //          the stack is bounded by 7 x 21 + 1 entries, so the walk is finite whatever the data.  Block sums of the
 //          distances below max_dist, then one summing block: no float atomics, the mean is the same run after run.
 // Every output store is guarded by the caller's capacity; point and triangle indices are 64-bit.
+#include "compact.h"
 #include "ufr_internal.h"
 
 #pragma clang fp contract(off)
@@ -26,7 +27,6 @@ namespace ufr {
 namespace {
 
 constexpr int kChThreads = 256;
-constexpr int kChScanThreads = 1024;
 constexpr int kKeyBits = 21;                       // per axis
 constexpr long long kMaxCell = (1ll << kKeyBits) - 1;
 
@@ -119,27 +119,11 @@ __device__ inline long long row_count(double a, double n2) {
   return c;
 }
 
-// block-wide exclusive scan over kChThreads threads; *tot = the block sum.  Ends with a barrier (lds reusable).
-__device__ inline long long block_scan(long long v, long long* lds, long long* tot) {
-  lds[threadIdx.x] = v;
-  __syncthreads();
-  for (int d = 1; d < kChThreads; d <<= 1) {
-    const long long u = threadIdx.x >= (unsigned)d ? lds[threadIdx.x - d] : 0;
-    __syncthreads();
-    lds[threadIdx.x] += u;
-    __syncthreads();
-  }
-  const long long incl = lds[threadIdx.x];
-  *tot = lds[kChThreads - 1];
-  __syncthreads();
-  return incl - v;
-}
-
 __global__ void __launch_bounds__(kChThreads) mesh_sample_count_kernel(const double* __restrict__ verts,
                                                                         const int* __restrict__ faces, long long V, long long F,
                                                                         double density, long long* __restrict__ tri_off,
                                                                         long long* __restrict__ block_tot) {
-  __shared__ long long lds[kChThreads];
+  __shared__ long long lds[kChThreads / 64];
   const long long t = (long long)blockIdx.x * kChThreads + threadIdx.x;
   long long cnt = 0;
   Tri s;
@@ -148,34 +132,9 @@ __global__ void __launch_bounds__(kChThreads) mesh_sample_count_kernel(const dou
     for (long long i = 0; i <= rows; ++i) cnt += row_count(((double)i + 0.5) / s.n1, s.n2);
   }
   long long tot;
-  const long long pre = block_scan(cnt, lds, &tot);
+  const long long pre = block_scan_excl<long long, kChThreads>(cnt, lds, &tot);
   if (t < F) tri_off[t] = pre;
   if (threadIdx.x == 0) block_tot[blockIdx.x] = tot;
-}
-
-// one block: block_off = exclusive prefix of block_tot, *total = the sum
-__global__ void __launch_bounds__(kChScanThreads) mesh_sample_scan_kernel(const long long* __restrict__ block_tot, long long n_blocks,
-                                                                           long long* __restrict__ block_off,
-                                                                           long long* __restrict__ total) {
-  __shared__ long long sa[kChScanThreads];
-  const long long per = (n_blocks + kChScanThreads - 1) / kChScanThreads;
-  const long long t0 = min((long long)threadIdx.x * per, n_blocks), t1 = min(t0 + per, n_blocks);
-  long long a = 0;
-  for (long long t = t0; t < t1; ++t) a += block_tot[t];
-  sa[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 1; d < kChScanThreads; d <<= 1) {
-    const long long u = threadIdx.x >= (unsigned)d ? sa[threadIdx.x - d] : 0;
-    __syncthreads();
-    sa[threadIdx.x] += u;
-    __syncthreads();
-  }
-  long long o = sa[threadIdx.x] - a;
-  for (long long t = t0; t < t1; ++t) {
-    block_off[t] = o;
-    o += block_tot[t];
-  }
-  if (threadIdx.x == kChScanThreads - 1) *total = sa[threadIdx.x];
 }
 
 __global__ void __launch_bounds__(kChThreads) mesh_sample_emit_kernel(const double* __restrict__ verts,
@@ -336,12 +295,12 @@ __global__ void __launch_bounds__(kChThreads) nn_dist_kernel(const double* __res
 }
 
 // one block: mean_out[0] = sum of the block sums, mean_out[1] = the count, in a fixed order
-__global__ void __launch_bounds__(kChScanThreads) nn_sum_kernel(const double* __restrict__ block_sum,
-                                                                 const long long* __restrict__ block_cnt, long long n_blocks,
-                                                                 double* __restrict__ mean_out) {
-  __shared__ double ss[kChScanThreads];
-  __shared__ long long sc[kChScanThreads];
-  const long long per = (n_blocks + kChScanThreads - 1) / kChScanThreads;
+__global__ void __launch_bounds__(kScanThreads) nn_sum_kernel(const double* __restrict__ block_sum,
+                                                               const long long* __restrict__ block_cnt, long long n_blocks,
+                                                               double* __restrict__ mean_out) {
+  __shared__ double ss[kScanThreads];
+  __shared__ long long sc[kScanThreads];
+  const long long per = (n_blocks + kScanThreads - 1) / kScanThreads;
   const long long t0 = min((long long)threadIdx.x * per, n_blocks), t1 = min(t0 + per, n_blocks);
   double s = 0.0;
   long long c = 0;
@@ -349,7 +308,7 @@ __global__ void __launch_bounds__(kChScanThreads) nn_sum_kernel(const double* __
   ss[threadIdx.x] = s;
   sc[threadIdx.x] = c;
   __syncthreads();
-  for (int d = kChScanThreads / 2; d > 0; d >>= 1) {
+  for (int d = kScanThreads / 2; d > 0; d >>= 1) {
     if (threadIdx.x < (unsigned)d) {
       ss[threadIdx.x] += ss[threadIdx.x + d];
       sc[threadIdx.x] += sc[threadIdx.x + d];
@@ -362,43 +321,40 @@ __global__ void __launch_bounds__(kChScanThreads) nn_sum_kernel(const double* __
   }
 }
 
-inline unsigned blocks_of(long long n) { return (unsigned)((n + kChThreads - 1) / kChThreads); }
-
 }  // namespace
 
 long long chamfer_blocks(long long n) { return (n + kChThreads - 1) / kChThreads; }
 
 hipError_t launch_points_cell_keys(const double* pts, long long n, const double* origin, double cell, long long* keys,
                                    hipStream_t s) {
-  hipLaunchKernelGGL(points_cell_keys_kernel, dim3(blocks_of(n)), dim3(kChThreads), 0, s, pts, n, origin[0], origin[1], origin[2],
+  hipLaunchKernelGGL(points_cell_keys_kernel, dim3((unsigned)chamfer_blocks(n)), dim3(kChThreads), 0, s, pts, n, origin[0], origin[1], origin[2],
                      cell, keys);
   return hipGetLastError();
 }
 
 hipError_t launch_mesh_sample_count(const double* verts, const int* faces, long long V, long long F, double density,
                                     long long* tri_off, long long* block_tot, hipStream_t s) {
-  hipLaunchKernelGGL(mesh_sample_count_kernel, dim3(blocks_of(F)), dim3(kChThreads), 0, s, verts, faces, V, F, density, tri_off,
+  hipLaunchKernelGGL(mesh_sample_count_kernel, dim3((unsigned)chamfer_blocks(F)), dim3(kChThreads), 0, s, verts, faces, V, F, density, tri_off,
                      block_tot);
   return hipGetLastError();
 }
 
 hipError_t launch_mesh_sample_scan(const long long* block_tot, long long n_blocks, long long* block_off, long long* total,
                                    hipStream_t s) {
-  hipLaunchKernelGGL(mesh_sample_scan_kernel, dim3(1), dim3(kChScanThreads), 0, s, block_tot, n_blocks, block_off, total);
-  return hipGetLastError();
+  return launch_scan_totals<1>(block_tot, n_blocks, block_off, total, s);
 }
 
 hipError_t launch_mesh_sample_emit(const double* verts, const int* faces, long long V, long long F, double density,
                                    const long long* tri_off, const long long* block_off, double* out, long long capacity,
                                    hipStream_t s) {
-  hipLaunchKernelGGL(mesh_sample_emit_kernel, dim3(blocks_of(F)), dim3(kChThreads), 0, s, verts, faces, V, F, density, tri_off,
+  hipLaunchKernelGGL(mesh_sample_emit_kernel, dim3((unsigned)chamfer_blocks(F)), dim3(kChThreads), 0, s, verts, faces, V, F, density, tri_off,
                      block_off, out, capacity);
   return hipGetLastError();
 }
 
 hipError_t launch_thin_round(const double* pts, const long long* keys, const int* rank, long long n, double radius,
                              unsigned char* state, int* undecided, hipStream_t s) {
-  hipLaunchKernelGGL(thin_round_kernel, dim3(blocks_of(n)), dim3(kChThreads), 0, s, pts, keys, rank, n, radius * radius, state,
+  hipLaunchKernelGGL(thin_round_kernel, dim3((unsigned)chamfer_blocks(n)), dim3(kChThreads), 0, s, pts, keys, rank, n, radius * radius, state,
                      undecided);
   return hipGetLastError();
 }
@@ -409,11 +365,11 @@ hipError_t launch_nn_dist(const double* query, long long nq, const double* ref, 
   NnGrid g;
   for (int a = 0; a < 3; ++a) g.o[a] = origin[a];
   g.cell = cell;
-  hipLaunchKernelGGL(nn_dist_kernel, dim3(blocks_of(nq)), dim3(kChThreads), 0, s, query, nq, ref, keys, nr, g, max_dist, dist,
+  hipLaunchKernelGGL(nn_dist_kernel, dim3((unsigned)chamfer_blocks(nq)), dim3(kChThreads), 0, s, query, nq, ref, keys, nr, g, max_dist, dist,
                      block_sum, block_cnt);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !mean_out) return e;
-  hipLaunchKernelGGL(nn_sum_kernel, dim3(1), dim3(kChScanThreads), 0, s, block_sum, block_cnt, chamfer_blocks(nq), mean_out);
+  hipLaunchKernelGGL(nn_sum_kernel, dim3(1), dim3(kScanThreads), 0, s, block_sum, block_cnt, chamfer_blocks(nq), mean_out);
   return hipGetLastError();
 }
 

@@ -18,16 +18,16 @@
 //          tested explicitly and gives 0 (on x86 OpenCV's conversion yields INT_MIN there, which saturates to -32768: all
 //          four taps outside).  NOT COMPARED WITH A REAL OpenCV: none exists where this was written.  It is one function so
 //          that there is one place to check.  Every tap index is bounds-checked before the load.
-//   depth_points_count / _scan / _emit   ordered stream compaction of the valid pixels of one reference view (the
-//          count / scan / emit shape of mcubes.hip): a block popcounts its 256 mask bytes (wave ballots), one block scans the
-//          block sums, and the emit kernel recomputes the ballots, so that pixel i's slot is block offset + lower waves + lower
-//          lanes: row-major pixel order, the order x[valid_points] gives.  xyz = inv(E_ref) [inv(K_ref) (x, y, 1) depth ; 1] in
+//   depth_points_count / _scan / _emit   the ordered compaction of compact.h over the valid pixels of one reference view,
+//          with block_rank as the block scan: pixel i's slot is block offset + lower waves + lower lanes: row-major pixel
+//          order, the order x[valid_points] gives.  xyz = inv(E_ref) [inv(K_ref) (x, y, 1) depth ; 1] in
 //          fp64 (:209-212), narrowed to fp32; rgb the 8-bit image value ((v / 255f) * 255f truncates back to v for every
 //          v in 0..255).  No atomics; every output store is guarded by the caller's capacity.
 //
 // Block shape: 256 threads (4 waves), no LDS in the consistency kernel, 16 B of it in the compaction kernels.  The
 // consistency kernel is a chain of fp64 3x3 products around four dependent 4-byte gathers per pair: latency bound, so what
 // matters is waves in flight, and nothing here limits them but registers.
+#include "compact.h"
 #include "ufr_internal.h"
 
 #pragma clang fp contract(off)
@@ -36,7 +36,6 @@ namespace ufr {
 namespace {
 
 constexpr int kDfThreads = 256;
-constexpr int kDfScanThreads = 1024;
 
 // offsets of the six row-major matrices in a pair's record of UFR_DEPTH_PAIR_DOUBLES doubles
 constexpr int kInvKRef = 0, kSrcFromRef = 9, kKSrc = 25, kInvKSrc = 34, kRefFromSrc = 43, kKRef = 59;
@@ -132,55 +131,13 @@ __global__ void __launch_bounds__(kDfThreads) depth_consistency_kernel(const flo
 }
 
 // ------------------------------------------------------------------ ordered compaction of the valid pixels
-// this thread's slot inside its block among the valid pixels, and the block's count (the same for every thread)
-__device__ inline int block_rank(bool valid, int* lds, int* block_count) {
-  const unsigned long long b = __ballot(valid);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) lds[wave] = __popcll(b);
-  __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kDfThreads / 64; ++w) {
-    const int c = lds[w];
-    before += w < wave ? c : 0;
-    total += c;
-  }
-  *block_count = total;
-  return before + __popcll(b & ((1ull << lane) - 1ull));
-}
-
 __global__ void __launch_bounds__(kDfThreads) depth_points_count_kernel(const unsigned char* __restrict__ mask, long long n,
                                                                          long long* __restrict__ block_tot) {
   __shared__ int lds[kDfThreads / 64];
   const long long i = (long long)blockIdx.x * kDfThreads + threadIdx.x;
   int total;
-  block_rank(i < n && mask[i] != 0, lds, &total);
+  block_rank<kDfThreads>(i < n && mask[i] != 0, lds, &total);
   if (threadIdx.x == 0) block_tot[blockIdx.x] = total;
-}
-
-// one block: block_off = exclusive prefix of block_tot, *total = the sum
-__global__ void __launch_bounds__(kDfScanThreads) depth_points_scan_kernel(const long long* __restrict__ block_tot, long long n_blocks,
-                                                                            long long* __restrict__ block_off,
-                                                                            long long* __restrict__ total) {
-  __shared__ long long sa[kDfScanThreads];
-  const long long per = (n_blocks + kDfScanThreads - 1) / kDfScanThreads;
-  const long long t0 = min((long long)threadIdx.x * per, n_blocks), t1 = min(t0 + per, n_blocks);
-  long long a = 0;
-  for (long long t = t0; t < t1; ++t) a += block_tot[t];
-  sa[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 1; d < kDfScanThreads; d <<= 1) {
-    const long long u = threadIdx.x >= (unsigned)d ? sa[threadIdx.x - d] : 0;
-    __syncthreads();
-    sa[threadIdx.x] += u;
-    __syncthreads();
-  }
-  long long o = sa[threadIdx.x] - a;
-  for (long long t = t0; t < t1; ++t) {
-    block_off[t] = o;
-    o += block_tot[t];
-  }
-  if (threadIdx.x == kDfScanThreads - 1) *total = sa[threadIdx.x];
 }
 
 __global__ void __launch_bounds__(kDfThreads) depth_points_emit_kernel(const unsigned char* __restrict__ mask,
@@ -194,7 +151,7 @@ __global__ void __launch_bounds__(kDfThreads) depth_points_emit_kernel(const uns
   const long long i = (long long)blockIdx.x * kDfThreads + threadIdx.x;
   const bool valid = i < n && mask[i] != 0;
   int total;
-  const int rank = block_rank(valid, lds, &total);
+  const int rank = block_rank<kDfThreads>(valid, lds, &total);
   if (!valid) return;
   const long long o = block_off[blockIdx.x] + rank;
   if (o < 0 || o >= capacity) return;
@@ -232,8 +189,7 @@ hipError_t launch_depth_points_count(const unsigned char* mask, long long n, lon
                                      long long* total, hipStream_t s) {
   const long long blocks = depth_points_blocks(n);
   hipLaunchKernelGGL(depth_points_count_kernel, dim3((unsigned)blocks), dim3(kDfThreads), 0, s, mask, n, block_tot);
-  hipLaunchKernelGGL(depth_points_scan_kernel, dim3(1), dim3(kDfScanThreads), 0, s, block_tot, blocks, block_off, total);
-  return hipGetLastError();
+  return launch_scan_totals<1>(block_tot, blocks, block_off, total, s);
 }
 
 hipError_t launch_depth_points_emit(const unsigned char* mask, const double* depth_avg, const unsigned char* color, int H, int W,

@@ -3,15 +3,16 @@
 // Replaces skimage.measure.marching_cubes_lewiner as the reference's TSDFVolume.get_mesh calls it (tsdf_fusion.py:340-357),
 // without copying the volumes to the host.
 //
-// Four launches, no atomics, no inter-block flags:
+// Four launches, the ordered compaction of compact.h with two columns (vertices, faces) and two emit kernels:
 //   count  one thread per voxel (lanes along z, coalesced), TILE voxels per block: the voxel's crossing edges (<= 3,
 //          owned by it: p -> p + e_axis) and, for a cube origin, its case's triangle count; one block sum per tile;
-//   scan   one block: exclusive prefix of the tile sums -> tile offsets and the two totals (the host reads those);
+//   scan   the tile sums -> tile offsets and the two totals (the host reads those);
 //   verts  recount, block scan + tile offset -> vertex ids in (voxel, axis) order; position, normal; the voxel's first
 //          vertex id into the index volume (workspace, written only where the voxel owns a vertex);
 //   faces  recount cases, block scan + tile offset -> face ids in (cube, table order) order; vertex id of a triangle
 //          edge = index[owner] + popcount(owner's crossing bits below the edge's axis).
 // Every output store is guarded by the caller's capacity.  Volumes hold fewer than 2^31 voxels (api_geometry.hip checks it).
+#include "compact.h"
 #include "mcubes_table.h"
 #include "ufr_internal.h"
 
@@ -22,7 +23,6 @@ namespace {
 
 constexpr int kMcThreads = 256;
 constexpr int kMcIters = 16;
-constexpr int kMcScanThreads = 1024;
 
 struct McVol {
   const float* f;
@@ -68,33 +68,8 @@ __device__ inline float grad(const McVol& v, int x, int y, int z, int a) {
   return (v.at(x + dx, y + dy, z + dz) - v.at(x - dx, y - dy, z - dz)) * 0.5f;
 }
 
-// block-wide exclusive scan of (a, b) over kMcThreads threads; *tot gets the block sums.  Starts and ends with a barrier
-// so that consecutive calls may reuse lds.
-__device__ inline int2 block_scan2(int a, int b, int2* lds, int2* tot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int ia = a, ib = b;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int ua = __shfl_up(ia, d), ub = __shfl_up(ib, d);
-    if (lane >= d) { ia += ua; ib += ub; }
-  }
-  __syncthreads();
-  if (lane == 63) lds[wave] = make_int2(ia, ib);
-  __syncthreads();
-  int2 pre = make_int2(0, 0), all = make_int2(0, 0);
-#pragma unroll
-  for (int w = 0; w < kMcThreads / 64; ++w) {
-    const int2 s = lds[w];
-    if (w < wave) { pre.x += s.x; pre.y += s.y; }
-    all.x += s.x; all.y += s.y;
-  }
-  __syncthreads();
-  *tot = all;
-  return make_int2(pre.x + ia - a, pre.y + ib - b);
-}
-
 __global__ void __launch_bounds__(kMcThreads) mcubes_count_kernel(McVol v, unsigned n, int* __restrict__ tile_counts) {
-  __shared__ int2 lds[kMcThreads / 64];
+  __shared__ long long lds[kMcThreads / 64];
   const unsigned base = blockIdx.x * (unsigned)(kMcThreads * kMcIters);
   int nv = 0, nt = 0;
   for (int it = 0; it < kMcIters; ++it) {
@@ -106,48 +81,20 @@ __global__ void __launch_bounds__(kMcThreads) mcubes_count_kernel(McVol v, unsig
     const int c = cube_case(v, x, y, z);
     if (c >= 0) nt += kMcTriCount[c];
   }
-  int2 tot;
-  block_scan2(nv, nt, lds, &tot);
+  // both block sums from one scan: vertices in the high word, triangles in the low one (a tile has at most 3 * 4096 and
+  // 5 * 4096 of them, so the low word never carries): the shuffles and LDS traffic of one scan of an int pair
+  long long tot;
+  block_scan_excl<long long, kMcThreads>((long long)nv << 32 | nt, lds, &tot);
   if (threadIdx.x == 0) {
-    tile_counts[2 * blockIdx.x] = tot.x;
-    tile_counts[2 * blockIdx.x + 1] = tot.y;
+    tile_counts[2 * blockIdx.x] = (int)(tot >> 32);
+    tile_counts[2 * blockIdx.x + 1] = (int)tot;
   }
-}
-
-// one block: tile_off[2t..2t+1] = exclusive prefix of tile_counts, totals[0..1] = the sums (64-bit: the host checks range)
-__global__ void __launch_bounds__(kMcScanThreads) mcubes_scan_kernel(const int* __restrict__ tile_counts, int n_tiles,
-                                                                      long long* __restrict__ tile_off,
-                                                                      long long* __restrict__ totals) {
-  __shared__ long long sa[kMcScanThreads], sb[kMcScanThreads];
-  const int per = (n_tiles + kMcScanThreads - 1) / kMcScanThreads;
-  const int t0 = threadIdx.x * per, t1 = min(t0 + per, n_tiles);
-  long long a = 0, b = 0;
-  for (int t = t0; t < t1; ++t) { a += tile_counts[2 * t]; b += tile_counts[2 * t + 1]; }
-  sa[threadIdx.x] = a;
-  sb[threadIdx.x] = b;
-  __syncthreads();
-  for (int d = 1; d < kMcScanThreads; d <<= 1) {       // Hillis-Steele inclusive scan
-    const long long ua = threadIdx.x >= (unsigned)d ? sa[threadIdx.x - d] : 0;
-    const long long ub = threadIdx.x >= (unsigned)d ? sb[threadIdx.x - d] : 0;
-    __syncthreads();
-    sa[threadIdx.x] += ua;
-    sb[threadIdx.x] += ub;
-    __syncthreads();
-  }
-  long long oa = sa[threadIdx.x] - a, ob = sb[threadIdx.x] - b;
-  for (int t = t0; t < t1; ++t) {
-    tile_off[2 * t] = oa;
-    tile_off[2 * t + 1] = ob;
-    oa += tile_counts[2 * t];
-    ob += tile_counts[2 * t + 1];
-  }
-  if (threadIdx.x == kMcScanThreads - 1) { totals[0] = sa[threadIdx.x]; totals[1] = sb[threadIdx.x]; }
 }
 
 __global__ void __launch_bounds__(kMcThreads) mcubes_verts_kernel(McVol v, unsigned n, const long long* __restrict__ tile_off,
                                                                    int* __restrict__ index, float* __restrict__ verts,
                                                                    float* __restrict__ normals, long long n_verts) {
-  __shared__ int2 lds[kMcThreads / 64];
+  __shared__ int lds[kMcThreads / 64];
   const unsigned base = blockIdx.x * (unsigned)(kMcThreads * kMcIters);
   long long run = tile_off[2 * blockIdx.x];
   for (int it = 0; it < kMcIters; ++it) {
@@ -160,10 +107,9 @@ __global__ void __launch_bounds__(kMcThreads) mcubes_verts_kernel(McVol v, unsig
       f0 = v.at(x, y, z);
       m = crossing_bits(v, x, y, z, f0 < v.level);
     }
-    int2 tot;
-    const int2 pre = block_scan2(__popc(m), 0, lds, &tot);
-    long long id = run + pre.x;
-    run += tot.x;
+    int tot;
+    long long id = run + block_scan_excl<int, kMcThreads>(__popc(m), lds, &tot);
+    run += tot;
     if (!m) continue;
     index[idx] = (int)id;
     for (int a = 0; a < 3; ++a) {
@@ -206,7 +152,7 @@ __device__ inline long long edge_vertex(const McVol& v, const int* __restrict__ 
 __global__ void __launch_bounds__(kMcThreads) mcubes_faces_kernel(McVol v, unsigned n, const long long* __restrict__ tile_off,
                                                                    const int* __restrict__ index, int* __restrict__ faces,
                                                                    long long n_faces) {
-  __shared__ int2 lds[kMcThreads / 64];
+  __shared__ int lds[kMcThreads / 64];
   const unsigned base = blockIdx.x * (unsigned)(kMcThreads * kMcIters);
   long long run = tile_off[2 * blockIdx.x + 1];
   for (int it = 0; it < kMcIters; ++it) {
@@ -218,10 +164,9 @@ __global__ void __launch_bounds__(kMcThreads) mcubes_faces_kernel(McVol v, unsig
       c = cube_case(v, x, y, z);
     }
     const int nt = c >= 0 ? (int)kMcTriCount[c] : 0;
-    int2 tot;
-    const int2 pre = block_scan2(nt, 0, lds, &tot);
-    const long long first = run + pre.x;
-    run += tot.x;
+    int tot;
+    const long long first = run + block_scan_excl<int, kMcThreads>(nt, lds, &tot);
+    run += tot;
     for (int k = 0; k < nt; ++k) {
       const long long fid = first + k;
       if (fid < 0 || fid >= n_faces) continue;
@@ -262,9 +207,9 @@ hipError_t launch_mcubes_count(const float* vol, const int* dim, float level, in
   return hipGetLastError();
 }
 
+// tile_counts and tile_off hold two interleaved columns: vertices, faces
 hipError_t launch_mcubes_scan(const int* tile_counts, int n_tiles, long long* tile_off, long long* totals, hipStream_t s) {
-  hipLaunchKernelGGL(mcubes_scan_kernel, dim3(1), dim3(kMcScanThreads), 0, s, tile_counts, n_tiles, tile_off, totals);
-  return hipGetLastError();
+  return launch_scan_totals<2>(tile_counts, n_tiles, tile_off, totals, s);
 }
 
 hipError_t launch_mcubes_verts(const float* vol, const int* dim, float level, const long long* tile_off, int* index,
