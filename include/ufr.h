@@ -429,6 +429,48 @@ typedef struct ufr_render_args {
 size_t ufr_render_workspace_bytes(int32_t chunk_rays, int32_t SN, int32_t PN, int32_t NV);
 int32_t ufr_default_chunk_rays(void);
 int ufr_render_rays(const ufr_render_args* a, ufr_stream stream);
+/* ufr_render_rays that also hands out the COARSE pass (ABI 507, additive): the same checks, launches and bits in a's
+ * outputs; the one difference is that the coarse compositor writes its colour and ray-length depth to rgb_coarse (RN,3) /
+ * depth_coarse (RN) instead of the workspace.  Refuses coarse_only (one pass: call ufr_render_rays).  a->cam_ray_d == NULL
+ * is UFORecon.infer(extract_geometry=False) as validation_step calls it (model.py:423: near/far as given, no division by
+ * cam_ray_d.z); depth_z must then be NULL. */
+int ufr_render_rays_pair(const ufr_render_args* a, float* rgb_coarse, float* depth_coarse, ufr_stream stream);
+
+/* ---- the scores and previews of a validation frame (ABI 507, additive) -----------------------------------------
+ * UFORecon.validation_step's metrics (model.py:708-726) and save arithmetic (:731, :734, :742) for one frame of n rays.
+ * ufr_frame_metrics: rgb_c / rgb_f (n,3) the coarse / fine colours, rgb_gt (3,n) PLANAR (batch['ref_img']), depth_c / depth_f
+ *   / depth_gt (n): device fp32.  out8: eight device doubles
+ *     [0] [1]  MSE coarse / fine    mean over 3n of (x - y)^2                                   (F.mse_loss)
+ *     [2] [3]  PSNR coarse / fine   -10 log10(mean((clamp(x,0,1) - clamp(y,0,1))^2) + 1e-8)     (piq.psnr, data_range 1)
+ *     [4] [5]  L1 depth coarse / fine over the pixels with depth_gt != 0 && near <= depth_gt <= far; 0 when there is none
+ *     [6]      the number of such pixels
+ *     [7]      max of depth_c (NaN if one is NaN, as np.max)
+ *   Differences are formed in double from the fp32 inputs.  One pass over the inputs on a grid that depends on n alone: double
+ *   partials per thread, reduced across the wave and the block in a fixed order, one row per block; a second one-block
+ *   kernel adds the rows in index order.  No atomics: a rerun gives the same bits.  NaN inputs propagate as in torch (a NaN
+ *   depth_gt fails the mask).  workspace >= ufr_frame_metrics_workspace_bytes(n) (device).  1 <= n < 2^31 / 3.
+ * ufr_frame_preview_u8: rgb8 (n,3) = (uint8)(rgb * 255) and, when depth is given, depth8 (n) = (uint8)((depth * depth_scale)
+ *   / (max * depth_scale) * 255) with max = (float)*depth_max (DEVICE: &out8[7]); every product and the quotient are fp32,
+ *   unfused, so the bytes equal numpy's for the same expression; the float -> uint8 step truncates towards zero and keeps the
+ *   low 8 bits (values beyond int32 saturate first, NaN gives 0).  rgb / rgb8 or depth / depth_max / depth8 may be NULL as a
+ *   group.  Neither call synchronises; every argument error is UFR_ERR_ARG. */
+size_t ufr_frame_metrics_workspace_bytes(int32_t n);
+int ufr_frame_metrics(const float* rgb_c, const float* rgb_f, const float* rgb_gt, const float* depth_c, const float* depth_f,
+                      const float* depth_gt, float near, float far, int32_t n, double* out8, void* workspace, ufr_stream stream);
+int ufr_frame_preview_u8(const float* rgb, const float* depth, const double* depth_max, float depth_scale, int32_t n, uint8_t* rgb8,
+                         uint8_t* depth8, ufr_stream stream);
+/* ufr_depth_gt_prepare: the ground-truth ray depth of one view of the DTU training layout (code1/dataset/dtu_train.py: read_depth
+ *   :249-254, :429, :485) from pfm = the (Hs,Ws) fp32 rows of `Depths_raw/<scan>/depth_map_%04d.pfm` AS STORED (device):
+ *     depth[y, x] = (float)((double)(S[2 (y + y0), 2 (x + x0)] * scale_factor) / cam_ray_z[y * W + x])
+ *   with S the picture the file holds -- row r of S is stored row Hs - 1 - r when bottom_up (read_pfm's flip; every PFM file),
+ *   row r otherwise.  The factor 2 is OpenCV's INTER_NEAREST at fx = fy = 0.5, restated and not compared; the half-size
+ *   picture has rint(Hs / 2) x rint(Ws / 2) pixels (half to even) and the crop (y0, x0, H, W) must lie inside it (DTU: 1200 x
+ *   1600 -> 600 x 800, crop 512 x 640 at (44, 80)).  The product is fp32 (the reference multiplies float32 arrays), the
+ *   quotient double: cam_ray_z (H*W) is row 2 of the reference's cam_ray_d, which it leaves in float64 (device).  A hole (0)
+ *   stays 0; the scale of the PFM header is not applied (read_pfm returns it and the reference drops it).  Does not
+ *   synchronise; every argument error is UFR_ERR_ARG. */
+int ufr_depth_gt_prepare(const float* pfm, int32_t Hs, int32_t Ws, int32_t bottom_up, int32_t y0, int32_t x0, int32_t H, int32_t W,
+                         float scale_factor, const double* cam_ray_z, float* depth, ufr_stream stream);
 
 /* Per-kernel HIP-event timing of the most recent ufr_render_rays on this thread when
  * enabled (for bench.py's roofline line).  names/ms arrays of length `cap`; returns count. */

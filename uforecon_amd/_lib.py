@@ -118,6 +118,11 @@ SIGNATURES = {
     "ufr_render_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ufr_default_chunk_rays": (i32, []),
     "ufr_render_rays": (C.c_int, [C.POINTER(RenderArgs), vp]),
+    "ufr_render_rays_pair": (C.c_int, [C.POINTER(RenderArgs), vp, vp, vp]),
+    "ufr_frame_metrics_workspace_bytes": (sz, [i32]),
+    "ufr_frame_metrics": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp]),
+    "ufr_frame_preview_u8": (C.c_int, [vp, vp, vp, C.c_float, i32, vp, vp, vp]),
+    "ufr_depth_gt_prepare": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp]),
     "ufr_correlate_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ufr_frustum_correlate": (C.c_int, [vp, vp, C.POINTER(C.c_float), vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "ufr_conv3d": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),

@@ -1,4 +1,4 @@
-// extern "C" surface of libufr.so (include/ufr.h), part 6 of 6: geometry after the network -- TSDF fusion, marching cubes,
+// extern "C" surface of libufr.so (include/ufr.h), part 6 of 7: geometry after the network -- TSDF fusion, marching cubes,
 // the DTU chamfer evaluation, depth-map fusion, mesh cleaning and mesh rendering.  The count / emit pairs synchronise the
 // stream to hand a count to the host; so do the rounds of the two fixpoints (point thinning, face components).
 #include "api_common.h"

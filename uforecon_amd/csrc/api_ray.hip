@@ -1,4 +1,4 @@
-// extern "C" surface of libufr.so (include/ufr.h), part 3 of 6: the forward ray path -- its per-op entry points and the
+// extern "C" surface of libufr.so (include/ufr.h), part 3 of 7: the forward ray path -- its per-op entry points and the
 // whole-path two-pass renderer with its side streams.
 #include "api_common.h"
 
@@ -236,9 +236,13 @@ int side_pool_get(int n, SidePool** out) {
   return UFR_OK;
 }
 
+// where the coarse compositor's colour and depth go: the workspace (ufr_render_rays drops them) or the caller's
+// buffers (ufr_render_rays_pair)
+struct CoarseOut { float *rgb, *depth; };
+
 // one chunk of R rays starting at r0, entirely on stream s with workspace w
 int render_chunk(const ufr_render_args* a, const FrameDev* f, const RenderWs& w, bool& pe_ready, int r0, int R, bool lowp,
-                 int* status, hipStream_t s) {
+                 int* status, CoarseOut co, hipStream_t s) {
   const int RN = a->RN, SN = a->SN, PN = a->coarse_only ? 0 : a->PN, NV = f->NV;
   const PreSim ps = presim_of(a->raw);
   const int S2 = SN + PN, HW = f->H * f->W;
@@ -260,7 +264,8 @@ int render_chunk(const ufr_render_args* a, const FrameDev* f, const RenderWs& w,
                            nullptr, nullptr, lowp, status, s));
   const bool last = a->coarse_only != 0;
   UFR_TIMED("composite", s, launch_composite(w.z1, w.rad, nullptr, w.srdf1, a->raw->variance, R, SN,
-      last ? a->rgb + 3 * (size_t)r0 : w.rgb1, last ? a->depth + r0 : w.depth1, nullptr, w.w1, w.camz,
+      last ? a->rgb + 3 * (size_t)r0 : co.rgb ? co.rgb + 3 * (size_t)r0 : w.rgb1,
+      last ? a->depth + r0 : co.depth ? co.depth + r0 : w.depth1, nullptr, w.w1, w.camz,
       (last && a->depth_z) ? a->depth_z + r0 : nullptr, s));
   if (last) {
     if (a->srdf) UFR_HIP(hipMemcpyAsync(a->srdf + (size_t)r0 * SN, w.srdf1, (size_t)R * SN * 4, hipMemcpyDeviceToDevice, s));
@@ -294,8 +299,10 @@ size_t ufr_render_workspace_bytes(int32_t chunk_rays, int32_t SN, int32_t PN, in
   return carve_render(nullptr, chunk_rays, SN, PN, NV).bytes;
 }
 
-int ufr_render_rays(const ufr_render_args* a, ufr_stream stream) {
-  UFR_REQUIRE(a, "ufr_render_rays: null args");
+}  // extern "C"
+
+namespace {
+int render_impl(const ufr_render_args* a, CoarseOut co, ufr_stream stream) {
   const FrameDev* f = frame_of(a->frame);
   UFR_REQUIRE(f, "ufr_render_rays: frame handle not prepared");
   UFR_REQUIRE(f->match && f->vol[0], "ufr_render_rays: the frame was prepared without matching features / volumes");
@@ -340,7 +347,7 @@ int ufr_render_rays(const ufr_render_args* a, ufr_stream stream) {
     RenderWs w = carve_render(a->workspace, chunk, SN, PN, NV);
     bool pe_ready = false;
     for (int r0 = 0; r0 < RN; r0 += eff_chunk)
-      UFR_CHECK(render_chunk(a, f, w, pe_ready, r0, (RN - r0) < eff_chunk ? (RN - r0) : eff_chunk, lowp, status_word(sl), s));
+      UFR_CHECK(render_chunk(a, f, w, pe_ready, r0, (RN - r0) < eff_chunk ? (RN - r0) : eff_chunk, lowp, status_word(sl), co, s));
     return status_leave(sl, s);
   }
   SidePool* side = nullptr;
@@ -355,7 +362,7 @@ int ufr_render_rays(const ufr_render_args* a, ufr_stream stream) {
   int rc = UFR_OK;
   for (int c = 0; c < n_chunks && rc == UFR_OK; ++c) {
     const int l = c % lanes, r0 = c * eff_chunk;
-    rc = render_chunk(a, f, w[l], pe_ready[l], r0, (RN - r0) < eff_chunk ? (RN - r0) : eff_chunk, lowp, status_word(sl), side->s[l]);
+    rc = render_chunk(a, f, w[l], pe_ready[l], r0, (RN - r0) < eff_chunk ? (RN - r0) : eff_chunk, lowp, status_word(sl), co, side->s[l]);
   }
   // join even when a chunk failed: the caller's stream must not run ahead of (and its allocator must not recycle the
   // workspace under) side-stream kernels that were already enqueued
@@ -365,6 +372,22 @@ int ufr_render_rays(const ufr_render_args* a, ufr_stream stream) {
     if (e != hipSuccess) hipStreamSynchronize(side->s[l]);
   }
   return rc != UFR_OK ? rc : status_leave(sl, s);
+}
+}  // namespace
+
+extern "C" {
+
+int ufr_render_rays(const ufr_render_args* a, ufr_stream stream) {
+  UFR_REQUIRE(a, "ufr_render_rays: null args");
+  return render_impl(a, CoarseOut{nullptr, nullptr}, stream);
+}
+
+int ufr_render_rays_pair(const ufr_render_args* a, float* rgb_coarse, float* depth_coarse, ufr_stream stream) {
+  UFR_REQUIRE(a, "ufr_render_rays_pair: null args");
+  UFR_REQUIRE(rgb_coarse && depth_coarse, "ufr_render_rays_pair: null coarse output");
+  UFR_REQUIRE(!a->coarse_only, "ufr_render_rays_pair: coarse_only renders one pass; call ufr_render_rays");
+  UFR_REQUIRE(a->cam_ray_d || !a->depth_z, "ufr_render_rays_pair: depth_z needs cam_ray_d (without it near/far are ray lengths already)");
+  return render_impl(a, CoarseOut{rgb_coarse, depth_coarse}, stream);
 }
 
 }  // extern "C"

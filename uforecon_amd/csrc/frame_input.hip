@@ -19,6 +19,12 @@
 //          |v| = sqrt((v0^2 + v1^2) + v2^2), stored as float.  numpy's matmul and torch.norm may sum in another order: the host
 //          side differs by a few double ulps before the cast (tests/test_gpu_dtu_scan.py bounds what is left of that).
 //
+//   depth_gt      one thread per output pixel: the ground-truth depth of a training view as the reference's MVSDataset makes it
+//          (code1/dataset/dtu_train.py:249-254, :429, :485) from the rows of a grey PFM file as stored: the row flip of read_pfm
+//          (bottom_up), OpenCV's INTER_NEAREST at fx = fy = 0.5, restated (source pixel (2y, 2x); no OpenCV was compared), the
+//          crop, x scale_factor in float32, then / cam_ray_d.z in DOUBLE (the reference divides by its float64 ray table)
+//          and the cast to float.  A hole (0) stays 0.  The scale the PFM header carries is not applied (the reference drops it).
+//
 // Block shape: 256 threads, a 1-D grid over the pixels of all images; every index is 64-bit.
 #include "ufr_internal.h"
 
@@ -119,6 +125,18 @@ __global__ void __launch_bounds__(kFiThreads) pixel_rays_kernel(RayArgs a, int H
   for (int r = 0; r < 3; ++r) dir[r * HW + i] = (float)(v[r] / len);
 }
 
+__global__ void __launch_bounds__(kFiThreads) depth_gt_kernel(const float* __restrict__ pfm, int Hs, int Ws, int bottom_up, int y0, int x0,
+                                                               int H, int W, float scale_factor, const double* __restrict__ cam_ray_z,
+                                                               float* __restrict__ depth) {
+  const long long i = (long long)blockIdx.x * kFiThreads + threadIdx.x;
+  if (i >= (long long)H * W) return;
+  const int y = (int)(i / W), x = (int)(i - (long long)y * W);
+  const int ys = 2 * (y + y0), xs = 2 * (x + x0);                 // inside the file: the entry point checked the crop
+  const int row = bottom_up ? Hs - 1 - ys : ys;
+  const float scaled = pfm[(long long)row * Ws + xs] * scale_factor;
+  depth[i] = (float)((double)scaled / cam_ray_z[i]);
+}
+
 inline unsigned blocks_of(long long n) { return (unsigned)((n + kFiThreads - 1) / kFiThreads); }
 
 }  // namespace
@@ -136,6 +154,13 @@ hipError_t launch_pixel_rays(const float* m_inv, const float* origin, int H, int
   for (int k = 0; k < 12; ++k) a.m[k] = (double)m_inv[k];
   for (int k = 0; k < 3; ++k) a.o[k] = origin ? (double)origin[k] : 0.0;
   hipLaunchKernelGGL(pixel_rays_kernel, dim3(blocks_of((long long)H * W)), dim3(kFiThreads), 0, s, a, H, W, dir);
+  return hipGetLastError();
+}
+
+hipError_t launch_depth_gt(const float* pfm, int Hs, int Ws, int bottom_up, int y0, int x0, int H, int W, float scale_factor,
+                           const double* cam_ray_z, float* depth, hipStream_t s) {
+  hipLaunchKernelGGL(depth_gt_kernel, dim3(blocks_of((long long)H * W)), dim3(kFiThreads), 0, s, pfm, Hs, Ws, bottom_up, y0, x0, H, W,
+                     scale_factor, cam_ray_z, depth);
   return hipGetLastError();
 }
 

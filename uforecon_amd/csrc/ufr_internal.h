@@ -197,6 +197,14 @@ hipError_t launch_raster_downsample(const unsigned char* src, long long n, int H
 hipError_t launch_image_resize_u8(const unsigned char* src, long long n, int Hs, int Ws, int H, int W, int x0, int y0, int Ho, int Wo,
                                   float* dst, hipStream_t s);
 hipError_t launch_pixel_rays(const float* m_inv, const float* origin, int H, int W, float* dir, hipStream_t s);
+hipError_t launch_depth_gt(const float* pfm, int Hs, int Ws, int bottom_up, int y0, int x0, int H, int W, float scale_factor,
+                           const double* cam_ray_z, float* depth, hipStream_t s);
+// frame_metrics.hip: the scores and 8-bit previews of a validation frame (see the file header)
+constexpr int kFrameMetricsBlocks = 256;   // most partial rows one frame leaves in the workspace
+hipError_t launch_frame_metrics(const float* rgb_c, const float* rgb_f, const float* rgb_gt, const float* depth_c, const float* depth_f,
+                                const float* depth_gt, float near_z, float far_z, int n, double* out8, double* rows, hipStream_t s);
+hipError_t launch_frame_preview_u8(const float* rgb, const float* depth, const double* depth_max, float depth_scale, int n,
+                                   unsigned char* rgb8, unsigned char* depth8, hipStream_t s);
 // conv2d.hip: the plain 2-D convolutions of FeatureNet on channel-last tensors, epilogue fused (see the file header)
 struct Conv2dArgs {
   const float* in;      // [B][H][W][CIN] (the stem: planar [B][3][H][W])

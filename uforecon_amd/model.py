@@ -507,6 +507,68 @@ class UFORecon(nn.Module):
         return depths, rgbs
 
 
+    # ---- frame-level entry of validation: both passes of the reference view and their scores (model.py:672-758)
+    @torch.no_grad()
+    def validation_frame(self, batch, source_imgs_feat, feature_volume, match_feature, logdir=None, uniforms=None):
+        """The per-ray part of ``validation_step`` (code1/model.py:672-758) for a train-layout batch of one frame: every
+        pixel of the reference view through the coarse and the fine pass in one ``ufr_render_rays_pair`` call (no tape;
+        near/far as given, model.py:423), scored on the device (``ufr_frame_metrics``), previews by
+        ``ufr_frame_preview_u8``.  Returns the reference's dict (six floats and ``val/variance``, a (1,1) array); with
+        ``logdir`` it also writes the reference's three files (``save_validation_outputs``)."""
+        B, L, _, imgH, imgW = batch["source_imgs"].shape
+        if B != 1:
+            raise UfrError(f"validation_step: one frame per call (B=1), got B={B}: the reference's own file writing reads element 0 only")
+        dev = source_imgs_feat.device
+        HW = imgH * imgW
+        if uniforms is None:   # one draw per frame instead of one per train_ray_num chunk: same distribution
+            U1, U2 = torch.rand(self.point_num, HW), torch.rand(self.point_num_2, HW)
+        else:
+            U1, U2 = uniforms
+        U1 = U1.to(dev, torch.float32).contiguous()
+        U2 = U2.to(dev, torch.float32).contiguous()
+        # without cam_ray_d the ray setup leaves near/far unscaled: infer(extract_geometry=False)
+        fh = self.frame_handle({k: v for k, v in batch.items() if k != "cam_ray_d"}, source_imgs_feat, feature_volume, match_feature)
+        if self._ws is None or self._ws.key[:3] != (self.point_num, self.point_num_2, fh.NV):
+            self._ws = ops.RenderWorkspace(dev, self.point_num, self.point_num_2, fh.NV)
+        out = ops.render_rays(fh, self._weights(), torch.arange(HW, device=dev), U1, U2, workspace=self._ws, want_srdf=False,
+                              pair=True)
+        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
+        out8 = ops.frame_metrics(out["rgb_coarse"], out["rgb"], f32(batch["ref_img"][0]), out["depth_coarse"], out["depth"],
+                                 f32(batch["depths_h"][0, 0]), fh.near_z, fh.far_z)
+        host = torch.cat([out8, self._variance_out().detach().double().reshape(1)]).cpu()    # the frame's one small copy
+        result = {k: float(host[i]) for i, k in enumerate(ops.FRAME_METRIC_KEYS[:6])}
+        result["val/variance"] = host[8:9].float().reshape(1, 1).numpy()
+        if logdir is not None:
+            scale = batch["scale_mat"][0][0, 0].to(dev, torch.float32)
+            # the reference saves the COARSE ray-length depth (depth_list_save, model.py:688) and the FINE colour (:690)
+            rgb8, depth8 = ops.frame_preview_u8(out["rgb"], out["depth_coarse"], out8[7:8], float(scale))
+            depths = out["depth_coarse"].view(imgH, imgW) * scale                            # model.py:734
+            meta = batch["meta"][0]
+            save_validation_outputs(logdir, meta.split("_")[0], meta.split("_")[-1], depths.cpu().numpy(),
+                                    rgb8.view(imgH, imgW, 3).cpu().numpy(), depth8.view(imgH, imgW).cpu().numpy(),
+                                    batch["w2cs"][0][0].cpu().numpy(), batch["intrinsics"][0][0].cpu().numpy())
+        return result
+
+
+def save_validation_outputs(logdir, scan_name, ref_view, depths, rgb8, depth8, extrinsic, intrinsic):
+    """What validation_step leaves under ``args.logdir`` (model.py:737-749), from bytes already made on the device:
+      <logdir>/<scan>/depth/<view>.png   depth8 (H,W) uint8
+      <logdir>/rgb/<scan>/<view>.jpg     rgb8 (H,W,3) uint8
+      <logdir>/depth/<scan>/<view>.npy   pickled dict {"depth": (H,W) f32, "extrinsic": 4x4, "intrinsic": 3x3}
+    ``scan`` / ``view`` are the first / last ``_`` field of the batch's meta ("scan24_light3_refview23" -> "refview23")."""
+    import os
+
+    from PIL import Image
+
+    os.makedirs(os.path.join(logdir, scan_name, "depth"), exist_ok=True)
+    os.makedirs(os.path.join(logdir, "depth", scan_name), exist_ok=True)
+    os.makedirs(os.path.join(logdir, "rgb", scan_name), exist_ok=True)
+    Image.fromarray(np.asarray(depth8, np.uint8)).save(os.path.join(logdir, scan_name, "depth", "%s.png" % ref_view))
+    Image.fromarray(np.asarray(rgb8, np.uint8)).save(os.path.join(logdir, "rgb", scan_name, "%s.jpg" % ref_view))
+    np.save(os.path.join(logdir, "depth", scan_name, "%s.npy" % ref_view),
+            {"depth": np.asarray(depths, np.float32), "extrinsic": np.asarray(extrinsic), "intrinsic": np.asarray(intrinsic)})
+
+
 def save_depth_outputs(out_dir, scan_name, ref_view, depths, rgbs, extrinsic, intrinsic):
     """The reference's wire format (model.py:828-842), byte for byte:
       <out_dir>/<scan>/depth/<view>.png   8-bit preview, depth / max(depth) * 255 (truncating cast)

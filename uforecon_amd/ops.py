@@ -629,9 +629,14 @@ class RenderWorkspace:
 
 def render_rays(frame: FrameHandle, weights: PackedWeights, ray_idx: torch.Tensor, U1: torch.Tensor,
                 U2: Optional[torch.Tensor], coarse_only: bool = False, workspace: Optional[RenderWorkspace] = None,
-                want_srdf: bool = True, out: Optional[dict] = None):
-    """UFORecon.infer(extract_geometry=True) for the rays `ray_idx` (RN,) of the prepared frame."""
-    if frame.cam_ray_d is None or frame.ray_d is None or frame.ray_o is None:
+                want_srdf: bool = True, out: Optional[dict] = None, pair: bool = False):
+    """UFORecon.infer(extract_geometry=True) for the rays `ray_idx` (RN,) of the prepared frame.
+
+    ``pair=True`` (ufr_render_rays_pair) also returns the coarse pass as ``rgb_coarse`` (RN,3) / ``depth_coarse`` (RN); on that
+    route a frame without ``cam_ray_d`` renders as infer(extract_geometry=False) does (near/far as given; ``depth_z`` is None)."""
+    if pair and coarse_only:
+        raise UfrError("render_rays: pair=True returns both passes; coarse_only renders one")
+    if frame.ray_d is None or frame.ray_o is None or (frame.cam_ray_d is None and not pair):
         raise UfrError("batch['ray_o'], ['ray_d'] and ['cam_ray_d'] are required for extract_geometry rendering")
     dev = frame.device
     RN = ray_idx.numel()
@@ -642,7 +647,7 @@ def render_rays(frame: FrameHandle, weights: PackedWeights, ray_idx: torch.Tenso
         workspace = RenderWorkspace(dev, SN, PN, frame.NV)
     o = out or {}
     depth = o.get("depth", torch.empty(RN, dtype=torch.float32, device=dev))
-    depth_z = o.get("depth_z", torch.empty(RN, dtype=torch.float32, device=dev))
+    depth_z = o.get("depth_z", torch.empty(RN, dtype=torch.float32, device=dev)) if frame.cam_ray_d is not None else None
     rgb = o.get("rgb", torch.empty(RN, 3, dtype=torch.float32, device=dev))
     srdf = torch.empty(RN, S, dtype=torch.float32, device=dev) if want_srdf else None
     z_all = torch.empty(RN, S, dtype=torch.float32, device=dev) if want_srdf else None
@@ -651,7 +656,7 @@ def render_rays(frame: FrameHandle, weights: PackedWeights, ray_idx: torch.Tenso
     a.packed_weights = weights.packed.data_ptr()
     a.raw = C.pointer(weights.raw)
     a.ray_idx = _dev(ray_idx.reshape(-1), "ray_idx", torch.int64)
-    a.ray_d, a.cam_ray_d = _dev(frame.ray_d, "ray_d"), _dev(frame.cam_ray_d, "cam_ray_d")
+    a.ray_d, a.cam_ray_d = _dev(frame.ray_d, "ray_d"), _opt(frame.cam_ray_d, "cam_ray_d")
     a.ray_o = (C.c_float * 3)(*frame.ray_o)
     a.near_z, a.far_z = frame.near_z, frame.far_z
     a.U1 = _dev(U1, "U1")
@@ -660,14 +665,67 @@ def render_rays(frame: FrameHandle, weights: PackedWeights, ray_idx: torch.Tenso
         raise UfrError("U1/U2 must be (samples, RN)")
     a.RN, a.SN, a.PN, a.coarse_only = RN, SN, PN, int(coarse_only)
     a.precision = weights.mode()
-    a.depth, a.depth_z, a.rgb = depth.data_ptr(), depth_z.data_ptr(), rgb.data_ptr()
+    a.depth, a.depth_z, a.rgb = depth.data_ptr(), _opt(depth_z, "depth_z"), rgb.data_ptr()
     a.srdf = _opt(srdf, "srdf")
     a.z_all = _opt(z_all, "z_all")
     a.chunk_rays = workspace.chunk
     a.n_streams = workspace.n_streams
     a.workspace, a.workspace_bytes = workspace.buf.data_ptr(), workspace.nbytes
-    _lib.check(_lib.load().ufr_render_rays(C.byref(a), _stream()), "ufr_render_rays")
-    return dict(depth=depth, depth_z=depth_z, rgb=rgb, srdf=srdf, z_all=z_all, workspace=workspace)
+    if not pair:
+        _lib.check(_lib.load().ufr_render_rays(C.byref(a), _stream()), "ufr_render_rays")
+        return dict(depth=depth, depth_z=depth_z, rgb=rgb, srdf=srdf, z_all=z_all, workspace=workspace)
+    rgb_coarse = o.get("rgb_coarse", torch.empty(RN, 3, dtype=torch.float32, device=dev))
+    depth_coarse = o.get("depth_coarse", torch.empty(RN, dtype=torch.float32, device=dev))
+    _lib.check(_lib.load().ufr_render_rays_pair(C.byref(a), _dev(rgb_coarse, "rgb_coarse"), _dev(depth_coarse, "depth_coarse"),
+                                                _stream()), "ufr_render_rays_pair")
+    return dict(depth=depth, depth_z=depth_z, rgb=rgb, srdf=srdf, z_all=z_all, workspace=workspace, rgb_coarse=rgb_coarse,
+                depth_coarse=depth_coarse)
+
+
+# ---- a validation frame's scores and previews (csrc/frame_metrics.hip; pipeline.validation_step is the caller)
+FRAME_METRIC_KEYS = ("val/loss_rgb_coarse", "val/loss_rgb_fine", "psnr/coarse", "psnr/fine", "val/loss_depth_coarse",
+                     "val/loss_depth_fine", "valid_pixels", "depth_coarse_max")
+
+
+def frame_metrics(rgb_c: torch.Tensor, rgb_f: torch.Tensor, rgb_gt: torch.Tensor, depth_c: torch.Tensor, depth_f: torch.Tensor,
+                  depth_gt: torch.Tensor, near: float, far: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ufr_frame_metrics: the eight float64 values of FRAME_METRIC_KEYS, on the device.  rgb_c / rgb_f (n,3), rgb_gt (3,n)
+    planar (any trailing shape with n elements per channel, e.g. batch['ref_img'][0]), depths n values each.  Does not
+    synchronise."""
+    n = depth_c.numel()
+    if n < 1 or rgb_c.numel() != 3 * n or rgb_f.numel() != 3 * n or rgb_gt.numel() != 3 * n or depth_f.numel() != n \
+            or depth_gt.numel() != n or rgb_gt.shape[0] != 3 or rgb_c.shape[-1] != 3 or rgb_f.shape[-1] != 3:
+        raise UfrError(f"frame_metrics: colours {tuple(rgb_c.shape)} {tuple(rgb_f.shape)} (n,3), ground truth {tuple(rgb_gt.shape)} "
+                       f"(3,n), depths {tuple(depth_c.shape)} {tuple(depth_f.shape)} {tuple(depth_gt.shape)} (n)")
+    lib = _lib.load()
+    dev = depth_c.device
+    out8 = torch.empty(8, dtype=torch.float64, device=dev) if out is None else out
+    ws = torch.empty(lib.ufr_frame_metrics_workspace_bytes(n) // 8, dtype=torch.float64, device=dev)
+    _lib.check(lib.ufr_frame_metrics(_dev(rgb_c, "rgb_c"), _dev(rgb_f, "rgb_f"), _dev(rgb_gt, "rgb_gt"), _dev(depth_c, "depth_c"),
+                                     _dev(depth_f, "depth_f"), _dev(depth_gt, "depth_gt"), float(near), float(far), n,
+                                     _dev(out8, "out8", torch.float64), ws.data_ptr(), _stream()), "ufr_frame_metrics")
+    return out8
+
+
+def frame_preview_u8(rgb: Optional[torch.Tensor], depth: Optional[torch.Tensor] = None, depth_max: Optional[torch.Tensor] = None,
+                     depth_scale: float = 1.0):
+    """ufr_frame_preview_u8: (rgb8 (n,3) uint8 = (rgb * 255).astype(uint8), depth8 (n) uint8 = ((depth * depth_scale) / (max *
+    depth_scale) * 255).astype(uint8)) in numpy's float32 arithmetic; ``depth_max``: a one-element float64 CUDA tensor
+    (frame_metrics(...)[7:8]).  Either half may be None.  Does not synchronise."""
+    src = rgb if rgb is not None else depth
+    if src is None:
+        raise UfrError("frame_preview_u8: nothing to do (rgb and depth are both None)")
+    n = src.numel() // 3 if rgb is not None else src.numel()
+    if (rgb is not None and (rgb.shape[-1] != 3 or rgb.numel() != 3 * n)) or (depth is not None and depth.numel() != n) \
+            or (depth is not None) != (depth_max is not None) or (depth_max is not None and depth_max.numel() != 1):
+        raise UfrError("frame_preview_u8: rgb (n,3), depth (n) with a one-element depth_max")
+    rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=src.device) if rgb is not None else None
+    depth8 = torch.empty(n, dtype=torch.uint8, device=src.device) if depth is not None else None
+    _lib.check(_lib.load().ufr_frame_preview_u8(
+        _opt(rgb, "rgb"), _opt(depth, "depth"), None if depth_max is None else _dev(depth_max, "depth_max", torch.float64),
+        float(depth_scale), n, None if rgb8 is None else rgb8.data_ptr(), None if depth8 is None else depth8.data_ptr(), _stream()),
+        "ufr_frame_preview_u8")
+    return rgb8, depth8
 
 
 def fmt_layer(params, x: torch.Tensor, src: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1252,6 +1310,25 @@ def pixel_rays(m_inv, H: int, W: int, origin=None, device="cuda") -> torch.Tenso
     with torch.cuda.device(device):
         out = torch.empty((3, max(H, 0) * max(W, 0)), dtype=torch.float32, device=device)
         _lib.check(_lib.load().ufr_pixel_rays(m.ctypes.data_as(fp), po, H, W, out.data_ptr(), _stream()), "ufr_pixel_rays")
+    return out
+
+
+def depth_gt_prepare(pfm_rows: torch.Tensor, bottom_up: bool, y0: int, x0: int, H: int, W: int, scale_factor: float,
+                     cam_ray_z: torch.Tensor) -> torch.Tensor:
+    """ufr_depth_gt_prepare: (H,W) float32 ground-truth ray depth of one training view from the (Hs,Ws) float32 rows of its PFM
+    file as stored (``bottom_up``: the file's first row is the picture's last): nearest half-size picture, crop at (y0, x0),
+    x ``scale_factor`` in float32, / ``cam_ray_z`` (H*W float64: row 2 of the float64 cam_ray_d) in float64.  Does not
+    synchronise; uforecon_amd.dtu_train has the host form."""
+    p = _dev(pfm_rows, "pfm_rows")
+    if pfm_rows.dim() != 2:
+        raise UfrError(f"pfm_rows: expected (Hs, Ws), got {tuple(pfm_rows.shape)}")
+    H, W = int(H), int(W)
+    z = _dev(cam_ray_z, "cam_ray_z", torch.float64)
+    if cam_ray_z.numel() != max(H, 0) * max(W, 0):
+        raise UfrError(f"cam_ray_z: {cam_ray_z.numel()} values for {H}x{W} pixels")
+    out = torch.empty((max(H, 0), max(W, 0)), dtype=torch.float32, device=pfm_rows.device)
+    _lib.check(_lib.load().ufr_depth_gt_prepare(p, int(pfm_rows.shape[0]), int(pfm_rows.shape[1]), int(bool(bottom_up)), int(y0), int(x0),
+                                                H, W, float(scale_factor), z, out.data_ptr(), _stream()), "ufr_depth_gt_prepare")
     return out
 
 

@@ -48,9 +48,11 @@ class UFOReconInference(M.UFORecon):
         return imgs, pm, depth_values.expand(imgs.shape[0], -1)
 
     @torch.no_grad()
-    def encode_frame(self, batch):
+    def encode_frame(self, batch, cur_n_src_views=None):
         """model.py:775-806: everything `infer` needs besides the batch itself.  Returns (source_imgs_feat (B,V,32,h,w),
-        feature_volume dict, match_feature list) and sets batch['depth_info']."""
+        feature_volume dict, match_feature list) and sets batch['depth_info'].  ``cur_n_src_views`` is what the caller hands
+        `get_match_feat`: args.test_n_view by default (extract_geometry, model.py:785), args.train_n_view - 1 in validation
+        (model.py:644)."""
         imgs, pm, dv = self.build_pairs(batch["source_imgs"], batch["proj_matrices"], batch["depth_values_org_scale"])
         H, W = imgs.shape[-2:]
         # TransMVSNet.py:175-178 runs the backbone on view v of every rotation, i.e. on each source image N times; one
@@ -70,7 +72,7 @@ class UFOReconInference(M.UFORecon):
             frustums[st] = {"feature_volume": f, "weight_volume": w}
         for f in feats:
             f["stage1"] = f["stage1"][0:1]                                                        # :782-783
-        match_feature = self.transmvsnet.get_match_feat(feats, cur_n_src_views=self.args.test_n_view)   # :785
+        match_feature = self.transmvsnet.get_match_feat(feats, cur_n_src_views=self.args.test_n_view if cur_n_src_views is None else cur_n_src_views)   # :785
         source_imgs_feat = torch.stack([f["stage1"] for f in feats], dim=1)                       # :787-790
         if getattr(self.args, "mvs_depth_guide", 1) > 0:                                          # :804-806
             batch["depth_info"] = (volume_info["stage3"]["depth"] * batch["scale_factor"]).unsqueeze(0)
@@ -83,3 +85,29 @@ class UFOReconInference(M.UFORecon):
         out_dir = out_dir if out_dir is not None else getattr(self.args, "out_dir", None)
         return M.UFORecon.extract_geometry(self, batch, source_imgs_feat, frustums, match_feature, out_dir=out_dir,
                                            uniforms=uniforms)
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0, logdir=None, uniforms=None):
+        """code1/model.py:607-758 for a train-layout batch (dtu_train.py:442-495) of one frame: the reference view rendered
+        in full through both passes and scored against the ground truth.  Returns the reference's dict -- val/loss_rgb_coarse,
+        val/loss_rgb_fine, val/loss_depth_coarse, val/loss_depth_fine, psnr/coarse, psnr/fine (floats) and val/variance -- and
+        writes its three files under ``logdir`` (default args.logdir; None: no files)."""
+        if batch["source_imgs"].shape[0] != 1:
+            raise M.UfrError(f"validation_step: one frame per call (B=1), got B={batch['source_imgs'].shape[0]}: the reference's own "
+                             "file writing reads element 0 only")
+        source_imgs_feat, frustums, match_feature = self.encode_frame(batch, cur_n_src_views=self.args.train_n_view - 1)
+        logdir = logdir if logdir is not None else getattr(self.args, "logdir", None)
+        return self.validation_frame(batch, source_imgs_feat, frustums, match_feature, logdir=logdir, uniforms=uniforms)
+
+    @staticmethod
+    def validation_epoch_end(batch_parts):
+        """code1/model.py:578-604: the plain means of the frames' scores under the names the reference logs, and its return
+        value ``loss`` = val/rgb_coarse + val/rgb_fine."""
+        if not batch_parts:
+            raise M.UfrError("validation_epoch_end: no frames")
+        mean = lambda k: sum(p[k] for p in batch_parts) / len(batch_parts)  # noqa: E731
+        out = {"psnr/coarse": mean("psnr/coarse"), "psnr/fine": mean("psnr/fine"), "val/rgb_coarse": mean("val/loss_rgb_coarse"),
+               "val/rgb_fine": mean("val/loss_rgb_fine"), "val/loss_depth_coarse": mean("val/loss_depth_coarse"),
+               "val/loss_depth_fine": mean("val/loss_depth_fine")}
+        out["loss"] = out["val/rgb_coarse"] + out["val/rgb_fine"]
+        return out

@@ -1,0 +1,140 @@
+"""Validation scores of a checkpoint on the DTU training layout: what `trainer.validate` runs in the reference's main.py
+(:112-135, 222-224 with model.py:578-758), under main.py's flag names.
+
+    python -m uforecon_amd.validate --root_dir DTU_TRAINING --split_filepath lists/test.txt --load_ckpt uforecon.ckpt \\
+        --logdir OUT --volume_type correlation --depth_pos_encoding --mvs_depth_guide 1 --explicit_similarity \\
+        --test_n_view 3 --train_n_view 5 --test_ref_view 23 24 33 --view_selection_type best
+
+For every item of `dtu_train.DtuTrain` -- the 'test' split with `--test_ref_view`, or with `--val_only` the 'train' split
+(main.py:224 validates the training loader) -- `pipeline.UFOReconInference.validation_step` renders the reference view through
+both passes, scores it and writes `<logdir>/<scan>/depth/<view>.png`, `<logdir>/rgb/<scan>/<view>.jpg` and
+`<logdir>/depth/<scan>/<view>.npy`.  One line per frame; the epoch means (`validation_epoch_end`) go out as one JSON line and as
+`<logdir>/val_metrics.json`; `val/loss_depth_fine` is what main.py:197-203 keeps checkpoints by.  The sampler's uniforms of a frame
+come from a generator seeded by (`--seed`, scan, view): a rerun gives the same numbers.  The checkpoint load is strict.  A flag
+value the mirror does not implement ends the command with one line, exit code 2.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import re
+import sys
+
+import torch
+
+from ._lib import MAX_VIEWS
+from .extract_geometry import IMPLEMENTED, PRECISIONS, load_checkpoint, view_uniforms
+
+
+def make_parser():
+    """main.py's training / validation flags with main.py's defaults, then this project's own."""
+    parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    parser.add_argument("--root_dir", dest="root_dir", type=str, help="directory of dataset")
+    parser.add_argument("--load_ckpt", dest="load_ckpt", type=str, default=False, help="load pretrained lightning ckpt")
+    parser.add_argument("--logdir", default="./checkpoints/random_sample", help="the directory to save checkpoints/logs")
+    parser.add_argument("--val_only", dest="val_only", action="store_true", help="only validate: on the train split, as main.py does")
+    parser.add_argument("--train_ray_num", dest="train_ray_num", type=int, default=1024, help="accepted and ignored: chunking is internal")
+    parser.add_argument("--coarse_sample", dest="coarse_sample", type=int, default=64, help="number of coarse samples during training")
+    parser.add_argument("--fine_sample", dest="fine_sample", type=int, default=64, help="number of fine samples during training")
+    parser.add_argument("--test_n_view", dest="test_n_view", type=int, default=3)
+    parser.add_argument("--train_n_view", dest="train_n_view", type=int, default=5)
+    parser.add_argument("--test_ref_view", type=int, nargs="+", default=[23, 24, 33, 22, 15, 34, 14, 32, 16, 35, 25])
+    parser.add_argument("--ndepths", type=str, default="48,32,8", help="ndepths")
+    parser.add_argument("--depth_inter_r", type=str, default="4,2,1", help="depth_intervals_ratio")
+    parser.add_argument("--cr_base_chs", type=str, default="8,8,8", help="cost regularization base channels")
+    parser.add_argument("--view_selection_type", type=str, default="random", choices=["random", "best"])
+    parser.add_argument("--mvs_depth_guide", type=int, default=0, help="use mvs depth map as guidance")
+    parser.add_argument("--volume_type", type=str, default="correlation", choices=["featuregrid", "correlation"])
+    parser.add_argument("--volume_reso", dest="volume_reso", type=int, default=96, help="accepted and ignored (featuregrid only)")
+    parser.add_argument("--use_dir_srdf", action="store_true", help="use direction srdf")
+    parser.add_argument("--depth_pos_encoding", action="store_true", help="use depth pos encoding")
+    parser.add_argument("--explicit_similarity", action="store_true", help="use explicit similarity")
+    # ---- this project's own
+    parser.add_argument("--split_filepath", type=str, default=None, help="a file with one scan name per line")
+    parser.add_argument("--scans", type=str, nargs="+", default=None, help="scan names (instead of --split_filepath)")
+    parser.add_argument("--pair_filepath", type=str, default=None, help="default: <root_dir>/Cameras/pair.txt")
+    parser.add_argument("--max_frames", type=int, default=0, help="stop after this many frames (0: all)")
+    parser.add_argument("--seed", type=int, default=0, help="seed of the samplers' uniforms and of the random view selection")
+    parser.add_argument("--precision", choices=sorted(PRECISIONS), default="default", help="matrix precision of the ray path")
+    return parser
+
+
+def unimplemented(args):
+    """One line naming the first flag value outside what the mirror implements, or None."""
+    for flag, want in IMPLEMENTED.items():
+        if getattr(args, flag) != want:
+            return f"--{flag} {getattr(args, flag)!r} is not implemented here (only {want!r}: what the reference's scripts pass)"
+    if args.mvs_depth_guide <= 0:
+        return "--mvs_depth_guide 0 is not implemented here (the ray path reads the MVS depth: pass --mvs_depth_guide 1)"
+    n_src = args.train_n_view - 1 if args.val_only else len(args.test_ref_view)
+    if not 2 <= n_src <= MAX_VIEWS:
+        what = f"--train_n_view {args.train_n_view}" if args.val_only else f"--test_ref_view with {len(args.test_ref_view)} views"
+        return f"{what} is not implemented here ({n_src} source views per frame; the ray path takes 2 .. {MAX_VIEWS})"
+    if n_src != args.train_n_view - 1:
+        # model.py:644 builds the matching features for train_n_view - 1 sources whatever the batch holds
+        return (f"--train_n_view {args.train_n_view} is not implemented here with {n_src} source views per frame: validation "
+                f"builds its matching features for train_n_view - 1 = {args.train_n_view - 1} sources (pass --train_n_view {n_src + 1})")
+    return None
+
+
+def main(argv=None):
+    from .dtu_train import DtuTrain
+    from .pipeline import UFOReconInference
+
+    parser = make_parser()
+    args = parser.parse_args(argv)
+    why = unimplemented(args)
+    if why is None and not args.root_dir:
+        why = "--root_dir is required"
+    if why is None and not (args.split_filepath or args.scans):
+        why = "--split_filepath or --scans is required"
+    if why is not None:
+        parser.error(why)
+    args.extract_geometry = False
+    dev = torch.device("cuda:0")
+    net = UFOReconInference(args)
+    if args.load_ckpt:
+        load_checkpoint(net, args.load_ckpt)
+        print("Model loaded:", args.load_ckpt)
+    else:
+        print("no --load_ckpt: the model keeps its initial weights", file=sys.stderr)
+    net = net.to(dev)
+    net.precision = PRECISIONS[args.precision]
+    try:
+        if args.val_only:
+            ds = DtuTrain(args.root_dir, "train", n_views=args.train_n_view, split_filepath=args.split_filepath, scans=args.scans,
+                          pair_filepath=args.pair_filepath, view_selection_type=args.view_selection_type, device=dev, seed=args.seed)
+        else:
+            ds = DtuTrain(args.root_dir, "test", n_views=args.test_n_view, split_filepath=args.split_filepath, scans=args.scans,
+                          pair_filepath=args.pair_filepath, test_ref_views=args.test_ref_view,
+                          view_selection_type=args.view_selection_type, device=dev, seed=args.seed)
+    except FileNotFoundError as e:
+        parser.error(f"{e.filename} is missing (--root_dir {args.root_dir})")
+    parts = []
+    for i in range(len(ds) if args.max_frames <= 0 else min(len(ds), args.max_frames)):
+        scan, light, view, _ = ds.metas[i]
+        try:
+            batch = ds[i]
+        except FileNotFoundError as e:
+            parser.error(f"{e.filename} is missing (--root_dir {args.root_dir})")
+        H, W = batch["source_imgs"].shape[-2:]
+        digits = re.sub(r"\D", "", str(scan))
+        U = view_uniforms(args.seed, int(digits) if digits else i, view * 7 + light, net.point_num, net.point_num_2, H * W)
+        r = net.validation_step(batch, i, logdir=args.logdir, uniforms=U)
+        parts.append(r)
+        print("%s psnr %.3f / %.3f  rgb %.6f / %.6f  depth %.6f / %.6f" % (
+            batch["meta"][0], r["psnr/coarse"], r["psnr/fine"], r["val/loss_rgb_coarse"], r["val/loss_rgb_fine"],
+            r["val/loss_depth_coarse"], r["val/loss_depth_fine"]))
+    if not parts:
+        parser.error("no frames: the split and --test_ref_view select nothing")
+    end = dict(net.validation_epoch_end(parts), frames=len(parts))
+    os.makedirs(args.logdir, exist_ok=True)
+    with open(os.path.join(args.logdir, "val_metrics.json"), "w") as f:
+        json.dump(end, f, indent=1)
+    print(json.dumps(end))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
