@@ -815,6 +815,45 @@ int ufr_image_resize_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, i
                         ufr_stream stream);
 int ufr_pixel_rays(const float* m_inv, const float* origin, int32_t H, int32_t W, float* dir, ufr_stream stream);
 
+/* ---- the optimizer update and the ray draw of a training step (ABI 507, additive) ----------------------------
+ * What UFORecon.training_step / configure_optimizers (code1/model.py:72-87, 537) run around the ray path, each as one call.
+ * Neither synchronises; every argument error is UFR_ERR_ARG with the reason in the thread's last-error text.
+ *
+ * ufr_adam_step: torch.optim.Adam with its defaults (no weight decay, no amsgrad, no maximize) for n_tensors tensors in
+ *   ceil(n_tensors / UFR_ADAM_TABLE_CAPACITY) launches.  Per tensor (device fp32, numel elements each, 0 <= numel < 2^31):
+ *     exp_avg    += (grad - exp_avg) (1 - beta1)
+ *     exp_avg_sq  = beta2 exp_avg_sq + (1 - beta2) grad^2
+ *     param      -= (lr / bias_correction1) exp_avg / (sqrt(exp_avg_sq) / sqrt(bias_correction2) + eps)
+ *   bias_correction1 / 2 = 1 - beta1^step / 1 - beta2^step for THAT tensor's step count (after this step), formed by the
+ *   caller in double: a tensor without a gradient is left out of a call and its count does not advance, so the counts of
+ *   one call may differ.  lr / bias_correction1 and sqrt(bias_correction2) are formed in double and rounded to fp32, the
+ *   rest is fp32.  The table is HOST memory, read before the call returns; it travels to the kernel in the launch's own
+ *   arguments (no staging buffer).  The grid is split over elements, one block per 4096 elements of one tensor.  Pointers
+ *   need 4-byte alignment only: a tensor whose four pointers are all 16-byte aligned is updated with 16-byte accesses, any
+ *   other one with 4-byte accesses.  No two tensors of a call may overlap.
+ * ufr_select_rays: idx_out[0..k) (device int64) = the first k entries of the STABLE ascending argsort of u[0..n) (device
+ *   fp32) -- argsort(rand(H W))[:train_ray_num] of model.py:537 with equal values in index order.  The order is that of
+ *   the values' bit patterns as unsigned integers: the floats' own order for non-negative, non-NaN input; for any other
+ *   input the result is still k distinct indices in [0, n).  A radix select over the patterns (three digit passes), an
+ *   ordered compaction of the k smallest and one block sorting them; integer counters only, so a rerun gives the same
+ *   bits.  1 <= k <= min(n, 4096), n <= 2^24.  workspace >= ufr_select_rays_workspace_bytes(n, k) (device, 8-byte
+ *   aligned; 0 and an error text for sizes outside the range). */
+#define UFR_ADAM_TABLE_CAPACITY 64
+typedef struct ufr_adam_tensor {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t numel;
+  double bias_correction1, bias_correction2;
+} ufr_adam_tensor;
+int32_t ufr_adam_table_capacity(void);
+int ufr_adam_step(const ufr_adam_tensor* tensors, int32_t n_tensors, double lr, double beta1, double beta2, double eps,
+                  ufr_stream stream);
+size_t ufr_select_rays_workspace_bytes(int32_t n, int32_t k);
+int ufr_select_rays(const float* u, int32_t n, int32_t k, int64_t* idx_out, void* workspace, size_t workspace_bytes,
+                    ufr_stream stream);
+
 /* Pixel-wise view weights of the first cascade stage and the weighted aggregate (DepthNet.forward,
  * code1/encoder_utils/fmt/TransMVSNet.py:80-97 with PixelwiseNet :23-41), one pass over the similarity volume:
  *   view_weights[i] = max_d sigmoid(conv2(relu(bn1(conv1(relu(bn0(conv0(similarity[i]))))))))      (1x1x1 convolutions)

@@ -63,6 +63,11 @@ class RenderArgs(C.Structure):
                 ("chunk_rays", C.c_int32), ("n_streams", C.c_int32), ("workspace", fptr), ("workspace_bytes", C.c_size_t)]
 
 
+class AdamTensor(C.Structure):
+    _fields_ = [("param", fptr), ("grad", fptr), ("exp_avg", fptr), ("exp_avg_sq", fptr), ("numel", C.c_int64),
+                ("bias_correction1", C.c_double), ("bias_correction2", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/ufr.h declares
 i32, i64, sz, vp = C.c_int32, C.c_int64, C.c_size_t, C.c_void_p
 SIGNATURES = {
@@ -167,6 +172,10 @@ SIGNATURES = {
     "ufr_raster_downsample": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
     "ufr_image_resize_u8": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),
     "ufr_pixel_rays": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, vp, vp]),
+    "ufr_adam_table_capacity": (i32, []),
+    "ufr_adam_step": (C.c_int, [C.POINTER(AdamTensor), i32, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    "ufr_select_rays_workspace_bytes": (sz, [i32, i32]),
+    "ufr_select_rays": (C.c_int, [vp, i32, i32, vp, vp, sz, vp]),
     "ufr_pixelwise_view_weights": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "ufr_deform_conv2d_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ufr_deform_conv2d": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),

@@ -251,5 +251,18 @@ hipError_t launch_pixelwise_weights(const float* sim, const float* params, float
                                     hipStream_t s);
 hipError_t launch_correlate(const float* ref_cl, const float* src_cl, const float* proj_host, int NS, const float* depth,
                             const float* vw, float* sim, float* agg, int C, int H, int W, int D, hipStream_t s);
+// train_step.hip: the optimizer update and the ray draw of a training step (see the file header)
+constexpr int kAdamTableCap = UFR_ADAM_TABLE_CAPACITY;   // tensors per launch
+constexpr int kSelectMaxK = 4096;                        // pairs the sorting block holds in LDS
+struct SelectWorkspace {
+  uint32_t* hist;              // [3][2048] digit counters, then 4 words of state
+  int* totals;                 // [blocks][2]
+  long long* off;              // [blocks][2]
+  long long* grand;            // [2]
+  unsigned long long* cand;    // [k]
+};
+int select_compact_blocks(int n);
+hipError_t launch_adam(const ufr_adam_tensor* t, int nt, double lr, double beta1, double beta2, double eps, hipStream_t s);
+hipError_t launch_select_rays(const float* u, int n, int k, long long* idx_out, const SelectWorkspace& w, hipStream_t s);
 
 }  // namespace ufr

@@ -179,11 +179,10 @@ class DtuTrain:
                 return ops.image_resize_u8(torch.from_numpy(raw).to(self.device), self.img_H, self.img_W)
         return torch.from_numpy(image_planes_host(raw, self.img_H, self.img_W))
 
-    def _depths(self, files, scale_factor, cam_ray_z):
+    def _depths(self, decoded, scale_factor, cam_ray_z):
         y0, x0 = PFM_CROP
         out = []
-        for fn in files:
-            rows, bottom_up = read_pfm_rows(fn)
+        for rows, bottom_up in decoded:
             if self.device.type == "cuda":
                 from . import ops
 
@@ -196,19 +195,33 @@ class DtuTrain:
 
     # ---- dtu_train.py:318-498
     def __getitem__(self, idx):
+        return self.finish(idx, self.load(idx))
+
+    def load(self, idx):
+        """The files of item ``idx``, decoded: (its pictures (uint8 arrays), its depth maps' (rows, bottom_up)).  Host work on
+        host memory that touches no state of the loader, so a worker thread may run it ahead of `finish` (train.Prefetch)."""
         meta = self.metas[idx % len(self.metas)]
-        scan, light_idx, ref_view, _ = meta
-        view_ids = self._view_ids(meta)
-        w2c_ref_inv = np.linalg.inv(self.all_extrinsics[ref_view])
-        raw, depth_files, intrinsics, w2cs, near_fars, proj_matrices = [], [], [], [], [], []
-        for i, vid in enumerate(view_ids):
+        scan, light_idx, _, _ = meta
+        raw, depths = [], []
+        for vid in self._view_ids(meta):
             img = imread_rgb(os.path.join(self.root_dir, f"Rectified/{scan}_train/rect_{vid + 1:03d}_{light_idx}_r5000.png"))
             if img.shape != (self.img_H, self.img_W, 3):
                 raise ValueError(f"DtuTrain: {scan} view {vid} is {img.shape[1]}x{img.shape[0]}, expected {self.img_W}x{self.img_H}")
             raw.append(img)
             depth_filename = os.path.join(self.root_dir, f"Depths_raw/{scan}/depth_map_{vid:04d}.pfm")
             if os.path.exists(depth_filename):
-                depth_files.append(depth_filename)
+                depths.append(read_pfm_rows(depth_filename))
+        return raw, depths
+
+    def finish(self, idx, loaded):
+        """Item ``idx``'s batch from its decoded files: ``ds[idx]`` is ``ds.finish(idx, ds.load(idx))``."""
+        meta = self.metas[idx % len(self.metas)]
+        scan, light_idx, ref_view, _ = meta
+        view_ids = self._view_ids(meta)
+        raw, depth_rows = loaded
+        w2c_ref_inv = np.linalg.inv(self.all_extrinsics[ref_view])
+        intrinsics, w2cs, near_fars, proj_matrices = [], [], [], []
+        for i, vid in enumerate(view_ids):
             near_fars.append(self.all_near_fars[vid])
             intrinsics.append(self.all_intrinsics[vid])
             w2cs.append(self.all_extrinsics[vid] @ w2c_ref_inv)
@@ -276,7 +289,7 @@ class DtuTrain:
         batch["images"] = images[None]
         batch["ref_img"], batch["source_imgs"] = images[0][None], images[1:][None]
         batch["ray_d"], batch["cam_ray_d"] = ray_d[None], cam_ray_d[None]
-        batch["depths_h"] = self._depths(depth_files, float(np.float32(scale_factor)), cam_ray_z)[None]
+        batch["depths_h"] = self._depths(depth_rows, float(np.float32(scale_factor)), cam_ray_z)[None]
         batch["proj_matrices"] = {k: torch.from_numpy(v)[None].to(self.device)
                                   for k, v in (("stage1", proj_matrices), ("stage2", stage2), ("stage3", stage3))}
         batch["meta"] = [str(scan) + "_light" + str(light_idx) + "_refview" + str(ref_view)]

@@ -1555,3 +1555,101 @@ def conv3d_bwd_weight(x_cl: torch.Tensor, d_out_cl: torch.Tensor, mode: int, wei
                                                  B, D, H, W, cin, cout, int(mode), _stream()), "ufr_conv3d_bwd_weight")
     return dw, db
 
+
+
+# ---------------------------------------------------------------- the optimizer update and the ray draw of a training step
+def adam_table_capacity() -> int:
+    """Tensors one launch of ufr_adam_step carries (UFR_ADAM_TABLE_CAPACITY)."""
+    return int(_lib.load().ufr_adam_table_capacity())
+
+
+@torch.no_grad()
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, bias_corrections1, bias_corrections2, lr: float, beta1: float = 0.9,
+              beta2: float = 0.999, eps: float = 1e-8) -> None:
+    """torch.optim.Adam's update with its defaults for a list of fp32 tensors, in place: ufr_adam_step (one launch per
+    ``adam_table_capacity()`` tensors) on the GPU; on CPU tensors the same formula as torch expressions -- the statement of
+    what the kernel computes.  ``bias_corrections1 / 2``: per tensor 1 - beta^step of ITS step count, python floats.  The
+    kernel writes through raw pointers, so the version counters of the tensors it changed are advanced here: caches keyed on
+    them (RayTransformer.packed_weights, the convolutions' weight planes) and autograd's saved-tensor check see the update."""
+    import math
+
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(bias_corrections1) == len(bias_corrections2) == n):
+        raise UfrError("adam_step: the six lists differ in length")
+    if n == 0:
+        return
+    if not params[0].is_cuda:
+        for p, g, m, v, bc1, bc2 in zip(params, grads, exp_avgs, exp_avg_sqs, bias_corrections1, bias_corrections2):
+            if p.is_cuda or p.dtype != torch.float32:
+                raise UfrError("adam_step: fp32 tensors, all on the CPU or all on the GPU")
+            m.add_((g - m) * (1.0 - beta1))
+            v.mul_(beta2).add_(g * g * (1.0 - beta2))
+            p.sub_((lr / bc1) * (m / (v.sqrt() / math.sqrt(bc2) + eps)))
+        return
+    AdamTable(params, exp_avgs, exp_avg_sqs).step(grads, bias_corrections1, bias_corrections2, lr, beta1, beta2, eps)
+
+
+class AdamTable:
+    """The ufr_adam_tensor table of a fixed set of GPU tensors (parameter, exp_avg, exp_avg_sq), checked and filled once: a
+    step then sets the gradients' addresses and the bias corrections and makes the call -- the host's share of an optimizer
+    step is most of it (~62 small tensors).  Holds the tensors, so none of the addresses it recorded can be handed to another
+    allocation; `current()` says whether the parameters still live where they did (`.to()`, `p.data = ...` move them)."""
+
+    def __init__(self, params, exp_avgs, exp_avg_sqs):
+        n = len(params)
+        if not (len(exp_avgs) == len(exp_avg_sqs) == n):
+            raise UfrError("adam_step: the lists differ in length")
+        self.params = list(params)
+        self.tensors = self.params + list(exp_avgs) + list(exp_avg_sqs)
+        self.table = (_lib.AdamTensor * n)()
+        self.rows = list(self.table)           # views of the table's rows
+        for i, (e, p, m, v) in enumerate(zip(self.rows, params, exp_avgs, exp_avg_sqs)):
+            if m.shape != p.shape or v.shape != p.shape:
+                raise UfrError(f"adam_step: tensor {i}: parameter {tuple(p.shape)}, state {tuple(m.shape)} {tuple(v.shape)}")
+            e.param, e.exp_avg, e.exp_avg_sq, e.numel = _dev(p, "param"), _dev(m, "exp_avg"), _dev(v, "exp_avg_sq"), p.numel()
+        self.param_ptrs = [p.data_ptr() for p in self.params]
+
+    def current(self) -> bool:
+        return self.param_ptrs == [p.data_ptr() for p in self.params]
+
+    @torch.no_grad()
+    def step(self, grads, bias_corrections1, bias_corrections2, lr: float, beta1: float = 0.9, beta2: float = 0.999,
+             eps: float = 1e-8) -> None:
+        n = len(self.rows)
+        if not (len(grads) == len(bias_corrections1) == len(bias_corrections2) == n):
+            raise UfrError("adam_step: the lists differ in length")
+        if n == 0:
+            return
+        keep = []
+        for e, p, g, b1, b2 in zip(self.rows, self.params, grads, bias_corrections1, bias_corrections2):
+            if g.shape != p.shape:
+                raise UfrError(f"adam_step: parameter {tuple(p.shape)}, gradient {tuple(g.shape)}")
+            if not g.is_contiguous():
+                g = g.contiguous()
+                keep.append(g)
+            e.grad, e.bias_correction1, e.bias_correction2 = _dev(g, "grad"), b1, b2
+        _lib.check(_lib.load().ufr_adam_step(self.table, n, float(lr), float(beta1), float(beta2), float(eps), _stream()), "ufr_adam_step")
+        torch.autograd.graph.increment_version(self.tensors)
+
+
+def select_rays(u: torch.Tensor, k: int) -> torch.Tensor:
+    """The first ``k`` entries of the stable ascending argsort of the 1-D fp32 tensor ``u`` (int64): model.py:537's
+    ``argsort(rand(H W))[:train_ray_num]`` with equal values in index order.  GPU: ufr_select_rays (1 <= k <= min(n, 4096),
+    n <= 2^24; no synchronisation); CPU: ``torch.sort(stable=True)``, the statement of what the kernels compute."""
+    if not isinstance(u, torch.Tensor) or u.dim() != 1 or u.dtype != torch.float32:
+        raise UfrError("select_rays: u must be a 1-D float32 tensor")
+    n, k = u.numel(), int(k)
+    if not u.is_cuda:
+        if not 1 <= k <= n:
+            raise UfrError(f"select_rays: k={k} with n={n} (1 <= k <= n)")
+        return torch.sort(u, stable=True).indices[:k]
+    lib = _lib.load()
+    if n > 2 ** 31 - 1:
+        raise UfrError(f"select_rays: n={n}")
+    nbytes = lib.ufr_select_rays_workspace_bytes(n, k)
+    if nbytes == 0:
+        raise UfrError("ufr_select_rays failed (-1): " + lib.ufr_last_error().decode())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=u.device)
+    out = torch.empty(k, dtype=torch.int64, device=u.device)
+    _lib.check(lib.ufr_select_rays(_dev(u, "u"), n, k, out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "ufr_select_rays")
+    return out

@@ -52,7 +52,17 @@ class UFOReconInference(M.UFORecon):
         """model.py:775-806: everything `infer` needs besides the batch itself.  Returns (source_imgs_feat (B,V,32,h,w),
         feature_volume dict, match_feature list) and sets batch['depth_info'].  ``cur_n_src_views`` is what the caller hands
         `get_match_feat`: args.test_n_view by default (extract_geometry, model.py:785), args.train_n_view - 1 in validation
-        (model.py:644)."""
+        (model.py:644).  = the frozen half, then the frustum build, both without gradients."""
+        source_imgs_feat, cost_volumes, depth, match_feature = self.encode_frozen(batch, cur_n_src_views)
+        frustums = self.build_frustums(batch, cost_volumes)
+        self._set_depth_info(batch, depth)
+        return source_imgs_feat, frustums, match_feature
+
+    @torch.no_grad()
+    def encode_frozen(self, batch, cur_n_src_views=None):
+        """The half of `encode_frame` that `transmvsnet` computes (backbone, FMT, cascade) -- the half the reference freezes
+        (model.py:72-87), always without gradients.  Returns (source_imgs_feat (B,V,32,h,w), {stage: cost volume}, the
+        stage-3 depth, match_feature list)."""
         imgs, pm, dv = self.build_pairs(batch["source_imgs"], batch["proj_matrices"], batch["depth_values_org_scale"])
         H, W = imgs.shape[-2:]
         # TransMVSNet.py:175-178 runs the backbone on view v of every rotation, i.e. on each source image N times; one
@@ -66,17 +76,25 @@ class UFOReconInference(M.UFORecon):
             feats.append({st: base[st][idx] for st in ("stage1", "stage2", "stage3")})
         feats = self.transmvsnet.encode(feats, ref_idx=0)                                         # :181
         volume_info = self.transmvsnet(feats, pm, dv, (H, W))                                     # :183-236
-        frustums = {}
-        for st in ("stage1", "stage2", "stage3"):                                                 # model.py:795-802
-            f, w = self.feature_volume(batch, volume_info[st]["cost_volume"])
-            frustums[st] = {"feature_volume": f, "weight_volume": w}
         for f in feats:
             f["stage1"] = f["stage1"][0:1]                                                        # :782-783
         match_feature = self.transmvsnet.get_match_feat(feats, cur_n_src_views=self.args.test_n_view if cur_n_src_views is None else cur_n_src_views)   # :785
         source_imgs_feat = torch.stack([f["stage1"] for f in feats], dim=1)                       # :787-790
-        if getattr(self.args, "mvs_depth_guide", 1) > 0:                                          # :804-806
-            batch["depth_info"] = (volume_info["stage3"]["depth"] * batch["scale_factor"]).unsqueeze(0)
-        return source_imgs_feat, frustums, match_feature
+        cost_volumes = {st: volume_info[st]["cost_volume"] for st in ("stage1", "stage2", "stage3")}
+        return source_imgs_feat, cost_volumes, volume_info["stage3"]["depth"], match_feature
+
+    def build_frustums(self, batch, cost_volumes):
+        """model.py:795-802 / 517-524: the three stages' feature and weight frustums from `feature_volume.cost_reg_2`, the one
+        producer the reference trains.  Differentiable w.r.t. its parameters when gradients are on."""
+        frustums = {}
+        for st in ("stage1", "stage2", "stage3"):
+            f, w = self.feature_volume(batch, cost_volumes[st])
+            frustums[st] = {"feature_volume": f, "weight_volume": w}
+        return frustums
+
+    def _set_depth_info(self, batch, depth):
+        if getattr(self.args, "mvs_depth_guide", 1) > 0:                                          # model.py:804-806 / 529-531
+            batch["depth_info"] = (depth * batch["scale_factor"]).unsqueeze(0)
 
     @torch.no_grad()
     def extract_geometry(self, batch, batch_idx=0, out_dir=None, uniforms=None):
@@ -111,3 +129,62 @@ class UFOReconInference(M.UFORecon):
                "val/loss_depth_fine": mean("val/loss_depth_fine")}
         out["loss"] = out["val/rgb_coarse"] + out["val/rgb_fine"]
         return out
+
+
+class UFOReconTraining(UFOReconInference):
+    """The reference's training flow (code1/model.py:72-87, 492-575) on this code base: `configure_optimizers` and
+    `training_step` for one frame per step.
+
+    One stated difference from the reference: `train()` leaves `transmvsnet` in eval mode.  Under Lightning's `model.train()`
+    the reference's FROZEN TransMVSNet runs its BatchNorms on batch statistics and overwrites the checkpoint's running
+    statistics on every step, although none of its parameters train.  Here the frozen encoder stays on its running statistics
+    (`FeatureNet` and `CostRegNet` are inference-only kernels with the BatchNorms folded in), and its parameters and buffers
+    come out of training bit-identical."""
+
+    def train(self, mode: bool = True):
+        M.UFORecon.train(self, mode)          # the ray path and feature_volume
+        self.transmvsnet.eval()               # ... and never the frozen encoder
+        return self
+
+    def configure_optimizers(self):
+        """model.py:72-87: every `transmvsnet` parameter frozen, Adam over all others (the dead `pre_conv` among them: it never
+        gets a gradient, so it never gets a state or an update) at args.uforecon_lr."""
+        from . import optim
+
+        rest = []
+        for name, p in self.named_parameters():
+            if "transmvsnet" in name:
+                p.requires_grad = False
+            else:
+                rest.append(p)
+        return optim.Adam(rest, lr=self.args.uforecon_lr)
+
+    def training_step(self, batch, batch_idx=0, ray_idx=None, uniforms=None, generator=None):
+        """model.py:492-575 for one frame (B = 1) -> ``(loss, log)``: the frozen half without gradients, the three frustums
+        WITH, the ray draw, `infer`, `training_loss`.  ``ray_idx`` (1,RN) int64 and ``uniforms`` = (U1 (SN,RN), U2 (PN,RN)) pin
+        the step's randomness; by default the rays are `ops.select_rays` of H W device uniforms (model.py:537: the first
+        train_ray_num of their stable argsort) and the samplers' uniforms device draws, all from ``generator`` (a device
+        generator; None: the device's default).  ``log``: what the reference logs -- train/depth_ray_coarse, train/depth_ray_fine,
+        train/rgb_coarse, train/rgb_fine, train/loss_all, train/variance -- as detached device tensors: nothing in the step
+        waits for the device."""
+        B, _, _, H, W = batch["source_imgs"].shape
+        if B != 1:
+            raise M.UfrError(f"training_step: one frame per call (B=1), got B={B}: the frustum build and the ray draw are per frame")
+        dev = batch["source_imgs"].device
+        source_imgs_feat, cost_volumes, depth, match_feature = self.encode_frozen(batch, cur_n_src_views=self.args.train_n_view - 1)
+        frustums = self.build_frustums(batch, cost_volumes)
+        self._set_depth_info(batch, depth)
+        if ray_idx is None:
+            from . import ops
+
+            ray_idx = ops.select_rays(torch.rand(H * W, device=dev, generator=generator), self.args.train_ray_num)[None]
+        if uniforms is None:
+            RN = ray_idx.shape[1]
+            uniforms = (torch.rand(self.point_num, RN, device=dev, generator=generator),
+                        torch.rand(self.point_num_2, RN, device=dev, generator=generator))
+        r = self.infer(batch, ray_idx, source_imgs_feat, frustums, match_feature=match_feature, uniforms=uniforms)
+        loss, parts = self.training_loss(r, batch)
+        log = {"train/" + k: v for k, v in parts.items()}
+        log["train/loss_all"] = loss.detach()
+        log["train/variance"] = r[16].detach()
+        return loss, log

@@ -78,6 +78,27 @@ def unimplemented(args):
     return None
 
 
+def validate_frames(net, ds, args, max_frames, parser):
+    """`validation_step` on the first ``max_frames`` items of ``ds`` (0: all), one printed line per frame -> the list of their
+    score dicts.  (Also the validation pass of `uforecon_amd.train`.)"""
+    parts = []
+    for i in range(len(ds) if max_frames <= 0 else min(len(ds), max_frames)):
+        scan, light, view, _ = ds.metas[i]
+        try:
+            batch = ds[i]
+        except FileNotFoundError as e:
+            parser.error(f"{e.filename} is missing (--root_dir {args.root_dir})")
+        H, W = batch["source_imgs"].shape[-2:]
+        digits = re.sub(r"\D", "", str(scan))
+        U = view_uniforms(args.seed, int(digits) if digits else i, view * 7 + light, net.point_num, net.point_num_2, H * W)
+        r = net.validation_step(batch, i, logdir=args.logdir, uniforms=U)
+        parts.append(r)
+        print("%s psnr %.3f / %.3f  rgb %.6f / %.6f  depth %.6f / %.6f" % (
+            batch["meta"][0], r["psnr/coarse"], r["psnr/fine"], r["val/loss_rgb_coarse"], r["val/loss_rgb_fine"],
+            r["val/loss_depth_coarse"], r["val/loss_depth_fine"]))
+    return parts
+
+
 def main(argv=None):
     from .dtu_train import DtuTrain
     from .pipeline import UFOReconInference
@@ -111,21 +132,7 @@ def main(argv=None):
                           view_selection_type=args.view_selection_type, device=dev, seed=args.seed)
     except FileNotFoundError as e:
         parser.error(f"{e.filename} is missing (--root_dir {args.root_dir})")
-    parts = []
-    for i in range(len(ds) if args.max_frames <= 0 else min(len(ds), args.max_frames)):
-        scan, light, view, _ = ds.metas[i]
-        try:
-            batch = ds[i]
-        except FileNotFoundError as e:
-            parser.error(f"{e.filename} is missing (--root_dir {args.root_dir})")
-        H, W = batch["source_imgs"].shape[-2:]
-        digits = re.sub(r"\D", "", str(scan))
-        U = view_uniforms(args.seed, int(digits) if digits else i, view * 7 + light, net.point_num, net.point_num_2, H * W)
-        r = net.validation_step(batch, i, logdir=args.logdir, uniforms=U)
-        parts.append(r)
-        print("%s psnr %.3f / %.3f  rgb %.6f / %.6f  depth %.6f / %.6f" % (
-            batch["meta"][0], r["psnr/coarse"], r["psnr/fine"], r["val/loss_rgb_coarse"], r["val/loss_rgb_fine"],
-            r["val/loss_depth_coarse"], r["val/loss_depth_fine"]))
+    parts = validate_frames(net, ds, args, args.max_frames, parser)
     if not parts:
         parser.error("no frames: the split and --test_ref_view select nothing")
     end = dict(net.validation_epoch_end(parts), frames=len(parts))
