@@ -815,6 +815,49 @@ int ufr_image_resize_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, i
                         ufr_stream stream);
 int ufr_pixel_rays(const float* m_inv, const float* origin, int32_t H, int32_t W, float* dir, ufr_stream stream);
 
+/* ---- a custom scene's loader and converter (ABI 507, additive) ------------------------------------------------
+ * What GeneralFit (code1/dataset/general_fit.py) adds to the per-pixel work above, and the view selection of
+ * colmap2mvsnet.py (:379-408); uforecon_amd/general_scan.py and uforecon_amd/colmap2mvsnet.py are the callers.  Neither
+ * synchronises; every argument error is UFR_ERR_ARG with the reason in the thread's last-error text.
+ *
+ * ufr_image_resize_mask_u8: ufr_image_resize_u8's contract (sizes, clip4, limits, errors, the resize rule stated there) with a
+ *   second source, mask (n,Hs,Ws) uint8, device: colour and mask are each resized by that rule (the box mean included), and
+ *   each output is (float)(((double)v / 255.0) * ((double)m / 254.0)) -- general_fit.py:174-180; the 254 is the reference's
+ *   own and is kept, so a mask value of 255 gives slightly more than the colour.  A null mask is an error.
+ *
+ * ufr_view_pair_scores: score (N,N) fp64, device.  The N images' observation lists are CSR: offsets, HOST int64[N + 1], read
+ *   before the call returns (offsets[0] = 0, offsets[N] = n_obs, non-decreasing); obs, DEVICE int32[n_obs]: image i's
+ *   observations in file order are obs[offsets[i] .. offsets[i+1]), each the row of `points` of the 3-D point it saw or -1 for
+ *   none; an index may repeat.  points (M,3) and centres (N,3): device fp64.  For i < j, with c_i, c_j the centres:
+ *     score[i][j] = sum over the observations o of image i whose p = obs[o] is not -1 and occurs in image j's list of
+ *       term(p) = exp( -(theta - theta0)^2 / (2 sigma^2) ),  sigma = sigma1 if theta <= theta0 else sigma2,
+ *       theta   = (180 / pi) acos( ((c_i - p) . (c_j - p)) / |c_i - p| / |c_j - p| )      (degrees)
+ *   A point that occurs twice in image i counts twice; how often it occurs in image j does not matter.  score[j][i] is a copy
+ *   of score[i][j], not a second sum; the diagonal is 0.  The acos argument is clamped to [-1, 1]: where rounding carries it
+ *   past 1 the reference gets NaN and this gets the term of theta = 0 (a point AT a camera centre still gives NaN: 0 / 0).
+ *   All arithmetic is fp64, each product and sum rounded on its own.  One workgroup of 256 threads per pair: thread t adds the
+ *   terms of observations t, t + 256, ... in that order, the 256 partial sums are added in a fixed tree (lanes l + 32, 16, 8,
+ *   4, 2, 1 inside a wave, then (w0 + w1) + (w2 + w3)): the order depends on the list's length alone, there is no
+ *   floating-point atomic, and a rerun gives the same bits.  It is NOT the reference's order (one running sum in file
+ *   order): tests/test_gpu_view_select.py bounds the difference by what reversing that sum moves it.
+ *   Membership is a binary search in a per-image sorted copy of the lists, which THIS CALL makes on the device, in the
+ *   workspace (the caller passes no sorted copy).
+ *   obs_host: HOST copy of obs, nullable.  An entry point cannot read device memory without waiting for the stream, so the
+ *   range check of the indices runs on this copy, before anything is launched: an index outside [-1, M) is an argument error.
+ *   With a null obs_host the caller vouches for the range; the kernels treat an index outside 0 .. M-1 as -1 either way, so
+ *   no input makes them read outside `points`.
+ *   Errors: a null pointer (obs may be null when n_obs = 0, points when M = 0), N < 1, offsets that do not start at 0, end at
+ *   n_obs or decrease, an index outside [-1, M) in obs_host, sigma1 or sigma2 <= 0 or a non-finite parameter, a workspace
+ *   smaller than ufr_view_pair_scores_workspace_bytes(N, n_obs) (device; 0 and an error text for sizes outside the range).
+ *   1 <= N <= 32768, n_obs < 2^31, M < 2^31.  Enqueues ceil((N + 1) / 448) + 2 kernels (the offsets travel in launch
+ *   arguments) and one memset.                                                                                          */
+int ufr_image_resize_mask_u8(const uint8_t* src, const uint8_t* mask, int32_t n, int32_t Hs, int32_t Ws, int32_t H, int32_t W,
+                             const int32_t* clip4, float* dst, ufr_stream stream);
+size_t ufr_view_pair_scores_workspace_bytes(int32_t N, int64_t n_obs);
+int ufr_view_pair_scores(const int64_t* offsets, const int32_t* obs, const int32_t* obs_host, int64_t n_obs, const double* points,
+                         int64_t M, const double* centres, int32_t N, double theta0, double sigma1, double sigma2, double* score,
+                         void* workspace, size_t workspace_bytes, ufr_stream stream);
+
 /* ---- the optimizer update and the ray draw of a training step (ABI 507, additive) ----------------------------
  * What UFORecon.training_step / configure_optimizers (code1/model.py:72-87, 537) run around the ray path, each as one call.
  * Neither synchronises; every argument error is UFR_ERR_ARG with the reason in the thread's last-error text.

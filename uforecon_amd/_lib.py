@@ -172,6 +172,10 @@ SIGNATURES = {
     "ufr_raster_downsample": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
     "ufr_image_resize_u8": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),
     "ufr_pixel_rays": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, vp, vp]),
+    "ufr_image_resize_mask_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),
+    "ufr_view_pair_scores_workspace_bytes": (sz, [i32, i64]),
+    "ufr_view_pair_scores": (C.c_int, [C.POINTER(i64), vp, C.POINTER(i32), i64, vp, i64, vp, i32, C.c_double, C.c_double, C.c_double,
+                                       vp, vp, sz, vp]),
     "ufr_adam_table_capacity": (i32, []),
     "ufr_adam_step": (C.c_int, [C.POINTER(AdamTensor), i32, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "ufr_select_rays_workspace_bytes": (sz, [i32, i32]),

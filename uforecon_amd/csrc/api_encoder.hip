@@ -1,6 +1,7 @@
 // extern "C" surface of libufr.so (include/ufr.h), part 5 of 7: the encoder -- correlation volumes and view weights, the
 // 3-D convolutions of the frustum U-Nets, the 2-D and deformable convolutions of the feature backbone, the FMT layer, and
-// what a scan loader feeds them (image planes from 8-bit pictures, the per-pixel ray tables).
+// what a scan loader feeds them (image planes from 8-bit pictures, with or without a foreground mask; the per-pixel ray tables)
+// and what a COLMAP model's converter asks before any of it (the pair scores of the view selection).
 #include "api_common.h"
 
 using namespace ufr;
@@ -255,11 +256,14 @@ int ufr_fmt_layer(const ufr_fmt_layer_weights* w, const float* x, const float* s
   return UFR_OK;
 }
 
+}  // extern "C"
+
 // ------------------------------------------------------------------ the encoder's inputs: image planes and ray tables
-int ufr_image_resize_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* clip4, float* dst,
-                        ufr_stream stream) {
-  const char* who = "ufr_image_resize_u8";
-  UFR_REQUIRE(src && dst, "%s: null argument", who);
+namespace {
+// ufr_image_resize_u8 (mask null, masked false) and ufr_image_resize_mask_u8: one contract, one launcher
+int image_resize(const char* who, const char* timer, const uint8_t* src, const uint8_t* mask, bool masked, int32_t n, int32_t Hs,
+                 int32_t Ws, int32_t H, int32_t W, const int32_t* clip4, float* dst, ufr_stream stream) {
+  UFR_REQUIRE(src && dst && (mask || !masked), "%s: null argument", who);
   UFR_REQUIRE(n >= 1 && Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1, "%s: n %d, source %dx%d, resized %dx%d (each must be >= 1)", who, n, Hs,
               Ws, H, W);
   UFR_REQUIRE((long long)Hs * Ws < (1ll << 31) && (long long)H * W < (1ll << 31), "%s: an image of %dx%d or %dx%d has 2^31 pixels or more",
@@ -273,7 +277,69 @@ int ufr_image_resize_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, i
   UFR_REQUIRE((long long)n * Ho * Wo * 3 < (1ll << 38) && (long long)n * Hs * Ws * 3 < (1ll << 40),
               "%s: %d images of %dx%d from %dx%d are too many bytes", who, n, H, W, Hs, Ws);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  UFR_TIMED("image_resize_u8", s, launch_image_resize_u8(src, n, Hs, Ws, H, W, clip[0], clip[1], (int)Ho, (int)Wo, dst, s));
+  UFR_TIMED(timer, s, launch_image_resize_u8(src, mask, n, Hs, Ws, H, W, clip[0], clip[1], (int)Ho, (int)Wo, dst, s));
+  return UFR_OK;
+}
+
+// view selection: [the CSR offsets, on the device, int64 x (N + 1) | every image's observation list sorted, int32 x n_obs]
+struct ViewSelectWs { long long* offsets; int* sorted; };
+ViewSelectWs carve_view_select(Carver& c, int N, long long n_obs) {
+  ViewSelectWs w;
+  w.offsets = c.take<long long>((size_t)N + 1);
+  w.sorted = c.take<int>((size_t)n_obs);
+  return w;
+}
+constexpr int kViewSelectMaxImages = 32768;   // N (N - 1) / 2 workgroups in one grid
+bool view_select_sizes_ok(int N, long long n_obs) { return N >= 1 && N <= kViewSelectMaxImages && n_obs >= 0 && n_obs < (1ll << 31); }
+}  // namespace
+
+extern "C" {
+
+int ufr_image_resize_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, int32_t H, int32_t W, const int32_t* clip4, float* dst,
+                        ufr_stream stream) {
+  return image_resize("ufr_image_resize_u8", "image_resize_u8", src, nullptr, false, n, Hs, Ws, H, W, clip4, dst, stream);
+}
+
+int ufr_image_resize_mask_u8(const uint8_t* src, const uint8_t* mask, int32_t n, int32_t Hs, int32_t Ws, int32_t H, int32_t W,
+                             const int32_t* clip4, float* dst, ufr_stream stream) {
+  return image_resize("ufr_image_resize_mask_u8", "image_resize_mask_u8", src, mask, true, n, Hs, Ws, H, W, clip4, dst, stream);
+}
+
+// ------------------------------------------------------------------ view selection of a COLMAP model
+size_t ufr_view_pair_scores_workspace_bytes(int32_t N, int64_t n_obs) {
+  if (!view_select_sizes_ok(N, n_obs)) {
+    fail(UFR_ERR_ARG, "ufr_view_pair_scores_workspace_bytes: N %d, n_obs %lld (1 <= N <= %d, 0 <= n_obs < 2^31)", N, (long long)n_obs,
+         kViewSelectMaxImages);
+    return 0;
+  }
+  return carved_bytes(carve_view_select, (int)N, (long long)n_obs);
+}
+
+int ufr_view_pair_scores(const int64_t* offsets, const int32_t* obs, const int32_t* obs_host, int64_t n_obs, const double* points,
+                         int64_t M, const double* centres, int32_t N, double theta0, double sigma1, double sigma2, double* score,
+                         void* workspace, size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_view_pair_scores";
+  UFR_REQUIRE(offsets && centres && score && workspace && (obs || n_obs == 0) && (points || M == 0), "%s: null argument", who);
+  UFR_REQUIRE(view_select_sizes_ok(N, n_obs), "%s: N %d, n_obs %lld (1 <= N <= %d, 0 <= n_obs < 2^31)", who, N, (long long)n_obs,
+              kViewSelectMaxImages);
+  UFR_REQUIRE(M >= 0 && M < (1ll << 31), "%s: M %lld (0 <= M < 2^31)", who, (long long)M);
+  UFR_REQUIRE(offsets[0] == 0 && offsets[N] == n_obs, "%s: offsets run from %lld to %lld, the lists hold %lld indices", who,
+              (long long)offsets[0], (long long)offsets[N], (long long)n_obs);
+  for (int i = 0; i < N; ++i)
+    UFR_REQUIRE(offsets[i] <= offsets[i + 1], "%s: offsets are not monotone at image %d (%lld > %lld)", who, i, (long long)offsets[i],
+                (long long)offsets[i + 1]);
+  if (obs_host)
+    for (long long o = 0; o < n_obs; ++o)
+      UFR_REQUIRE(obs_host[o] >= -1 && obs_host[o] < M, "%s: observation %lld holds index %d, outside [-1, %lld)", who, o, obs_host[o],
+                  (long long)M);
+  UFR_REQUIRE(sigma1 > 0.0 && sigma2 > 0.0 && std::isfinite(sigma1) && std::isfinite(sigma2) && std::isfinite(theta0),
+              "%s: theta0 %g, sigma1 %g, sigma2 %g (sigma > 0, all finite)", who, theta0, sigma1, sigma2);
+  Carver c(workspace);
+  const ViewSelectWs w = carve_view_select(c, N, n_obs);
+  UFR_REQUIRE(workspace_bytes >= c.off, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, c.off);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("view_pair_scores", s, launch_view_pair_scores(reinterpret_cast<const long long*>(offsets), obs, points, M, centres, N, theta0,
+                                                           sigma1, sigma2, score, w.offsets, w.sorted, s));
   return UFR_OK;
 }
 

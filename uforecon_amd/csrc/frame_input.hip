@@ -14,6 +14,9 @@
 //          When Ws == 2 W and Hs == 2 H exactly, OpenCV takes its area path instead: (s00 + s01 + s10 + s11 + 2) >> 2.
 //          Reads of a pixel's three bytes are as scattered as the source image makes them (stride 3 * scale bytes along a
 //          row); the three plane writes are coalesced along W.
+//   image_resize_mask  the same kernel with a second source, a single-channel 8-bit mask of the source size (the reference's
+//          GeneralFit.load_scene, code1/dataset/general_fit.py:174-180): the mask goes through the same resize rule, and the
+//          output is (float)(((double)v / 255.0) * ((double)m / 254.0)) -- 254 is the reference's divisor.
 //   pixel_rays    one thread per pixel, in double: p = (x * 2 / (W - 1) - 1, y * 2 / (H - 1) - 1, 1, 1), v = (M p)[:3] - origin
 //          with M the float32 matrix widened to double and the four products of a row summed left to right, then v / |v|,
 //          |v| = sqrt((v0^2 + v1^2) + v2^2), stored as float.  numpy's matmul and torch.norm may sum in another order: the host
@@ -73,7 +76,10 @@ struct ResizeArgs {
   int x0, y0, Ho, Wo;     // crop: first column / row of the resized image that is kept, and the kept size
 };
 
-__global__ void __launch_bounds__(kFiThreads) image_resize_kernel(const unsigned char* __restrict__ src, long long total, ResizeArgs a,
+// kMask: a second, single-channel source (n,Hs,Ws) goes through the same resize, and the output is colour x mask (image_resize_mask)
+template <bool kMask>
+__global__ void __launch_bounds__(kFiThreads) image_resize_kernel(const unsigned char* __restrict__ src,
+                                                                   const unsigned char* __restrict__ mask, long long total, ResizeArgs a,
                                                                    float* __restrict__ dst) {
   const long long i = (long long)blockIdx.x * kFiThreads + threadIdx.x;
   if (i >= total) return;
@@ -83,12 +89,18 @@ __global__ void __launch_bounds__(kFiThreads) image_resize_kernel(const unsigned
   const int yo = (int)(p / a.Wo), xo = (int)(p - (long long)yo * a.Wo);
   const int dx = xo + a.x0, dy = yo + a.y0;
   const unsigned char* img = src + n * ((long long)a.Hs * a.Ws * 3);
-  int out[3];
+  const unsigned char* msk = kMask ? mask + n * ((long long)a.Hs * a.Ws) : nullptr;
+  int out[3], m = 0;
   if (a.Ws == 2 * a.W && a.Hs == 2 * a.H) {
     const unsigned char* r0 = img + ((long long)(2 * dy) * a.Ws + 2 * dx) * 3;
     const unsigned char* r1 = r0 + (long long)a.Ws * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = ((int)r0[c] + (int)r0[3 + c] + (int)r1[c] + (int)r1[3 + c] + 2) >> 2;
+    if (kMask) {
+      const unsigned char* m0 = msk + (long long)(2 * dy) * a.Ws + 2 * dx;
+      const unsigned char* m1 = m0 + a.Ws;
+      m = ((int)m0[0] + (int)m0[1] + (int)m1[0] + (int)m1[1] + 2) >> 2;
+    }
   } else {
     const Tap tx = tap_x(dx, (double)a.Ws / (double)a.W, a.Ws);
     const Tap ty = tap_y(dy, (double)a.Hs / (double)a.H, a.Hs);
@@ -100,9 +112,22 @@ __global__ void __launch_bounds__(kFiThreads) image_resize_kernel(const unsigned
       const int h1 = (int)r1[3 * (long long)tx.s0 + c] * tx.w0 + (int)r1[3 * (long long)tx.s1 + c] * tx.w1;
       out[c] = (((ty.w0 * (h0 >> 4)) >> 16) + ((ty.w1 * (h1 >> 4)) >> 16) + 2) >> 2;
     }
+    if (kMask) {
+      const unsigned char* m0 = msk + (long long)ty.s0 * a.Ws;
+      const unsigned char* m1 = msk + (long long)ty.s1 * a.Ws;
+      const int h0 = (int)m0[tx.s0] * tx.w0 + (int)m0[tx.s1] * tx.w1;
+      const int h1 = (int)m1[tx.s0] * tx.w0 + (int)m1[tx.s1] * tx.w1;
+      m = (((ty.w0 * (h0 >> 4)) >> 16) + ((ty.w1 * (h1 >> 4)) >> 16) + 2) >> 2;
+    }
   }
+  if (kMask) {
+    const double w = (double)m / 254.0;     // the reference's own divisor (general_fit.py:178), kept
 #pragma unroll
-  for (int c = 0; c < 3; ++c) dst[(n * 3 + c) * plane + p] = (float)((double)out[c] / 255.0);
+    for (int c = 0; c < 3; ++c) dst[(n * 3 + c) * plane + p] = (float)(((double)out[c] / 255.0) * w);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[(n * 3 + c) * plane + p] = (float)((double)out[c] / 255.0);
+  }
 }
 
 struct RayArgs {
@@ -141,11 +166,14 @@ inline unsigned blocks_of(long long n) { return (unsigned)((n + kFiThreads - 1) 
 
 }  // namespace
 
-hipError_t launch_image_resize_u8(const unsigned char* src, long long n, int Hs, int Ws, int H, int W, int x0, int y0, int Ho, int Wo,
-                                  float* dst, hipStream_t s) {
+hipError_t launch_image_resize_u8(const unsigned char* src, const unsigned char* mask, long long n, int Hs, int Ws, int H, int W, int x0,
+                                  int y0, int Ho, int Wo, float* dst, hipStream_t s) {
   const ResizeArgs a{Hs, Ws, H, W, x0, y0, Ho, Wo};
   const long long total = n * Ho * Wo;
-  hipLaunchKernelGGL(image_resize_kernel, dim3(blocks_of(total)), dim3(kFiThreads), 0, s, src, total, a, dst);
+  if (mask)
+    hipLaunchKernelGGL(image_resize_kernel<true>, dim3(blocks_of(total)), dim3(kFiThreads), 0, s, src, mask, total, a, dst);
+  else
+    hipLaunchKernelGGL(image_resize_kernel<false>, dim3(blocks_of(total)), dim3(kFiThreads), 0, s, src, mask, total, a, dst);
   return hipGetLastError();
 }
 

@@ -194,8 +194,13 @@ hipError_t launch_raster_shade(const double* verts, const int* faces, long long 
                                int H, int W, unsigned char* image, float* depth, int* face_out, float* normal_out, hipStream_t s);
 hipError_t launch_raster_downsample(const unsigned char* src, long long n, int H, int W, int sf, unsigned char* dst, hipStream_t s);
 // frame_input.hip: a scan loader's per-pixel work -- 8-bit images to resized, cropped float planes; ray tables (see the file header)
-hipError_t launch_image_resize_u8(const unsigned char* src, long long n, int Hs, int Ws, int H, int W, int x0, int y0, int Ho, int Wo,
-                                  float* dst, hipStream_t s);
+// (mask: null, or a second source (n,Hs,Ws) resized by the same rule and multiplied in as m / 254)
+hipError_t launch_image_resize_u8(const unsigned char* src, const unsigned char* mask, long long n, int Hs, int Ws, int H, int W, int x0,
+                                  int y0, int Ho, int Wo, float* dst, hipStream_t s);
+// view_select.hip: the pair scores of a COLMAP model's view selection (see the file header)
+hipError_t launch_view_pair_scores(const long long* offsets_host, const int* obs, const double* points, long long M,
+                                   const double* centres, int N, double theta0, double sigma1, double sigma2, double* score,
+                                   long long* offsets_dev, int* sorted, hipStream_t s);
 hipError_t launch_pixel_rays(const float* m_inv, const float* origin, int H, int W, float* dir, hipStream_t s);
 hipError_t launch_depth_gt(const float* pfm, int Hs, int Ws, int bottom_up, int y0, int x0, int H, int W, float scale_factor,
                            const double* cam_ray_z, float* depth, hipStream_t s);

@@ -115,6 +115,21 @@ def image_planes_host(images, H: int, W: int, clip=(0, 0, 0, 0)):
     return np.ascontiguousarray(np.transpose(small, (0, 3, 1, 2))).astype(np.float32)
 
 
+def image_mask_planes_host(images, masks, H: int, W: int, clip=(0, 0, 0, 0)):
+    """ufr_image_resize_mask_u8 on the host, in the reference's calls (general_fit.py:174-180): colour (n,Hs,Ws,3) and mask
+    (n,Hs,Ws) uint8 each through `resize_u8`, value = float32((v / 255) * (m / 254)) with the product taken in float64."""
+    images, masks = np.asarray(images), np.asarray(masks)
+    H, W = int(H), int(W)
+    left, top, right, bottom = (int(c) for c in clip)
+    if images.ndim != 4 or images.shape[3] != 3 or masks.shape != images.shape[:3] or masks.dtype != np.uint8 \
+            or min(left, top, right, bottom) < 0 or H - top - bottom < 1 or W - left - right < 1:
+        raise ValueError(f"image_mask_planes_host: images {images.shape}, masks {masks.dtype} {masks.shape}, {H}x{W}, clip {tuple(clip)}")
+    small = resize_u8(images, (W, H)) / 255.
+    small = small * (resize_u8(masks[..., None], (W, H)) / 254.)
+    small = small[:, top:H - bottom, left:W - right]
+    return np.ascontiguousarray(np.transpose(small, (0, 3, 1, 2))).astype(np.float32)
+
+
 def homo_pixels(H: int, W: int):
     """dtu_test_sparse.py:171-176: the (4, H*W) float64 table of normalised pixel coordinates (x, y, 1, 1)."""
     h_line = (np.linspace(0, H - 1, H)) * 2 / (H - 1) - 1

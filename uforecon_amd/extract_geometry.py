@@ -8,7 +8,12 @@ For every scan and every render view: `dtu_scan.DtuScan` makes the batch, `pipel
 renders it and writes `<out_dir>/depth/<scan>/<%08d>.npy`, `<out_dir>/rgb/<scan>/<%08d>.jpg` and
 `<out_dir>/<scan>/depth/<%08d>.png` (model.save_depth_outputs), the tree `python -m uforecon_amd.depth_fusion` and
 `python -m uforecon_amd.tsdf` take as `--root_dir`.  The sampler's uniforms of a view come from a generator seeded by
-(`--seed`, scan, view): a rerun writes the same files.  A flag value the mirror does not implement (`--volume_type
+(`--seed`, scan, view): a rerun writes the same files.
+
+With `--test_general` (main.py:164-176) the scenes are `--test_scan` under `--test_dir`, read by `general_scan.GeneralScan`
+(`--dataset blendedmvs | mvimage`, `--use_mask`); `--scans`, `--set` and `--original_img_wh` are not read, the image size is
+the dataset's unless `--img_wh` is given, and the files are named `refview<i>` after each batch's reference view -- the tree
+`python -m uforecon_amd.tsdf --dataset general --test_scan ...` reads.  A flag value the mirror does not implement (`--volume_type
 featuregrid`, a missing `--explicit_similarity`, another cascade layout ...) ends the command with one line, exit code 2.
 """
 from __future__ import annotations
@@ -16,6 +21,7 @@ from __future__ import annotations
 import argparse
 import os
 import sys
+import zlib
 
 import torch
 
@@ -27,6 +33,7 @@ from .dtu_eval import DTU_SCANS
 IMPLEMENTED = {"volume_type": "correlation", "explicit_similarity": True, "depth_pos_encoding": True, "use_dir_srdf": False,
                "ndepths": "48,32,8", "depth_inter_r": "4,2,1", "cr_base_chs": "8,8,8"}
 PRECISIONS = {"default": None, "fp32": 0, "16bit": 1}      # ops.PRECISION_FP32 / PRECISION_16BIT
+IMG_MULTIPLE = 32     # the first cascade stage's volume is (H/4, W/4), and the 3-D U-Nets halve every extent three times (unet3d.py)
 
 
 def make_parser():
@@ -53,6 +60,11 @@ def make_parser():
     parser.add_argument("--depth_pos_encoding", action="store_true", help="use depth pos encoding")
     parser.add_argument("--explicit_similarity", action="store_true", help="use explicit similarity")
     parser.add_argument("--set", dest="set", type=int, default=0, help="two sets are provided by SparseNeuS")
+    parser.add_argument("--test_general", dest="test_general", action="store_true", help="test on custom dataset")
+    parser.add_argument("--test_scan", dest="test_scan", type=str, nargs="+",
+                        default=["5aa235f64a17b335eeaf9609", "5ba19a8a360c7c30c1c169df", "5adc6bd52430a05ecb2ffb85", "5bf7d63575c26f32dbf7413b"])
+    parser.add_argument("--dataset", dest="dataset", type=str, default="blendedmvs", help="dataset name")
+    parser.add_argument("--use_mask", dest="use_mask", action="store_true", help="use mask")
     # ---- this project's own
     parser.add_argument("--scans", type=int, nargs="+", default=DTU_SCANS, help="scan numbers (default: the reference's 15 test scans)")
     parser.add_argument("--img_wh", type=int, nargs=2, default=[800, 640], help="width and height the images are resized to")
@@ -69,10 +81,47 @@ def unimplemented(args):
             return f"--{flag} {getattr(args, flag)!r} is not implemented here (only {want!r}: what the reference's scripts pass)"
     if args.mvs_depth_guide <= 0:
         return "--mvs_depth_guide 0 is not implemented here (the ray path reads the MVS depth: pass --mvs_depth_guide 1)"
+    if getattr(args, "test_general", False):
+        # the custom-scene rule: a batch is the reference view plus the first test_n_view - 1 of --test_ref_view (a scene's
+        # pair file is checked when the scene is opened)
+        most = min(len(args.test_ref_view) + 1, MAX_VIEWS)
+        if not 2 <= args.test_n_view <= most:
+            return (f"--test_n_view {args.test_n_view} is not implemented here (2 .. {most}: the reference view and up to "
+                    f"{len(args.test_ref_view)} of --test_ref_view)")
+        from .general_scan import DATASET_WH
+
+        if args.dataset not in DATASET_WH:
+            return f"--dataset {args.dataset!r} is not implemented here (one of {sorted(DATASET_WH)})"
+        return None
     views = args.test_ref_view if args.set == 0 else SET1_VIEWS
     if not 2 <= args.test_n_view <= min(len(views), MAX_VIEWS):
         return f"--test_n_view {args.test_n_view} is not implemented here (2 .. {min(len(views), MAX_VIEWS)} of the {len(views)} listed views)"
     return None
+
+
+def parse_args(argv=None, parser=None):
+    """`make_parser()`'s arguments with the two image sizes left open (None) unless given: `resolve_img_wh` fills them in."""
+    parser = parser or make_parser()
+    parser.set_defaults(img_wh=None, original_img_wh=None)
+    return parser.parse_args(argv)
+
+
+def resolve_img_wh(args):
+    """(img_wh, original_img_wh) of a command line: what was given, else 800x640 of 1600x1200 for DTU and the dataset's own
+    size for --test_general (which reads each picture's size from its file and ignores --original_img_wh)."""
+    if args.test_general:
+        from .general_scan import DATASET_WH
+
+        default = list(DATASET_WH[args.dataset])
+    else:
+        default = [800, 640]
+    return (list(args.img_wh) if args.img_wh is not None else default,
+            list(args.original_img_wh) if args.original_img_wh is not None else [1600, 1200])
+
+
+def scan_seed(scan_id: str) -> int:
+    """what stands in `view_uniforms` for the scan number of a custom scene"""
+    return zlib.crc32(str(scan_id).encode("utf-8"))
 
 
 def view_uniforms(seed: int, scan: int, view: int, point_num: int, point_num_2: int, rays: int, coarse_only: bool = False):
@@ -91,19 +140,9 @@ def load_checkpoint(net, path):
     net.load_state_dict(ckpt["state_dict"] if "state_dict" in ckpt else ckpt, strict=True)
 
 
-def main(argv=None):
-    from .dtu_scan import DtuScan
+def load_net(args, dev):
     from .pipeline import UFOReconInference
 
-    parser = make_parser()
-    args = parser.parse_args(argv)
-    why = unimplemented(args)
-    if why is None and not (args.test_dir and args.out_dir):
-        why = "--test_dir and --out_dir are required"
-    if why is not None:
-        parser.error(why)
-    args.extract_geometry = True
-    dev = torch.device("cuda:0")
     net = UFOReconInference(args)
     if args.load_ckpt:
         load_checkpoint(net, args.load_ckpt)
@@ -112,6 +151,58 @@ def main(argv=None):
         print("no --load_ckpt: the model keeps its initial weights", file=sys.stderr)
     net = net.to(dev)
     net.precision = PRECISIONS[args.precision]
+    return net
+
+
+def main_general(parser, args):
+    """The --test_general branch (main.py:164-176): one `GeneralScan` per --test_scan; --scans, --set and --original_img_wh are
+    not read.  Every batch is named by its reference view: the files are `refview<i>.npy / .jpg / .png`, which is what
+    `python -m uforecon_amd.tsdf --dataset general --test_scan ...` looks for."""
+    from .general_scan import GeneralScan
+
+    if args.img_wh[0] % IMG_MULTIPLE or args.img_wh[1] % IMG_MULTIPLE:
+        parser.error(f"--img_wh {args.img_wh[0]} {args.img_wh[1]}: width and height must be multiples of {IMG_MULTIPLE} "
+                     "(the first cascade stage works at a quarter of the size, and its U-Net halves that three times)")
+    scenes = []
+    for scan in args.test_scan:        # every scene is opened before the model is built: a missing file costs nothing
+        try:
+            scenes.append(GeneralScan(args.test_dir, scan, n_views=args.test_n_view, test_ref_view=args.test_ref_view, dataset=args.dataset,
+                                      use_mask=args.use_mask, img_wh=args.img_wh, device="cuda:0"))
+        except FileNotFoundError as e:
+            parser.error(f"{scan}: {e.filename} is missing under --test_dir {args.test_dir}")
+        except ValueError as e:
+            parser.error(f"{scan}: --test_n_view {args.test_n_view}: {e}")
+    net = load_net(args, torch.device("cuda:0"))
+    for frames in scenes:
+        for i in range(len(frames)):
+            try:
+                batch = frames[i]
+            except FileNotFoundError as e:
+                parser.error(f"{frames.scan_id}: {e.filename} is missing under --test_dir {args.test_dir}")
+            ref_view = frames.metas[i][0]
+            H, W = batch["source_imgs"].shape[-2:]
+            U = view_uniforms(args.seed, scan_seed(frames.scan_id), ref_view, net.point_num, net.point_num_2, H * W, args.test_coarse_only)
+            net.extract_geometry(batch, out_dir=args.out_dir, uniforms=U)
+            print("%s reference view %d -> %s" % (frames.scan_id, ref_view, os.path.join(args.out_dir, "depth", frames.scan_id, "refview%d.npy" % ref_view)))
+    return 0
+
+
+def main(argv=None):
+    from .dtu_scan import DtuScan
+
+    parser = make_parser()
+    args = parse_args(argv, parser)
+    why = unimplemented(args)
+    if why is None and not (args.test_dir and args.out_dir):
+        why = "--test_dir and --out_dir are required"
+    if why is not None:
+        parser.error(why)
+    args.img_wh, args.original_img_wh = resolve_img_wh(args)
+    args.extract_geometry = True
+    if args.test_general:
+        return main_general(parser, args)
+    dev = torch.device("cuda:0")
+    net = load_net(args, dev)
     for scan in args.scans:
         try:
             frames = DtuScan(args.test_dir, "scan%d" % scan, n_views=args.test_n_view, img_wh=args.img_wh,

@@ -1287,6 +1287,62 @@ def image_resize_u8(images: torch.Tensor, H: int, W: int, clip=(0, 0, 0, 0)) -> 
     return out
 
 
+def image_resize_mask_u8(images: torch.Tensor, masks: torch.Tensor, H: int, W: int, clip=(0, 0, 0, 0)) -> torch.Tensor:
+    """ufr_image_resize_mask_u8: `image_resize_u8` with a foreground mask ``masks`` (n,Hs,Ws) CUDA uint8 that goes through the
+    same resize; each output is float32((v / 255) * (m / 254)) in float64 (the reference's divisor).  Does not synchronise."""
+    p = _dev(images, "images", torch.uint8)
+    q = _dev(masks, "masks", torch.uint8)
+    if images.dim() != 4 or images.shape[3] != 3 or tuple(masks.shape) != tuple(images.shape[:3]):
+        raise UfrError(f"images / masks: expected shapes (n, Hs, Ws, 3) and (n, Hs, Ws), got {tuple(images.shape)} and {tuple(masks.shape)}")
+    clip = [int(c) for c in clip]
+    if len(clip) != 4:
+        raise UfrError(f"image_resize_mask_u8: clip {clip!r} (left, top, right, bottom)")
+    n, Hs, Ws = (int(s) for s in images.shape[:3])
+    H, W = int(H), int(W)
+    Ho, Wo = H - clip[1] - clip[3], W - clip[0] - clip[2]
+    out = torch.empty((n, 3, max(Ho, 0), max(Wo, 0)), dtype=torch.float32, device=images.device)
+    _lib.check(_lib.load().ufr_image_resize_mask_u8(p, q, n, Hs, Ws, H, W, (C.c_int32 * 4)(*clip), out.data_ptr(), _stream()),
+               "ufr_image_resize_mask_u8")
+    return out
+
+
+def view_pair_scores(offsets, obs, points, centres, theta0: float = 5.0, sigma1: float = 1.0, sigma2: float = 10.0,
+                     device="cuda") -> torch.Tensor:
+    """ufr_view_pair_scores: the (N,N) float64 score matrix, on ``device``, of a COLMAP model's view selection.  ``offsets``
+    (N+1) and ``obs`` (n_obs; -1 = no point) are the images' observation lists in CSR form, host arrays (``obs`` is uploaded
+    here and also checked on the host); ``points`` (M,3) and ``centres`` (N,3) float64, host arrays or tensors on ``device``.
+    Does not synchronise beyond torch's own uploads; uforecon_amd.colmap2mvsnet has the host form."""
+    import numpy as np
+
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise UfrError(f"view_pair_scores: device {device} (must be a GPU; uforecon_amd.colmap2mvsnet has the host form)")
+    off = np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(-1))
+    ob = np.asarray(obs).reshape(-1)
+    if ob.size and (ob.min() < -2 ** 31 or ob.max() >= 2 ** 31):
+        raise UfrError("view_pair_scores: an observation index does not fit 32 bits")
+    ob = np.ascontiguousarray(ob.astype(np.int32))
+    N = off.size - 1
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        f64 = lambda t, name: (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, np.float64)))).to(device)  # noqa: E731
+        pts, cen = f64(points, "points").reshape(-1, 3), f64(centres, "centres")
+        if cen.dim() != 2 or tuple(cen.shape) != (max(N, 0), 3):
+            raise UfrError(f"view_pair_scores: centres {tuple(cen.shape)} for {N} images")
+        nbytes = lib.ufr_view_pair_scores_workspace_bytes(N, ob.size)
+        if nbytes == 0:
+            raise UfrError("ufr_view_pair_scores failed (-1): " + lib.ufr_last_error().decode())
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        ob_dev = torch.from_numpy(ob).to(device)
+        out = torch.empty((N, N), dtype=torch.float64, device=device)
+        _lib.check(lib.ufr_view_pair_scores(off.ctypes.data_as(C.POINTER(C.c_int64)), _dev(ob_dev, "obs", torch.int32) if ob.size else None,
+                                            ob.ctypes.data_as(C.POINTER(C.c_int32)), ob.size,
+                                            _dev(pts, "points", torch.float64) if pts.numel() else None, int(pts.shape[0]),
+                                            _dev(cen, "centres", torch.float64), N, float(theta0), float(sigma1), float(sigma2),
+                                            out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "ufr_view_pair_scores")
+    return out
+
+
 def pixel_rays(m_inv, H: int, W: int, origin=None, device="cuda") -> torch.Tensor:
     """ufr_pixel_rays: (3,H*W) float32 unit vectors on ``device``; ``m_inv`` 4x4 and ``origin`` (3 values or None): host
     arrays, narrowed to float32.  Per pixel, in float64: p = (2x/(W-1) - 1, 2y/(H-1) - 1, 1, 1), v = (m_inv p)[:3] - origin,
