@@ -13,7 +13,7 @@ the loader takes its depth range from the last file), and random 8-bit pictures.
   set1  n_views 2, set=1, 128x60 -> img_wh 64x30 (both factors exactly 2: the box mean), clip_wh (4, 2)
 
 How the reference is made to run: `cv2` is a stand-in module of exactly three functions, each a call into
-uforecon_amd.dtu_scan's host restatements (imread, resize, decomposeProjectionMatrix); `torchvision.transforms` holds empty
+uforecon_amd's host restatements (imread, resize, decomposeProjectionMatrix); `torchvision.transforms` holds empty
 names; and the module's `torch.from_numpy` passes tensors through, because dtu_test_sparse.py:389 hands it something that
 load_scene (:294) has already made a tensor -- as shipped, the class raises TypeError on every torch.  The class then runs
 through `DataLoader(batch_size=1, num_workers=0)`, and every tensor of every render view's batch is recorded.
@@ -87,12 +87,12 @@ def write_scan(root, cams, imgs):
 def import_reference_loader(ref_root):
     import torch
 
-    from uforecon_amd import dtu_scan as D
+    from uforecon_amd import cameras, host_forms as D
 
     cv2 = types.ModuleType("cv2")
     cv2.imread = lambda path: np.ascontiguousarray(D.imread_rgb(path)[:, :, ::-1])
     cv2.resize = lambda image, size: D.resize_u8(image, size)
-    cv2.decomposeProjectionMatrix = lambda P: D.decompose_projection_matrix(P)
+    cv2.decomposeProjectionMatrix = lambda P: cameras.decompose_projection_matrix(P)
     sys.modules["cv2"] = cv2
     tv = types.ModuleType("torchvision")
     tv.transforms = types.ModuleType("torchvision.transforms")

@@ -21,7 +21,7 @@ other three, which the reference leaves in float64, rounded to float32.  `len` a
 cases.
 
 How the reference is made to run: `cv2` is a stand-in of two functions (resize for INTER_NEAREST at fx = fy = 0.5: source
-pixel (2y, 2x); decomposeProjectionMatrix: uforecon_amd.dtu_scan's restatement), `torchvision` one of `T.Compose` /
+pixel (2y, 2x); decomposeProjectionMatrix: uforecon_amd.cameras' restatement), `torchvision` one of `T.Compose` /
 `T.ToTensor` (/ 255 in float32) and empty names, `termcolor.colored` the identity.  The class then runs through
 `DataLoader(batch_size=1, num_workers=0)`.
 """
@@ -153,7 +153,7 @@ def pixel_set():
 def import_reference_loader(ref_root):
     import torch
 
-    from uforecon_amd import dtu_scan as D
+    from uforecon_amd import cameras
 
     cv2 = types.ModuleType("cv2")
     cv2.INTER_NEAREST = 0
@@ -163,7 +163,7 @@ def import_reference_loader(ref_root):
         return np.ascontiguousarray(image[0::2, 0::2][:int(np.rint(image.shape[0] * 0.5)), :int(np.rint(image.shape[1] * 0.5))])
 
     cv2.resize = resize
-    cv2.decomposeProjectionMatrix = lambda P: D.decompose_projection_matrix(P)
+    cv2.decomposeProjectionMatrix = lambda P: cameras.decompose_projection_matrix(P)
     sys.modules["cv2"] = cv2
     tv = types.ModuleType("torchvision")
     tv.transforms = types.ModuleType("torchvision.transforms")

@@ -115,15 +115,15 @@ def write_scene(root, files):
 
 
 def import_reference_loader(ref_root):
-    from uforecon_amd import dtu_scan as D, general_scan as S
+    from uforecon_amd import cameras, host_forms as D
 
     def resize(image, size):
         return D.resize_u8(image, size) if image.ndim == 3 else D.resize_u8(image[..., None], size)[..., 0]
 
     cv2 = types.ModuleType("cv2")
-    cv2.imread = lambda path, flag=1: S.imread_gray(path) if flag == 0 else np.ascontiguousarray(D.imread_rgb(path)[:, :, ::-1])
+    cv2.imread = lambda path, flag=1: D.imread_gray(path) if flag == 0 else np.ascontiguousarray(D.imread_rgb(path)[:, :, ::-1])
     cv2.resize = resize
-    cv2.decomposeProjectionMatrix = lambda P: D.decompose_projection_matrix(P)
+    cv2.decomposeProjectionMatrix = lambda P: cameras.decompose_projection_matrix(P)
     sys.modules["cv2"] = cv2
     try:
         import einops  # noqa: F401

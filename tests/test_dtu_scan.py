@@ -1,4 +1,5 @@
-"""The DTU scan loader (uforecon_amd/dtu_scan.py) on the host and the extract_geometry command's parser.
+"""The DTU scan loader (uforecon_amd/dtu_scan.py) on the host, the restated resize and decomposition it rests on
+(uforecon_amd/host_forms.py, cameras.py) and the extract_geometry command's parser.
 
 The golden batches (tests/golden/dtu_scan_small.npz) went through the reference's own `DtuFitSparse`; what that pins and
 what it does not is in tests/golden/make_golden_dtu_scan.py.  On the machine that wrote the file every key comes out equal bit
@@ -14,7 +15,7 @@ import numpy as np
 import pytest
 
 import dtu_scan_golden as G
-from uforecon_amd import _lib, dtu_scan as D, extract_geometry as E
+from uforecon_amd import _lib, cameras, extract_geometry as E, host_forms as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -150,13 +151,13 @@ def test_decomposition_gives_back_the_camera():
                       [0, rng.uniform(500, 3000), rng.uniform(100, 700)], [0, 0, 1.0]])
         c = rng.uniform(-700, 700, 3)
         P = (K @ np.concatenate([R, (-R @ c)[:, None]], axis=1)).astype(np.float32)
-        K2, R2, c2 = D.decompose_projection_matrix(P)
+        K2, R2, c2 = cameras.decompose_projection_matrix(P)
         assert K2.dtype == R2.dtype == c2.dtype == np.float32 and c2.shape == (4, 1) and c2[3, 0] == 1
         assert (np.diag(K2) > 0).all() and np.allclose(np.tril(K2, -1), 0, atol=1e-3)
         assert np.allclose(K2, K, rtol=2e-6, atol=2e-3)
         assert np.allclose(R2, R, atol=2e-6)
         assert np.allclose(c2[:3, 0], c, rtol=1e-5, atol=2e-3)
-        intr, pose = D.load_K_Rt_from_P(P)
+        intr, pose = cameras.load_K_Rt_from_P(P)
         assert intr.dtype == np.float64 and pose.dtype == np.float32 and np.allclose(pose[:3, :3], R.T, atol=2e-6)
 
 

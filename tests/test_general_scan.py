@@ -14,7 +14,7 @@ import pytest
 import dtu_scan_golden as G
 import general_scan_golden as S
 from test_dtu_scan import SCHEMA
-from uforecon_amd import _lib, dtu_scan as D, extract_geometry as E, general_scan as GS
+from uforecon_amd import _lib, extract_geometry as E, general_scan as GS, host_forms as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -84,7 +84,7 @@ def test_dataset_sizes_names_and_the_mask_switch(scene_dir):
     blended = GS.GeneralScan(root, scan, dataset="blendedmvs", use_mask=True, **kw)[0]["source_imgs"]
     assert np.array_equal(plain.numpy(), blended.numpy()) and not np.array_equal(plain.numpy(), masked.numpy())
     raw = np.stack([D.imread_rgb(os.path.join(root, scan, "images", "%08d.jpg" % v)) for v in (1, 1)])
-    msk = np.stack([GS.imread_gray(os.path.join(root, scan, "masks", "%08d_mask.jpg" % v)) for v in (1, 1)])
+    msk = np.stack([D.imread_gray(os.path.join(root, scan, "masks", "%08d_mask.jpg" % v)) for v in (1, 1)])
     assert msk.dtype == np.uint8 and msk.shape == raw.shape[:3]
     assert np.array_equal(masked[0].numpy(), D.image_mask_planes_host(raw, msk, 32, 64))
 
@@ -113,10 +113,10 @@ def test_grey_level_of_a_mask_file(tmp_path):
     rng = np.random.default_rng(6)
     grey = rng.integers(0, 256, (6, 9), dtype=np.uint8)
     Image.fromarray(grey).save(tmp_path / "grey.png")
-    assert np.array_equal(GS.imread_gray(tmp_path / "grey.png"), grey)                        # one channel: read as it is
+    assert np.array_equal(D.imread_gray(tmp_path / "grey.png"), grey)                        # one channel: read as it is
     rgb = rng.integers(0, 256, (6, 9, 3), dtype=np.uint8)
     Image.fromarray(rgb).save(tmp_path / "rgb.png")
-    got = GS.imread_gray(tmp_path / "rgb.png").astype(np.float64)
+    got = D.imread_gray(tmp_path / "rgb.png").astype(np.float64)
     r, g, b = (rgb[..., c].astype(np.float64) for c in range(3))
     luma = (299 * r + 587 * g + 114 * b) / 1000
     assert np.abs(got - luma).max() <= 1.0                                                    # the rule of the module text, in integers

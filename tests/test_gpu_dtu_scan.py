@@ -1,4 +1,4 @@
-"""The scan loader's two kernels (csrc/frame_input.hip) against their host forms (uforecon_amd/dtu_scan.py), the loader on the
+"""The scan loader's two kernels (csrc/frame_input.hip) against their host forms (uforecon_amd/host_forms.py), the loader on the
 device against the golden batches, and the extract_geometry command end to end on the golden scan."""
 import argparse
 import ctypes as C
@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import dtu_scan_golden as G
-from uforecon_amd import _lib, dtu_scan as D, ops
+from uforecon_amd import _lib, host_forms as D, ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

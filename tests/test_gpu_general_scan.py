@@ -12,7 +12,7 @@ import torch
 import dtu_scan_golden as G
 import general_scan_golden as S
 from test_gpu_dtu_scan import RAY_ATOL, _rays_close
-from uforecon_amd import _lib, dtu_scan as D, general_scan as GS, ops
+from uforecon_amd import _lib, general_scan as GS, host_forms as D, ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

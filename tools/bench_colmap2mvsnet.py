@@ -4,7 +4,7 @@
     form `colmap2mvsnet.pair_scores_host` (wall time; vectorised per pair with np.isin, so already far faster than the
     reference's per-pair list comprehension, which is not run here);
   * the masked resize (ufr_image_resize_mask_u8) for 3 pictures of 1920 x 1080 -> 960 x 544 against its host form
-    `dtu_scan.image_mask_planes_host`.
+    `host_forms.image_mask_planes_host`.
 There is no pass mark and no earlier figure to compare with: this file records what was measured and on what.  Prints one JSON
 line; --out writes it to a file (profiles/colmap2mvsnet_bench.json is one such run)."""
 import argparse
@@ -18,7 +18,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from uforecon_amd import colmap2mvsnet as M, dtu_scan as D, ops  # noqa: E402
+from uforecon_amd import colmap2mvsnet as M, host_forms as D, ops  # noqa: E402
 
 IMAGES, OBSERVATIONS, POINTS = 100, 2000, 20000
 SOURCE_HW, IMG_HW, VIEWS = (1080, 1920), (544, 960), 3

@@ -1,4 +1,4 @@
-"""Benchmark of the DTU scan loader (uforecon_amd/dtu_scan.py) at DTU's sizes: 3 views of 1600 x 1200 -> 800 x 640.
+"""Benchmark of the DTU scan loader (uforecon_amd/dtu_scan.py, host_forms.py) at DTU's sizes: 3 views of 1600 x 1200 -> 800 x 640.
   * PNG decode on the host (PIL), per image;
   * the resize kernel (3 images in one launch) and the two ray calls, with HIP events (ufr_profile_*);
   * the same two steps in their host forms (numpy / CPU torch);
@@ -18,7 +18,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from uforecon_amd import dtu_scan as D, ops  # noqa: E402
+from uforecon_amd import cameras, host_forms as D, ops  # noqa: E402
+from uforecon_amd.dtu_scan import DtuScan  # noqa: E402
 
 ORIGINAL_WH, IMG_WH, VIEWS, SCAN = (1600, 1200), (800, 640), [23, 24, 33], "scan1"
 
@@ -72,7 +73,7 @@ def main():
         res["png_decode_ms_per_image"] = best_ms(lambda: [D.imread_rgb(p) for p in paths], a.repeats) / len(paths)
         raw = np.stack([D.imread_rgb(p) for p in paths])
         raw_dev = torch.from_numpy(raw).to(dev)
-        scan = D.DtuScan(root, SCAN, img_wh=IMG_WH, original_img_wh=ORIGINAL_WH, test_view_pair=VIEWS, device=dev)   # warm: library, allocator
+        scan = DtuScan(root, SCAN, img_wh=IMG_WH, original_img_wh=ORIGINAL_WH, test_view_pair=VIEWS, device=dev)   # warm: library, allocator
         batch = scan[0]
         m_ref, origin = batch["ref_pose_inv"][0].cpu().numpy(), batch["ray_o"][0].cpu().numpy()
         m_cam = np.eye(4, dtype=np.float32)       # any matrix costs the same
@@ -89,12 +90,12 @@ def main():
         res["ray_kernel_ms_per_call"] = prof["pixel_rays"]["ms"] / (2 * a.repeats)
         res["upload_ms"] = best_ms(lambda: (torch.from_numpy(raw).to(dev), torch.cuda.synchronize()), a.repeats)
         res["host_resize_ms"] = best_ms(lambda: D.image_planes_host(raw, H, W), a.repeats)
-        hp = D.homo_pixels(H, W)
+        hp = cameras.homo_pixels(H, W)
         res["host_rays_ms_per_call"] = best_ms(lambda: (D.pixel_rays_host(m_ref, H, W, origin, hp), D.pixel_rays_host(m_cam, H, W, None, hp)),
                                                a.repeats) / 2
 
         def end_to_end(device):
-            s = D.DtuScan(root, SCAN, img_wh=IMG_WH, original_img_wh=ORIGINAL_WH, test_view_pair=VIEWS, device=device)
+            s = DtuScan(root, SCAN, img_wh=IMG_WH, original_img_wh=ORIGINAL_WH, test_view_pair=VIEWS, device=device)
             s[0]
             if device != "cpu":
                 torch.cuda.synchronize()

@@ -34,6 +34,7 @@ import sys
 
 import numpy as np
 
+from . import cameras
 from .dtu_eval import DTU_SCANS, read_ply
 
 TEST_REF_VIEW = [23, 24, 33, 22, 15, 34, 14, 32, 16, 35, 25]
@@ -50,10 +51,7 @@ def ellipse_half_widths(k: int):
 def read_cam_file(filename, scale_factor=None):
     """(K 3x3, E 4x4) float32 of a ``*_cam.txt`` (the reference's ``read_cam_file``, before it forms P = K4 @ E); E is
     multiplied by 1 / scale_factor when one is given."""
-    with open(filename) as f:
-        lines = [line.rstrip() for line in f.readlines()]
-    E = np.array(" ".join(lines[1:5]).split(), dtype=np.float32).reshape(4, 4)
-    K = np.array(" ".join(lines[7:10]).split(), dtype=np.float32).reshape(3, 3)
+    K, E, _ = cameras.read_cam_file(filename)
     if scale_factor is not None:
         if not scale_factor > 0:
             raise ValueError(f"scale_factor {scale_factor}: must be positive")

@@ -20,17 +20,12 @@ import os
 
 import numpy as np
 
+from . import cameras
+
 
 def read_pair_file(filename):
     """[(ref_view, [src_view ...])] of an MVSNet ``pair.txt``; views without sources are dropped (depth_fusion.py:14-24)."""
-    pairs = []
-    with open(filename) as f:
-        for _ in range(int(f.readline())):
-            ref = int(f.readline().rstrip())
-            srcs = [int(t) for t in f.readline().rstrip().split()[1::2]]
-            if srcs:
-                pairs.append((ref, srcs))
-    return pairs
+    return [(ref, srcs) for ref, srcs in cameras.read_pair_file(filename) if srcs]
 
 
 def pair_matrices(K_ref, E_ref, K_src, E_src) -> np.ndarray:

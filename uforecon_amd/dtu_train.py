@@ -8,10 +8,11 @@
 The tree: `Cameras/train/%08d_cam.txt` (all 49 are read), `Cameras/pair.txt`, `Rectified/<scan>_train/rect_%03d_<light>_r5000.png`
 (640x512, used as they are) and `Depths_raw/<scan>/depth_map_%04d.pfm` (1600x1200).
 
-Who computes what, as in `dtu_scan`: every 4x4 on the host, in the reference's calls, order and dtypes; everything
-per pixel on the device -- the pictures (`ops.image_resize_u8` at equal sizes: the identity on the bytes, then / 255), the ray
-table `ray_d` (`ops.pixel_rays`) and the ground-truth depths (`ops.depth_gt_prepare`).  With ``device="cpu"`` the host forms
-stand in (`dtu_scan.image_planes_host`, the float64 ray table of `_rays64`, `depth_gt_host`).
+Who computes what, as in `dtu_scan` (DESIGN 3.4.4): every 4x4 on the host, in the reference's calls, order and dtypes (`cameras`);
+everything per pixel on the device, through `host_forms.image_planes` / `pixel_rays` and `depth_gt` below -- the pictures
+(`ops.image_resize_u8` at equal sizes: the identity on the bytes, then / 255), the ray table `ray_d` (`ops.pixel_rays`) and
+the ground-truth depths (`ops.depth_gt_prepare`).  With ``device="cpu"`` their host forms stand in (`depth_gt_host` here).  `cam_ray_d` is always the host's float64 table
+(`host_forms.pixel_rays64`): the depths divide by its z row.
 
 Kept quirks of the reference (tests/golden/dtu_train_small.npz went through its own code): `depth_min` / `depth_interval`
 (x 1.06) are those of the LAST camera file read (view 48); with `test_ref_views` the source list of a 'val' / 'test' item is that
@@ -32,8 +33,9 @@ import re
 import numpy as np
 import torch
 
+from . import cameras
 from ._lib import MAX_VIEWS, UfrError
-from .dtu_scan import get_boundingbox, homo_pixels, image_planes_host, imread_rgb, load_K_Rt_from_P
+from .host_forms import image_planes, imread_rgb, pixel_rays, pixel_rays64
 
 NUM_ALL_IMGS = 49                       # dtu_train.py:96
 PFM_CROP = (44, 80)                     # dtu_train.py:253: rows 44..556, columns 80..720 of the half-size depth map
@@ -69,17 +71,24 @@ def depth_gt_host(pfm_rows, bottom_up, y0, x0, H, W, scale_factor, cam_ray_z):
     return (scaled.astype(np.float64).reshape(-1) / np.asarray(cam_ray_z, np.float64).reshape(-1)).astype(np.float32).reshape(H, W)
 
 
+def depth_gt(device, pfm_rows, bottom_up, y0, x0, H, W, scale_factor, cam_ray_z):
+    """The (H,W) float32 ground-truth ray depth on ``device`` from a PFM file's rows (a host array); ``cam_ray_z`` (H*W float64)
+    is a tensor on ``device``."""
+    device = torch.device(device)
+    if device.type == "cuda":
+        from . import ops
+
+        with torch.cuda.device(device):
+            return ops.depth_gt_prepare(torch.from_numpy(pfm_rows).to(device), bottom_up, y0, x0, H, W, scale_factor, cam_ray_z)
+    return torch.from_numpy(depth_gt_host(pfm_rows, bottom_up, y0, x0, H, W, scale_factor, cam_ray_z.numpy())).to(device)
+
+
 def read_cam_file(filename):
     """dtu_train.py:211-233: (intrinsics 4x4 float32, extrinsics 4x4 float32, [depth_min, depth_max], depth_min, interval * 1.06)."""
-    with open(filename) as f:
-        lines = [line.rstrip() for line in f.readlines()]
-    extrinsics = np.fromstring(" ".join(lines[1:5]), dtype=np.float32, sep=" ").reshape((4, 4))
-    intrinsics = np.fromstring(" ".join(lines[7:10]), dtype=np.float32, sep=" ").reshape((3, 3))
-    depth_min = float(lines[11].split()[0])
-    depth_max = depth_min + float(lines[11].split()[1]) * 192
-    intrinsics_ = np.float32(np.diag([1, 1, 1, 1]))
-    intrinsics_[:3, :3] = intrinsics
-    return intrinsics_, extrinsics, [depth_min, depth_max], depth_min, float(lines[11].split()[1]) * 1.06
+    K, E, depth = cameras.read_cam_file(filename)
+    intrinsics = np.float32(np.diag([1, 1, 1, 1]))
+    intrinsics[:3, :3] = K
+    return intrinsics, E, [depth[0], depth[0] + depth[1] * 192], depth[0], depth[1] * 1.06
 
 
 class DtuTrain:
@@ -117,20 +126,14 @@ class DtuTrain:
             self.all_intrinsics.append(K)
             self.all_extrinsics.append(E)
             self.all_near_fars.append(near_far)
-        self.homo_pixel = homo_pixels(self.img_H, self.img_W)
+        self.homo_pixel = cameras.homo_pixels(self.img_H, self.img_W)
         self._cam_rays = {}                       # bytes of the normalised intrinsics' inverse -> (cam_ray_d float32, z float64)
 
     # ---- dtu_train.py:160-208
     def build_metas(self):
-        metas, ref_src_pairs = [], {}
+        metas = []
         light_idxs = [3] if "train" not in self.split else range(7)
-        pairs = []
-        with open(self.pair_filepath) as f:
-            for _ in range(int(f.readline())):
-                ref_view = int(f.readline().rstrip())
-                src_views = [int(x) for x in f.readline().rstrip().split()[1::2]]
-                pairs.append((ref_view, src_views))
-                ref_src_pairs[ref_view] = src_views
+        pairs = cameras.read_pair_file(self.pair_filepath)
         for light_idx in light_idxs:
             for scan in self.scans:
                 for ref_view, src_views in pairs:
@@ -141,7 +144,7 @@ class DtuTrain:
                             continue
                         src_views = self.test_ref_views
                     metas.append((scan, light_idx, ref_view, list(src_views)))
-        return metas, ref_src_pairs
+        return metas, dict(pairs)
 
     def _view_ids(self, meta):
         _, _, ref_view, src_views = meta
@@ -153,45 +156,14 @@ class DtuTrain:
     def __iter__(self):
         return (self[i] for i in range(len(self)))
 
-    # ---- per pixel
-    def _rays64(self, m_inv, origin=None):
-        """dtu_train.py:473-478 in its own calls: the float32 matrix times the float64 pixel table, minus the origin, over the
-        norm -- (3, H*W) float64"""
-        v = torch.from_numpy(np.matmul(torch.as_tensor(m_inv, dtype=torch.float32).numpy(), self.homo_pixel))[:3]
-        if origin is not None:
-            v = v - torch.as_tensor(origin, dtype=torch.float32)[:, None]
-        return v / torch.linalg.norm(v, dim=0, keepdim=True)
-
     def _cam_ray_d(self, m_inv):
         key = m_inv.numpy().tobytes()
         if key not in self._cam_rays:
             if len(self._cam_rays) >= 4:
                 self._cam_rays.clear()
-            d64 = self._rays64(m_inv)
+            d64 = pixel_rays64(m_inv, self.homo_pixel)
             self._cam_rays[key] = (d64.float().to(self.device), d64[2].contiguous().to(self.device))
         return self._cam_rays[key]
-
-    def _images(self, raw):
-        if self.device.type == "cuda":
-            from . import ops
-
-            with torch.cuda.device(self.device):
-                return ops.image_resize_u8(torch.from_numpy(raw).to(self.device), self.img_H, self.img_W)
-        return torch.from_numpy(image_planes_host(raw, self.img_H, self.img_W))
-
-    def _depths(self, decoded, scale_factor, cam_ray_z):
-        y0, x0 = PFM_CROP
-        out = []
-        for rows, bottom_up in decoded:
-            if self.device.type == "cuda":
-                from . import ops
-
-                with torch.cuda.device(self.device):
-                    out.append(ops.depth_gt_prepare(torch.from_numpy(rows).to(self.device), bottom_up, y0, x0, self.img_H, self.img_W,
-                                                    scale_factor, cam_ray_z))
-            else:
-                out.append(torch.from_numpy(depth_gt_host(rows, bottom_up, y0, x0, self.img_H, self.img_W, scale_factor, cam_ray_z.numpy())))
-        return torch.stack(out)
 
     # ---- dtu_train.py:318-498
     def __getitem__(self, idx):
@@ -220,43 +192,20 @@ class DtuTrain:
         view_ids = self._view_ids(meta)
         raw, depth_rows = loaded
         w2c_ref_inv = np.linalg.inv(self.all_extrinsics[ref_view])
-        intrinsics, w2cs, near_fars, proj_matrices = [], [], [], []
-        for i, vid in enumerate(view_ids):
-            near_fars.append(self.all_near_fars[vid])
-            intrinsics.append(self.all_intrinsics[vid])
-            w2cs.append(self.all_extrinsics[vid] @ w2c_ref_inv)
-            if i >= 1:
-                intrinsic_cp = self.all_intrinsics[vid].copy()[:3, :3]
-                intrinsic_cp[:2] /= 4
-                proj_mat = np.zeros(shape=(2, 4, 4), dtype=np.float32)
-                proj_mat[0, :4, :4] = self.all_extrinsics[vid]
-                proj_mat[1, :3, :3] = intrinsic_cp
-                proj_matrices.append(proj_mat)
+        intrinsics = [self.all_intrinsics[vid] for vid in view_ids]
+        w2cs = [self.all_extrinsics[vid] @ w2c_ref_inv for vid in view_ids]
+        near_fars = [self.all_near_fars[vid] for vid in view_ids]
         depth_max = self.depth_interval * self.ndepths + self.depth_min
         depth_values_org_scale = np.arange(self.depth_min, depth_max, self.depth_interval, dtype=np.float32)
-        proj_matrices = np.stack(proj_matrices)
-        stage2, stage3 = proj_matrices.copy(), proj_matrices.copy()
-        stage2[:, 1, :2, :] = proj_matrices[:, 1, :2, :] * 2
-        stage3[:, 1, :2, :] = proj_matrices[:, 1, :2, :] * 4
+        proj_matrices = cameras.proj_matrices_ms(np.stack([self.all_extrinsics[vid] for vid in view_ids[1:]]), np.stack(intrinsics[1:]))
 
         # cal_scale_mat (dtu_train.py:299-307)
-        center, radius, _ = get_boundingbox([self.img_H, self.img_W], torch.from_numpy(np.stack(intrinsics)),
-                                            torch.from_numpy(np.stack(w2cs)), near_fars)
-        radius = radius * 1.1
-        scale_mat = np.diag([radius, radius, radius, 1.0])
-        scale_mat[:3, 3] = center.cpu().numpy()
-        scale_mat = scale_mat.astype(np.float32)
-        scale_factor = 1. / radius.cpu().numpy()
-
-        new_near_fars, new_w2cs, new_c2ws = [], [], []
-        for intrinsic, extrinsic in zip(intrinsics, w2cs):
-            P = (intrinsic @ extrinsic @ scale_mat)[:3, :4]
-            c2w = load_K_Rt_from_P(P)[1]
-            new_w2cs.append(np.linalg.inv(c2w))
-            new_c2ws.append(c2w)
-            dist = np.sqrt(np.sum(c2w[:3, 3] ** 2))
-            new_near_fars.append([0.95 * (dist - 1), 1.05 * (dist + 1)])
-        intrinsics, w2cs, c2ws, near_fars = np.stack(intrinsics), np.stack(new_w2cs), np.stack(new_c2ws), np.stack(new_near_fars)
+        center, radius, _ = cameras.get_boundingbox([self.img_H, self.img_W], torch.from_numpy(np.stack(intrinsics)),
+                                                    torch.from_numpy(np.stack(w2cs)), near_fars)
+        scale_mat, scale_factor = cameras.scale_matrix(center, radius)
+        scaled = [cameras.scaled_camera((intrinsic @ extrinsic @ scale_mat)[:3, :4]) for intrinsic, extrinsic in zip(intrinsics, w2cs)]
+        intrinsics = np.stack(intrinsics)
+        w2cs, c2ws, near_fars = (np.stack(x) for x in zip(*scaled))
 
         s = {}
         s["w2cs"] = torch.from_numpy(w2cs.astype(np.float32))
@@ -265,10 +214,8 @@ class DtuTrain:
         s["intrinsics"] = torch.from_numpy(intrinsics.astype(np.float32))[:, :3, :3]
         s["scale_mat"] = torch.from_numpy(scale_mat)
         s["trans_mat"] = torch.from_numpy(w2c_ref_inv)
-        intrinsics_pad = torch.eye(4).expand(len(s["w2cs"]), 4, 4).clone()
-        intrinsics_pad[:, :3, :3] = s["intrinsics"]
-        normalize_matrix = torch.tensor([[1 / ((self.img_W - 1) / 2), 0, -1, 0], [0, 1 / ((self.img_H - 1) / 2), -1, 0],
-                                         [0, 0, 1, 0], [0, 0, 0, 1]])
+        intrinsics_pad = cameras.pad_intrinsics(s["intrinsics"])
+        normalize_matrix = cameras.normalize_matrix(self.img_H, self.img_W)
         s["ref_pose"] = normalize_matrix @ (intrinsics_pad @ s["w2cs"])[0]
         s["source_poses"] = normalize_matrix @ (intrinsics_pad @ s["w2cs"])[1:]
         s["ref_pose_inv"] = torch.inverse(s["ref_pose"])
@@ -279,18 +226,14 @@ class DtuTrain:
         batch = {k: v.contiguous()[None].to(self.device) for k, v in s.items()}
 
         cam_ray_d, cam_ray_z = self._cam_ray_d(torch.inverse(normalize_matrix @ intrinsics_pad[0]))
-        if self.device.type == "cuda":
-            from . import ops
-
-            ray_d = ops.pixel_rays(s["ref_pose_inv"].numpy(), self.img_H, self.img_W, s["ray_o"].numpy(), self.device)
-        else:
-            ray_d = self._rays64(s["ref_pose_inv"], s["ray_o"]).float()
-        images = self._images(np.stack(raw))
+        ray_d = pixel_rays(self.device, s["ref_pose_inv"], self.img_H, self.img_W, s["ray_o"], self.homo_pixel)
+        images = image_planes(self.device, np.stack(raw), self.img_H, self.img_W)
         batch["images"] = images[None]
         batch["ref_img"], batch["source_imgs"] = images[0][None], images[1:][None]
         batch["ray_d"], batch["cam_ray_d"] = ray_d[None], cam_ray_d[None]
-        batch["depths_h"] = self._depths(depth_rows, float(np.float32(scale_factor)), cam_ray_z)[None]
-        batch["proj_matrices"] = {k: torch.from_numpy(v)[None].to(self.device)
-                                  for k, v in (("stage1", proj_matrices), ("stage2", stage2), ("stage3", stage3))}
+        y0, x0 = PFM_CROP
+        batch["depths_h"] = torch.stack([depth_gt(self.device, rows, bottom_up, y0, x0, self.img_H, self.img_W,
+                                                  float(np.float32(scale_factor)), cam_ray_z) for rows, bottom_up in depth_rows])[None]
+        batch["proj_matrices"] = {k: torch.from_numpy(v)[None].to(self.device) for k, v in proj_matrices.items()}
         batch["meta"] = [str(scan) + "_light" + str(light_idx) + "_refview" + str(ref_view)]
         return batch
