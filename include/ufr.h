@@ -605,6 +605,25 @@ int ufr_marching_cubes_emit(const float* vol, const int32_t* dim, float level, v
                             float* verts, float* normals, int32_t* faces, int32_t n_verts, int32_t n_faces, ufr_stream stream);
 int ufr_marching_cubes_table(int8_t* out, int32_t out_len);
 
+/* ---- the similarity field of a frame's matching features (ABI 507, additive) ----------------------------------
+ * UFORecon.extract_fields with query_cond_info (model.py:891-911, 218-305): u (X,Y,Z) fp32, z fastest (device; the layout
+ * ufr_marching_cubes_* takes), voxel (i,j,k) at p = (gx[i], gy[j], gz[k]).  gx / gy / gz are HOST fp32 tables of dim[0] /
+ * dim[1] / dim[2] entries (the reference's torch.linspace per axis); they are consumed before the call returns.
+ * Per view v: q = pose[v] (p, 1), xy = q.xy / q.z (ufr_project_gather's arithmetic), NO depth mask; the frame's match maps
+ * sampled bilinearly with align_corners=True and border clamping; for every pair (a, b), 0 <= a <= b <= NV-2, the sides (view
+ * a, chunk b) and (view b+1, chunk a), 8 groups of 4 channels each, cosine similarity by ufr_project_gather's sim8 expression;
+ * u = the mean over the pairs, then over the 8 groups.
+ * Two options, both off (= the reference) by default:
+ *   n_vis (X,Y,Z) uint8 (device, nullable): the number of views with q.z > 0 and -1 < x < 1 and -1 < y < 1.
+ *   min_views > 0: a voxel with n_vis < min_views gets u = -1.0 exactly (border clamping gives a voxel outside every
+ *     frustum an arbitrary similarity).
+ * One stated difference: a voxel whose projected x or y is not finite in some view (q.z = 0) gets u = -1.0; the reference
+ * would sample at NaN there.
+ * Asynchronous, no workspace.  UFR_ERR_ARG before any launch: a frame that is not prepared or has no match maps, a null
+ * table / dim / u, a dim below 2, X Y Z >= 2^31, min_views outside 0 .. NV.                                          */
+int ufr_similarity_field(const ufr_frame* frame, const float* gx, const float* gy, const float* gz, const int32_t* dim, float* u,
+                         uint8_t* n_vis, int32_t min_views, ufr_stream stream);
+
 /* ---- DTU chamfer evaluation of a mesh or point cloud (ABI 505) ----------------------------------------------
  * The device side of evaluation/dtu_eval.py: sample the mesh (:68-91), thin the cloud to the density (:105-115), nearest
  * neighbour distances and their means (:139-155).  Positions and distances are fp64 as in the reference; every count n, V, F

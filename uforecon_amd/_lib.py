@@ -144,6 +144,8 @@ SIGNATURES = {
     "ufr_marching_cubes_count": (C.c_int, [vp, C.POINTER(i32), C.c_float, vp, sz, C.POINTER(i32), vp]),
     "ufr_marching_cubes_emit": (C.c_int, [vp, C.POINTER(i32), C.c_float, vp, sz, vp, vp, vp, i32, i32, vp]),
     "ufr_marching_cubes_table": (C.c_int, [C.POINTER(C.c_int8), i32]),
+    "ufr_similarity_field": (C.c_int, [C.POINTER(Frame), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(i32), vp, vp, i32, vp]),
     "ufr_mesh_sample_workspace_bytes": (sz, [i64]),
     "ufr_mesh_sample_count": (C.c_int, [vp, vp, i64, i64, C.c_double, vp, sz, C.POINTER(i64), vp]),
     "ufr_mesh_sample_emit": (C.c_int, [vp, vp, i64, i64, C.c_double, vp, sz, vp, i64, vp]),

@@ -1,5 +1,5 @@
 // extern "C" surface of libufr.so (include/ufr.h), part 6 of 7: geometry after the network -- TSDF fusion, marching cubes,
-// the DTU chamfer evaluation, depth-map fusion, mesh cleaning and mesh rendering.  The count / emit pairs synchronise the
+// the similarity field, the DTU chamfer evaluation, depth-map fusion, mesh cleaning and mesh rendering.  The count / emit pairs synchronise the
 // stream to hand a count to the host; so do the rounds of the two fixpoints (point thinning, face components).
 #include "api_common.h"
 #include "mcubes_table.h"
@@ -233,6 +233,23 @@ int ufr_marching_cubes_table(int8_t* out, int32_t out_len) {
   UFR_REQUIRE(out_len >= 256 * UFR_MC_TABLE_ROW, "ufr_marching_cubes_table: out_len %d < %d", out_len, 256 * UFR_MC_TABLE_ROW);
   memcpy(out, kMcTable, sizeof(kMcTable));
   return UFR_MC_TABLE_ROW;
+}
+
+// ------------------------------------------------------------------ similarity field
+int ufr_similarity_field(const ufr_frame* frame, const float* gx, const float* gy, const float* gz, const int32_t* dim, float* u,
+                         uint8_t* n_vis, int32_t min_views, ufr_stream stream) {
+  const FrameDev* f = frame_of(frame);
+  UFR_REQUIRE(f, "ufr_similarity_field: frame handle not prepared");
+  UFR_REQUIRE(f->match, "ufr_similarity_field: the frame has no matching features");
+  UFR_REQUIRE(gx && gy && gz && dim && u, "ufr_similarity_field: null argument");
+  UFR_REQUIRE(dim[0] >= 2 && dim[1] >= 2 && dim[2] >= 2, "ufr_similarity_field: grid %dx%dx%d (every dim must be >= 2)", dim[0], dim[1],
+              dim[2]);
+  UFR_REQUIRE((long long)dim[0] * dim[1] * dim[2] < (1ll << 31), "ufr_similarity_field: grid %dx%dx%d has 2^31 voxels or more", dim[0],
+              dim[1], dim[2]);
+  UFR_REQUIRE(min_views >= 0 && min_views <= f->NV, "ufr_similarity_field: min_views %d (0 .. NV = %d)", min_views, f->NV);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("similarity_field", s, launch_similarity_field(*f, gx, gy, gz, dim, u, n_vis, min_views, s));
+  return UFR_OK;
 }
 
 // ------------------------------------------------------------------ DTU chamfer evaluation

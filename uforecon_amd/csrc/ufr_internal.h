@@ -143,6 +143,9 @@ hipError_t launch_mcubes_verts(const float* vol, const int* dim, float level, co
                                float* verts, float* normals, long long n_verts, hipStream_t s);
 hipError_t launch_mcubes_faces(const float* vol, const int* dim, float level, const long long* tile_off, const int* index,
                                int* faces, long long n_faces, hipStream_t s);
+// similarity_field.hip: the pair similarity of the match maps on a voxel grid; gx / gy / gz are HOST tables (kernel arguments)
+hipError_t launch_similarity_field(const FrameDev& f, const float* gx, const float* gy, const float* gz, const int* dim, float* u,
+                                   unsigned char* n_vis, int min_views, hipStream_t s);
 // chamfer.hip: DTU chamfer evaluation in fp64 (mesh sampling, cell keys, thinning rounds, nearest neighbours; see the file header)
 long long chamfer_blocks(long long n);   // blocks of the per-item kernels: sizes the per-block workspace arrays
 hipError_t launch_points_cell_keys(const double* pts, long long n, const double* origin, double cell, long long* keys,

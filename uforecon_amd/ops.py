@@ -808,6 +808,37 @@ def marching_cubes(vol: torch.Tensor, level: float = 0.0):
     return verts, faces, normals
 
 
+def grid_tables(bound_min, bound_max, resolution):
+    """The three coordinate tables of a voxel grid as the reference forms them (model.py:893-895): ``torch.linspace`` in
+    float32 per axis between the float32 values of the bounds.  ``resolution``: an int or (X, Y, Z).  Host tensors."""
+    dim = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(int(r) for r in resolution)
+    if len(dim) != 3:
+        raise UfrError(f"resolution {resolution!r}: expected an int or three ints")
+    lo = torch.as_tensor(bound_min, dtype=torch.float32).reshape(-1)
+    hi = torch.as_tensor(bound_max, dtype=torch.float32).reshape(-1)
+    if lo.numel() != 3 or hi.numel() != 3:
+        raise UfrError("bound_min / bound_max: expected three values each")
+    return tuple(torch.linspace(lo[a], hi[a], max(dim[a], 0), dtype=torch.float32).contiguous() for a in range(3))
+
+
+def similarity_field(frame: FrameHandle, bound_min, bound_max, resolution, min_views: int = 0, return_visibility: bool = False):
+    """The similarity field of a frame's matching features on a voxel grid (ufr_similarity_field): ``u`` (X,Y,Z) fp32 on the
+    frame's device, z fastest, voxel (i,j,k) at ``grid_tables(...)[0][i], [1][j], [2][k]``; the mean over view pairs and the 8
+    channel groups of the gather's pair similarity, without a depth mask, border clamped.  ``min_views > 0``: voxels that
+    fewer views see get -1.0.  ``return_visibility``: also ``n_vis`` (X,Y,Z) uint8.  ``u`` starts NaN-filled: a voxel the
+    kernel leaves unwritten cannot pass for a value.  Asynchronous on the current stream."""
+    gx, gy, gz = grid_tables(bound_min, bound_max, resolution)
+    dims = [gx.numel(), gy.numel(), gz.numel()]
+    ok = all(d >= 2 for d in dims) and dims[0] * dims[1] * dims[2] < 2 ** 31    # the library refuses these before a launch; so does the allocation here
+    u = torch.full(dims if ok else [1], float("nan"), dtype=torch.float32, device=frame.device)
+    n_vis = torch.full(dims if ok else [1], 255, dtype=torch.uint8, device=frame.device) if return_visibility else None
+    fp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float))  # noqa: E731
+    _lib.check(_lib.load().ufr_similarity_field(C.byref(frame.frame), fp(gx), fp(gy), fp(gz), (C.c_int32 * 3)(*dims), u.data_ptr(),
+                                                None if n_vis is None else n_vis.data_ptr(), int(min_views), _stream()),
+               "ufr_similarity_field")
+    return (u, n_vis) if return_visibility else u
+
+
 def marching_cubes_table():
     """The kernel's 256-case triangle table as a (256, UFR_MC_TABLE_ROW) int8 array (host only; no GPU needed)."""
     import numpy as np

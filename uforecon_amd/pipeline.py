@@ -8,6 +8,8 @@ loads with strict=True.  `extract_geometry` follows code1/model.py:760-842 end t
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -103,6 +105,31 @@ class UFOReconInference(M.UFORecon):
         out_dir = out_dir if out_dir is not None else getattr(self.args, "out_dir", None)
         return M.UFORecon.extract_geometry(self, batch, source_imgs_feat, frustums, match_feature, out_dir=out_dir,
                                            uniforms=uniforms)
+
+    @torch.no_grad()
+    def extract_similarity(self, batch, batch_idx=0, bound_min=(-1., -1., -1.), bound_max=(1., 1., 1.), resolution=512, threshold=0.99,
+                           min_views=0, out_dir=None):
+        """code1/model.py:844-888: the mean grouped cosine similarity of the frame's matching features on a ``resolution``^3
+        grid over [bound_min, bound_max] (`similarity_field.similarity_field`), `fraction occupied` printed, marching cubes at
+        ``threshold``.  ``min_views > 0`` masks voxels that fewer views see (off = the reference).  Three stated differences
+        from the reference:
+          * with ``out_dir`` the mesh goes to ``<out_dir>/sim_<scan>_<resolution>.ply`` through `tsdf.meshwrite`, in scene
+            coordinates; the reference writes ``sim_<scan>_512.dae`` through PyMCubes into the working directory, in voxel
+            indices.  Without ``out_dir`` no mesh is extracted.
+          * the return value ``u`` (X,Y,Z) is a device tensor; the reference returns a numpy array.
+          * ``threshold`` is honoured; the reference overwrites its argument with 0.99, which is the default here."""
+        from . import similarity_field as SF
+
+        source_imgs_feat, frustums, match_feature = self.encode_frame(batch)
+        fh = self.frame_handle(batch, source_imgs_feat, frustums, match_feature)
+        u = SF.similarity_field(fh, bound_min, bound_max, resolution, min_views=min_views)
+        print("fraction occupied", float((u > threshold).float().mean()))
+        if out_dir is not None:
+            verts, faces, normals = SF.field_mesh(u, bound_min, bound_max, level=threshold)
+            print("done", tuple(verts.shape), tuple(faces.shape))
+            os.makedirs(out_dir, exist_ok=True)
+            SF.write_mesh(os.path.join(out_dir, "sim_%s_%s.ply" % (SF.scan_name(batch), SF.resolution_tag(resolution))), verts, faces, normals)
+        return u
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0, logdir=None, uniforms=None):
