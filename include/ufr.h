@@ -809,6 +809,47 @@ int ufr_raster_frames(const double* verts, const int32_t* faces, int64_t V, int6
                       void* workspace, size_t workspace_bytes, ufr_stream stream);
 int ufr_raster_downsample(const uint8_t* src, int32_t n, int32_t H, int32_t W, int32_t s, uint8_t* dst, ufr_stream stream);
 
+/* ---- point-cloud rendering (ABI 507, additive) ----------------------------------------------------------------
+ * A z-buffered splat renderer with eye-dome lighting for the clouds the chain writes (depth_fusion's and tsdf's PLY files under pcd/,
+ * dtu_eval's error clouds): the reference looks at them in an Open3D window, here there is no display.
+ * uforecon_amd/render_trajectory.py (render_points) is the caller, tests/points_ref.py the numpy statement of every rule
+ * below.  points (N,3) fp64, images row-major: device.  H, W >= 1, H * W < 2^31; 1 <= N <= 2^32 - 2 (2^31 - 1 with point_id).
+ *
+ * ufr_splat_frames: n_frames >= 1 views of the cloud in one call.  k 3x3 (shared; the caller has divided it by k[2][2]) and
+ *   w2c (n_frames,4,4): HOST fp64 row-major, w2c the caller's fp64 inverse of the camera-to-world matrix.  Per frame the key
+ *   image (H,W) uint64 is set to all ones, then
+ *   (1) one thread per point, in fp64, products summed left to right, no fused multiply-add:
+ *         c = w2c[:3,:3] p + w2c[:3,3] (the three products, then the translation),  q = k c,
+ *         px = rint(q.x / q.z), py = rint(q.y / q.z), round half to even; pixel centres are the integers, as in
+ *         ufr_mesh_first_hit.
+ *       The point is dropped when a coordinate of p is not finite, when not c.z > z_min (z_min >= 0), when px or py is not
+ *       finite, and when its whole footprint lies outside the image.  Footprint: the pixels (px + dx, py + dy) with
+ *       dx^2 + dy^2 <= r^2 + r, r = radius in 0..4 (0: one pixel, 1: the 3x3 block, 2: a 21-pixel disc), clipped to the image.
+ *       Every pixel of it takes key = (bits of (float)c.z) << 32 | point index with a 64-bit unsigned atomic minimum: the
+ *       nearest (float) depth wins, ties go to the lowest index, whatever the order of arrival -- the same bits run after run.
+ *       (The pixel's key is read with a plain load first and the atomic skipped when the point cannot win.)
+ *   (2) one thread per pixel resolves.  Key all ones: background, depth 0, point_id -1.  Otherwise z = the stored float and,
+ *       in fp64 with z widened,
+ *         o_k = max(0, log2(z) - log2(z_k)) over the neighbours (x - d, y), (x + d, y), (x, y - d), (x, y + d), d = edl_radius
+ *               >= 1; a neighbour that is empty or outside the image gives 0,
+ *         s = ((o_1 + o_2) + o_3) + o_4,  I = exp(-(edl_strength * s) / 4): eye-dome lighting, a pixel darkens by how far it
+ *               lies behind its neighbours in log depth; edl_strength = 0 or s = 0 give I = 1 with no call of exp,
+ *         colour = colors[index] ((N,3) uint8, device, nullable) or 255 * base_color,
+ *         pixel = rint(colour * I), round half to even, clamped to 0..255.
+ *   base_color: HOST float[3] in 0..1, nullable = white; background: HOST uint8[3], nullable = 255 255 255.  Outputs (device,
+ *   n_frames images): image (H,W,3) uint8; depth (H,W) fp32, nullable = the stored z: z-depth, comparable with
+ *   ufr_raster_frames' depth; point_id (H,W) int32, nullable.  workspace >= ufr_splat_frames_workspace_bytes(H, W) (device; 0
+ *   for unsupported sizes).  A camera that is not finite or whose w2c[:3,:3] is singular fails before anything is launched.
+ *   Enqueues 1 memset and 2 kernels per frame and synchronises nowhere.
+ * Every argument error (null pointer, N < 1 or too large, H, W or n_frames < 1, H * W >= 2^31, radius outside 0..4, edl_radius
+ * < 1, a negative or non-finite edl_strength or z_min, a base colour outside 0..1, a workspace that is too small) is
+ * UFR_ERR_ARG with the reason in the thread's last-error text.                                                       */
+size_t ufr_splat_frames_workspace_bytes(int32_t H, int32_t W);
+int ufr_splat_frames(const double* points, int64_t N, const uint8_t* colors, const double* k, const double* w2c, int32_t n_frames,
+                     int32_t H, int32_t W, int32_t radius, double z_min, const float* base_color, const uint8_t* background,
+                     double edl_strength, int32_t edl_radius, uint8_t* image, float* depth, int32_t* point_id, void* workspace,
+                     size_t workspace_bytes, ufr_stream stream);
+
 /* ---- a scan loader's per-pixel work (ABI 507, additive) -----------------------------------------------------
  * What DtuFitSparse (code1/dataset/dtu_test_sparse.py:247-298, 412-429) computes per pixel; uforecon_amd/dtu_scan.py does the
  * 4x4 camera arithmetic on the host and calls these two.  Neither synchronises.

@@ -1,5 +1,5 @@
 // extern "C" surface of libufr.so (include/ufr.h), part 6 of 7: geometry after the network -- TSDF fusion, marching cubes,
-// the similarity field, the DTU chamfer evaluation, depth-map fusion, mesh cleaning and mesh rendering.  The count / emit pairs synchronise the
+// the similarity field, the DTU chamfer evaluation, depth-map fusion, mesh cleaning, mesh rendering and point-cloud rendering.  The count / emit pairs synchronise the
 // stream to hand a count to the host; so do the rounds of the two fixpoints (point thinning, face components).
 #include "api_common.h"
 #include "mcubes_table.h"
@@ -127,6 +127,9 @@ RasterFramesWs carve_raster_frames(Carver& c, long long F, long long pixels) {
   w.face_img = c.take<int>((size_t)pixels);
   return w;
 }
+
+// point-cloud rendering: [key image uint64 per pixel]
+unsigned long long* carve_splat_frames(Carver& c, long long pixels) { return c.take<unsigned long long>((size_t)pixels); }
 
 // components: [pair faces int32 x2 per edge slot | parent int32 per face | adjacency flag uint8 per face | changed int32]
 struct ComponentsWs { int *pair_a, *pair_b, *parent, *changed; unsigned char* has_adj; };
@@ -576,6 +579,54 @@ int ufr_raster_downsample(const uint8_t* src, int32_t n, int32_t H, int32_t W, i
   UFR_REQUIRE((long long)n * H * W * 3 < (1ll << 38), "%s: %d images of %dx%d have 2^38 bytes or more", who, n, H, W);
   hipStream_t st = static_cast<hipStream_t>(stream);
   UFR_TIMED("raster_downsample", st, launch_raster_downsample(src, n, H, W, s, dst, st));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ point-cloud rendering
+size_t ufr_splat_frames_workspace_bytes(int32_t H, int32_t W) {
+  if (H < 1 || W < 1 || (long long)H * W >= (1ll << 31)) return 0;
+  return carved_bytes(carve_splat_frames, (long long)H * W);
+}
+
+int ufr_splat_frames(const double* points, int64_t N, const uint8_t* colors, const double* k, const double* w2c, int32_t n_frames,
+                     int32_t H, int32_t W, int32_t radius, double z_min, const float* base_color, const uint8_t* background,
+                     double edl_strength, int32_t edl_radius, uint8_t* image, float* depth, int32_t* point_id, void* workspace,
+                     size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_splat_frames";
+  UFR_REQUIRE(points && k && w2c && image && workspace, "%s: null argument", who);
+  UFR_REQUIRE(N >= 1 && N <= (1ll << 32) - 2, "%s: N %lld (must be 1 .. 2^32 - 2)", who, (long long)N);
+  UFR_REQUIRE(!point_id || N <= kChMax, "%s: N %lld with a point-id image (must be 1 .. 2^31 - 1)", who, (long long)N);
+  UFR_REQUIRE(n_frames >= 1, "%s: n_frames %d (must be >= 1)", who, n_frames);
+  UFR_CHECK(depth_image_check(who, H, W));
+  UFR_REQUIRE(radius >= 0 && radius <= 4, "%s: radius %d (must be 0 .. 4)", who, radius);
+  UFR_REQUIRE(edl_radius >= 1, "%s: edl_radius %d (must be >= 1)", who, edl_radius);
+  UFR_REQUIRE(edl_strength >= 0.0 && std::isfinite(edl_strength), "%s: edl_strength %g (must be >= 0 and finite)", who, edl_strength);
+  UFR_REQUIRE(z_min >= 0.0 && std::isfinite(z_min), "%s: z_min %g (must be >= 0 and finite)", who, z_min);
+  double base[3] = {1.0, 1.0, 1.0};
+  unsigned char bg[3] = {255, 255, 255};
+  for (int c = 0; c < 3; ++c) {
+    if (base_color) base[c] = (double)base_color[c];
+    if (background) bg[c] = background[c];
+    UFR_REQUIRE(base[c] >= 0.0 && base[c] <= 1.0, "%s: base colour %g (must be 0 .. 1)", who, base[c]);
+  }
+  Carver cv(workspace);
+  unsigned long long* keys = carve_splat_frames(cv, (long long)H * W);
+  UFR_REQUIRE(workspace_bytes >= cv.off, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, cv.off);
+  for (int i = 0; i < 9; ++i) UFR_REQUIRE(std::isfinite(k[i]), "%s: k is not finite", who);
+  for (int32_t f = 0; f < n_frames; ++f) {   // all, before any launch
+    const double* m = w2c + 16 * (size_t)f;
+    for (int i = 0; i < 16; ++i) UFR_REQUIRE(std::isfinite(m[i]), "%s: frame %d: w2c is not finite", who, f);
+    const double r3[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
+    double inv[9];
+    UFR_REQUIRE(invert3(r3, inv), "%s: frame %d: w2c is singular", who, f);
+  }
+  const size_t px = (size_t)H * W;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int32_t f = 0; f < n_frames; ++f) {   // launches only: the cameras travel as kernel arguments, nothing waits for a frame
+    UFR_TIMED("splat", s, launch_splat(points, N, k, w2c + 16 * (size_t)f, H, W, radius, z_min, keys, s));
+    UFR_TIMED("splat_resolve", s, launch_splat_resolve(keys, N, colors, base, bg, edl_strength, edl_radius, H, W, image + 3 * px * f,
+        depth ? depth + px * f : nullptr, point_id ? point_id + px * f : nullptr, s));
+  }
   return UFR_OK;
 }
 

@@ -196,6 +196,13 @@ hipError_t launch_raster_shade(const double* verts, const int* faces, long long 
                                const double* proj, const double* base, double ambient, const unsigned char* bg, const int* face_img,
                                int H, int W, unsigned char* image, float* depth, int* face_out, float* normal_out, hipStream_t s);
 hipError_t launch_raster_downsample(const unsigned char* src, long long n, int H, int W, int sf, unsigned char* dst, hipStream_t s);
+// splat.hip: point-cloud rendering -- z-buffered splat into a key image, resolve with eye-dome lighting (see the file header)
+// (k 3x3 and w2c 4x4: host fp64; launch_splat presets the key image before its kernel)
+hipError_t launch_splat(const double* points, long long N, const double* k, const double* w2c, int H, int W, int radius, double z_min,
+                        unsigned long long* keys, hipStream_t s);
+hipError_t launch_splat_resolve(const unsigned long long* keys, long long N, const unsigned char* colors, const double* base,
+                                const unsigned char* bg, double edl_strength, int edl_radius, int H, int W, unsigned char* image,
+                                float* depth, int* point_id, hipStream_t s);
 // frame_input.hip: a scan loader's per-pixel work -- 8-bit images to resized, cropped float planes; ray tables (see the file header)
 // (mask: null, or a second source (n,Hs,Ws) resized by the same rule and multiplied in as m / 254)
 hipError_t launch_image_resize_u8(const unsigned char* src, const unsigned char* mask, long long n, int Hs, int Ws, int H, int W, int x0,

@@ -6,7 +6,9 @@ point sampling, thinning and nearest-neighbour passes as HIP kernels (csrc/chamf
 
 takes the reference's flags and paths and appends the reference's lines to ``<outdir>/eval_final.log``.  The one
 difference: the reference shuffles the cloud with an unseeded generator, here the permutation is
-``numpy.random.default_rng(seed).permutation(N)`` (``--seed``, default 0), so a run can be repeated.
+``numpy.random.default_rng(seed).permutation(N)`` (``--seed``, default 0), so a run can be repeated.  ``--write_vis`` adds what
+the reference only describes in a commented-out block: the error-coloured clouds ``<vis_out_dir>/vis_<scan:03>_d2s.ply`` and
+``..._s2d.ply`` (``error_clouds``), which ``python -m uforecon_amd.render_trajectory --ply`` renders.
 
 Inputs of any float dtype are converted to float64 once on entry, as the reference sees the text of a PLY file as
 float64; ``chamfer()`` on an in-memory fp32 mesh and the command line on its ``%f``-formatted PLY file may therefore differ
@@ -203,9 +205,66 @@ def chamfer(data, gt_points, obs_mask, bb, res, plane, *, density: float = 0.2, 
     return out
 
 
-def evaluate_scan(data_path: str, mode: str, gt_path: str, obs_path: str, plane_path: str, **kw) -> dict:
+def error_clouds(result: dict, gt_points, max_dist: float = 20, vis_dist: float = 10):
+    """The error-coloured clouds of one scan, ``((points, colors), (points, colors))`` for d2s and s2d, from the result of
+    ``chamfer(..., details=True)``: float64 (n,3) points and uint8 (n,3) colours, tensors on the device the result's tensors
+    live on (torch ops only; CPU tensors work).  The rule is the one the reference's evaluation/dtu_eval.py describes in a
+    commented-out block (:159-173), in this module's names:
+
+    * d2s: every point of the thinned cloud ``data_pcd[thin_mask]``, blue; the points that passed the box, the grid and ObsMask
+      -- the ones ``dist_d2s`` belongs to, in its order -- get ``a = min(dist, vis_dist) / vis_dist`` and the colour
+      ``(1, 1 - a, 1 - a)``, white to red; those with ``dist >= max_dist`` (infinite included) are green;
+    * s2d: every ground-truth point, blue; the points above the plane are coloured the same way by ``dist_s2d``.
+
+    Bytes are ``rint(255 c)`` in float64, round half to even."""
+    import torch
+
+    max_dist, vis_dist = float(max_dist), float(vis_dist)
+    if not vis_dist > 0:
+        raise ValueError(f"error_clouds: vis_dist {vis_dist} (must be positive)")
+    data_down = result["data_pcd"][result["thin_mask"]]
+    dev = data_down.device
+    gt = gt_points if isinstance(gt_points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gt_points))
+    gt = gt.to(device=dev, dtype=torch.float64).reshape(-1, 3)
+
+    def paint(n, where, dist):
+        col = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        col[:, 2] = 1.0                                                       # blue
+        dist = dist.to(torch.float64).reshape(-1)
+        a = torch.clamp(dist, max=vis_dist) / vis_dist
+        ramp = torch.stack([torch.ones_like(a), 1.0 - a, 1.0 - a], 1)
+        ramp[dist >= max_dist] = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64, device=dev)   # green
+        col[where] = ramp
+        return torch.round(255.0 * col).to(torch.uint8)                       # half to even
+
+    idx = torch.nonzero(result["inbound"]).reshape(-1)[result["grid_inbound"]][result["in_obs"]]
+    above = torch.nonzero(result["above"]).reshape(-1)
+    return ((data_down, paint(data_down.shape[0], idx, result["dist_d2s"])),
+            (gt, paint(gt.shape[0], above, result["dist_s2d"])))
+
+
+def write_ply_points(filename: str, points, colors) -> None:
+    """binary little-endian PLY of a coloured cloud: double x / y / z, uchar red / green / blue (``read_ply(...,
+    with_colors=True)`` reads it back bit for bit)"""
+    points = np.asarray(points, np.float64).reshape(-1, 3)
+    colors = np.asarray(colors).reshape(-1, 3)
+    if colors.dtype != np.uint8 or len(colors) != len(points):
+        raise ValueError(f"write_ply_points: colors {colors.shape} {colors.dtype}: expected ({len(points)}, 3) uint8")
+    rec = np.empty(len(points), dtype=[("p", "<f8", (3,)), ("c", "u1", (3,))])
+    rec["p"] = points
+    rec["c"] = colors
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(rec))
+    with open(filename, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def evaluate_scan(data_path: str, mode: str, gt_path: str, obs_path: str, plane_path: str, vis_prefix=None, vis_dist: float = 10,
+                  **kw) -> dict:
     """``chamfer`` on files: a mesh or point-cloud PLY, the ground-truth PLY, ObsMask*_10.mat and Plane*.mat (or .npz files
-    with the same keys)."""
+    with the same keys).  With ``vis_prefix`` the error clouds (``error_clouds``) go to ``<vis_prefix>_d2s.ply`` and
+    ``<vis_prefix>_s2d.ply``; the scores are the same either way."""
     verts, faces = read_ply(data_path)
     if mode == "mesh":
         if faces is None:
@@ -216,7 +275,13 @@ def evaluate_scan(data_path: str, mode: str, gt_path: str, obs_path: str, plane_
     gt, _ = read_ply(gt_path)
     obs_mask, bb, res = _load_arrays(obs_path, ["ObsMask", "BB", "Res"])
     (plane,) = _load_arrays(plane_path, ["P"])
-    return chamfer(data, gt, obs_mask, bb, res, plane, **kw)
+    if vis_prefix is None:
+        return chamfer(data, gt, obs_mask, bb, res, plane, **kw)
+    r = chamfer(data, gt, obs_mask, bb, res, plane, details=True, **kw)
+    clouds = error_clouds(r, gt, max_dist=kw.get("max_dist", 20), vis_dist=vis_dist)
+    for name, (pts, col) in zip(("d2s", "s2d"), clouds):
+        write_ply_points(f"{vis_prefix}_{name}.ply", pts.cpu().numpy(), col.cpu().numpy())
+    return r
 
 
 def main(argv=None) -> int:
@@ -225,17 +290,22 @@ def main(argv=None) -> int:
     ap.add_argument("--scan", type=int, default=1, help="accepted and unused, as in the reference")
     ap.add_argument("--mode", type=str, default="mesh", choices=["mesh", "pcd"])
     ap.add_argument("--dataset_dir", type=str, default="./MVS_Data")
-    ap.add_argument("--vis_out_dir", type=str, default=".", help="accepted and unused, as in the reference")
+    ap.add_argument("--vis_out_dir", type=str, default=".", help="directory of the error clouds; unused without --write_vis")
     ap.add_argument("--downsample_density", type=float, default=0.2)
     ap.add_argument("--patch_size", type=float, default=60)
     ap.add_argument("--max_dist", type=float, default=20)
-    ap.add_argument("--visualize_threshold", type=float, default=10, help="accepted and unused, as in the reference")
+    ap.add_argument("--visualize_threshold", type=float, default=10,
+                    help="distance at which an error cloud's ramp reaches full red; unused without --write_vis")
     ap.add_argument("--scans", type=int, nargs="+", default=DTU_SCANS, help="scan numbers (default: the reference's 15 test scans)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the shuffle before thinning")
     ap.add_argument("--mesh_dir", type=str, default=None,
                     help="directory holding scan{N}.ply (default <outdir>/mesh/final; <outdir>/mesh scores the un-cleaned "
                          "meshes that `python -m uforecon_amd.tsdf` writes)")
+    ap.add_argument("--write_vis", action="store_true",
+                    help="write the error-coloured clouds <vis_out_dir>/vis_<scan:03>_d2s.ply and ..._s2d.ply of every scan")
     args = ap.parse_args(argv)
+    if args.write_vis:
+        os.makedirs(args.vis_out_dir, exist_ok=True)
 
     log = logging.getLogger("uforecon_amd.dtu_eval")
     handler = logging.FileHandler(f"{args.outdir}/eval_final.log")
@@ -255,7 +325,9 @@ def main(argv=None) -> int:
                 data = os.path.join(args.outdir, "pcd", "scan{}.ply".format(scan))
             r = evaluate_scan(data, args.mode, f"{args.dataset_dir}/Points/stl/stl{scan:03}_total.ply",
                               _pick(f"{args.dataset_dir}/ObsMask/ObsMask{scan}_10"), _pick(f"{args.dataset_dir}/ObsMask/Plane{scan}"),
-                              density=args.downsample_density, patch=args.patch_size, max_dist=args.max_dist, seed=args.seed)
+                              density=args.downsample_density, patch=args.patch_size, max_dist=args.max_dist, seed=args.seed,
+                              vis_prefix=f"{args.vis_out_dir}/vis_{scan:03}" if args.write_vis else None,
+                              vis_dist=args.visualize_threshold)
             print(scan, r["d2s"], r["s2d"], r["overall"])
             log.info("scan: {} | d2s:{} | s2d:{} | all: {}".format(scan, r["d2s"], r["s2d"], r["overall"]))
             d2s_l.append(r["d2s"])

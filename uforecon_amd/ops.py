@@ -1298,6 +1298,60 @@ def raster_downsample(images: torch.Tensor, s: int) -> torch.Tensor:
     return out
 
 
+# ---- point-cloud rendering (csrc/splat.hip; uforecon_amd/render_trajectory.py's render_points is the caller)
+def splat_frames(points: torch.Tensor, k, w2cs, H: int, W: int, colors: Optional[torch.Tensor] = None, radius: int = 1,
+                 z_min: float = 0.0, base_color=(1.0, 1.0, 1.0), background=(255, 255, 255), edl_strength: float = 0.0,
+                 edl_radius: int = 1, return_depth: bool = False, return_point_ids: bool = False):
+    """ufr_splat_frames: ``n`` z-buffered splat views of a point cloud in one call (include/ufr.h states every rule).
+    ``points`` (N,3) CUDA float64; ``k`` 3x3 and ``w2cs`` (n,4,4): host float64 arrays, ``k`` already divided by ``k[2,2]``,
+    ``w2cs`` the world-to-camera matrices; ``colors`` (N,3) CUDA uint8 or None (``base_color``, 0..1); ``radius`` 0..4 the
+    footprint; ``edl_strength`` >= 0 and ``edl_radius`` >= 1 the eye-dome lighting.  Returns a dict: ``image`` (n,H,W,3) uint8,
+    and when asked ``depth`` (n,H,W) float32 z-depth (0: empty), ``point_id`` (n,H,W) int32 (-1: empty).  No points: the
+    background, without a library call.  Synchronises nowhere."""
+    import numpy as np
+
+    pp = _points64(points, "points")
+    N = int(points.shape[0])
+    kk = np.ascontiguousarray(np.asarray(k, np.float64))
+    wc = np.ascontiguousarray(np.asarray(w2cs, np.float64))
+    if kk.shape != (3, 3) or wc.ndim != 3 or wc.shape[1:] != (4, 4) or wc.shape[0] < 1:
+        raise UfrError(f"splat_frames: k {kk.shape}, w2cs {wc.shape}: expected (3, 3) and (n, 4, 4) with n >= 1")
+    n, H, W = int(wc.shape[0]), int(H), int(W)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise UfrError(f"splat_frames: image {H}x{W} (H, W >= 1, H * W < 2^31)")
+    base = np.ascontiguousarray(np.asarray(base_color, np.float32).reshape(-1))
+    bg = np.ascontiguousarray(np.asarray(background).reshape(-1))
+    if base.shape != (3,) or not ((base >= 0) & (base <= 1)).all():
+        raise UfrError(f"splat_frames: base_color {base_color!r} (three values in 0 .. 1)")
+    if bg.shape != (3,) or not ((bg >= 0) & (bg <= 255) & (bg == np.rint(bg))).all():
+        raise UfrError(f"splat_frames: background {background!r} (three integers in 0 .. 255)")
+    bg = np.ascontiguousarray(bg.astype(np.uint8))
+    pc = None
+    if colors is not None:
+        pc = _dev(colors, "colors", torch.uint8)
+        if tuple(colors.shape) != (N, 3):
+            raise UfrError(f"colors: expected shape ({N}, 3), got {tuple(colors.shape)}")
+    dev = points.device
+    out = {"image": torch.from_numpy(bg).to(dev).expand(n, H, W, 3).contiguous()}
+    if return_depth:
+        out["depth"] = torch.zeros((n, H, W), dtype=torch.float32, device=dev)
+    if return_point_ids:
+        out["point_id"] = torch.full((n, H, W), -1, dtype=torch.int32, device=dev)
+    if N == 0:
+        return out
+    lib = _lib.load()
+    nbytes = lib.ufr_splat_frames_workspace_bytes(H, W)
+    if nbytes == 0:
+        raise UfrError(f"splat_frames: image {H}x{W} unsupported")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dp, ptr = C.POINTER(C.c_double), lambda key: out[key].data_ptr() if key in out else None  # noqa: E731
+    _lib.check(lib.ufr_splat_frames(pp, N, pc, kk.ctypes.data_as(dp), wc.ctypes.data_as(dp), n, H, W, int(radius), float(z_min),
+                                    base.ctypes.data_as(C.POINTER(C.c_float)), bg.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                    float(edl_strength), int(edl_radius), out["image"].data_ptr(), ptr("depth"), ptr("point_id"),
+                                    ws.data_ptr(), nbytes, _stream()), "ufr_splat_frames")
+    return out
+
+
 # ---- a scan loader's per-pixel work (csrc/frame_input.hip; uforecon_amd/dtu_scan.py is the caller)
 def image_resize_u8(images: torch.Tensor, H: int, W: int, clip=(0, 0, 0, 0)) -> torch.Tensor:
     """ufr_image_resize_u8: (n,Hs,Ws,3) CUDA uint8 RGB -> (n,3,Ho,Wo) float32 planes in [0,1]: every image resized to ``H`` x

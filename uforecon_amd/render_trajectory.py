@@ -22,6 +22,15 @@ Differences from the reference, all deliberate: the reference renders through an
 ``render.json`` (not in its tree); the shading here is this module's own rule, not a copy of that window's.  The reference holds
 the key poses in float32; here they stay float64 until the ray generator narrows them.  ``--dump_poses`` writes the Open3D
 pinhole-camera JSON of every frame (the fields the reference fills), so that the path can be replayed where Open3D exists.
+
+Point clouds (the chain's ``pcd/scan<N>.ply`` of depth_fusion and tsdf, dtu_eval's error clouds) go through the same path, sizes
+and files, which the reference has no script for:
+
+    python -m uforecon_amd.render_trajectory --pcd_dir OUT/pcd --root_dir DTU_TEST --out_dir OUT/rendering
+        [--ply FILE ... --point_radius 1 --edl 200 --color vertex|uniform  and the flags above but --flat / --ambient]
+
+``render_points``: a z-buffered splat (one thread per point, a 64-bit atomic minimum of depth bits and index per covered pixel)
+and a resolve with eye-dome lighting (csrc/splat.hip through ``ops.splat_frames``); tests/points_ref.py is the numpy statement.
 """
 from __future__ import annotations
 
@@ -40,6 +49,9 @@ NUM_VIEWS = 240
 IMG_WH = [800, 640]
 ORIGINAL_IMG_WH = [1600, 1200]
 OFFSET_DIST = 25.0
+# eye-dome lighting strength of render_points.  Derived, not tuned on a real scan: a depth step of 1 % of the depth at one of
+# the four neighbours contributes log2(1.01) / 4 = 0.00359 to the exponent, and ln 2 / 0.00359 = 193 halves the brightness there.
+DEFAULT_EDL = 200.0
 
 
 # ------------------------------------------------------------------ the camera path
@@ -246,6 +258,80 @@ def render_mesh(verts, faces, K, c2ws, H, W, colors=None, smooth=True, ambient=0
     return res[0] if not extras else tuple(res)
 
 
+def render_points(points, K, c2ws, H, W, colors=None, radius=1, edl_strength=DEFAULT_EDL, edl_radius=None, base_color=(1, 1, 1),
+                  background=(255, 255, 255), supersample=1, return_depth=False, return_point_ids=False, device="cuda"):
+    """Splat views of a point cloud, the sibling of ``render_mesh``: uint8 (n,H,W,3) images as a numpy array.  ``points`` (N,3)
+    any float dtype, ``K`` 3x3 intrinsics (divided by ``K[2,2]`` as ``clean_mesh.ray_camera`` does), ``c2ws`` (n,4,4) or (4,4)
+    camera-to-world matrices (inverted here in float64), ``colors`` (N,3) uint8 or None (``base_color``, 0..1).  Every point
+    covers the pixels within ``radius`` (0..4) of its projection, the nearest point wins a pixel, and eye-dome lighting darkens
+    a pixel by how far it lies behind its four neighbours at distance ``edl_radius`` in log depth (``edl_strength=0``: none).
+    ``supersample`` s in 1..4 renders at s x the size with radius ``s * radius + (s - 1)`` (capped at 4) and ``edl_radius``
+    defaulting to s, so that a dot keeps its screen size, and box-filters down.  With ``return_depth`` / ``return_point_ids``
+    a tuple: the images, then float32 (n,H,W) z-depth (0: empty), int32 (n,H,W) point ids (-1: empty) -- at ``supersample=1``
+    only.  An empty cloud gives background frames.  Chunked from free device memory as ``render_mesh`` is."""
+    import torch
+
+    from . import ops
+    from ._lib import UfrError
+
+    points = np.asarray(points, np.float64).reshape(-1, 3)
+    c2ws = np.asarray(c2ws, np.float64)
+    if c2ws.ndim == 2:
+        c2ws = c2ws[None]
+    s, H, W, radius = int(supersample), int(H), int(W), int(radius)
+    extras = [k for k, on in (("depth", return_depth), ("point_id", return_point_ids)) if on]
+    if not 1 <= s <= 4:
+        raise UfrError(f"render_points: supersample {supersample} (must be 1 .. 4)")
+    if extras and s != 1:
+        raise UfrError("render_points: depth and point-id maps are only available at supersample=1")
+    if c2ws.ndim != 3 or c2ws.shape[1:] != (4, 4) or len(c2ws) < 1:
+        raise UfrError(f"render_points: c2ws {c2ws.shape}: expected (n, 4, 4) with n >= 1")
+    if H < 1 or W < 1:
+        raise UfrError(f"render_points: image {H}x{W} (H and W must be >= 1)")
+    if not 0 <= radius <= 4:
+        raise UfrError(f"render_points: radius {radius} (must be 0 .. 4)")
+    edl_radius = s if edl_radius is None else int(edl_radius)
+    if edl_radius < 1 or not (float(edl_strength) >= 0.0 and np.isfinite(float(edl_strength))):
+        raise UfrError(f"render_points: edl_strength {edl_strength}, edl_radius {edl_radius} (must be finite and >= 0, and >= 1)")
+    N, n = len(points), len(c2ws)
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.shape != (N, 3) or colors.dtype != np.uint8:
+            raise UfrError(f"render_points: colors {colors.shape} {colors.dtype}: expected ({N}, 3) uint8")
+    if N == 0:
+        bg = np.asarray(background).reshape(-1)
+        if bg.shape != (3,) or not ((bg >= 0) & (bg <= 255) & (bg == np.rint(bg))).all():
+            raise UfrError(f"render_points: background {background!r} (three integers in 0 .. 255)")
+        res = [np.broadcast_to(bg.astype(np.uint8), (n, H, W, 3)).copy()]
+        res += [np.zeros((n, H, W), np.float32) if k == "depth" else np.full((n, H, W), -1, np.int32) for k in extras]
+        return res[0] if not extras else tuple(res)
+    Ks = supersampled_intrinsics(K, s)
+    if not np.isfinite(Ks).all() or Ks[2, 2] == 0:
+        raise UfrError("render_points: K is not finite or K[2,2] is 0")
+    Ks = Ks / Ks[2, 2]
+    try:
+        w2cs = np.linalg.inv(c2ws)
+    except np.linalg.LinAlgError:
+        raise UfrError("render_points: a camera-to-world matrix is singular") from None
+    if not (np.isfinite(c2ws).all() and np.isfinite(w2cs).all()):
+        raise UfrError("render_points: a camera-to-world matrix is singular or not finite")
+    dev = torch.device(device)
+    tp = torch.from_numpy(np.ascontiguousarray(points)).to(dev)
+    tc = None if colors is None else torch.from_numpy(np.ascontiguousarray(colors)).to(dev)
+    chunk = _frames_per_chunk(n, H, W, s, 4 * return_depth + 4 * return_point_ids, dev)
+    out = {k: [] for k in ["image"] + extras}
+    for i in range(0, n, chunk):
+        r = ops.splat_frames(tp, Ks, w2cs[i:i + chunk], s * H, s * W, colors=tc, radius=min(4, s * radius + (s - 1)),
+                             base_color=base_color, background=background, edl_strength=edl_strength, edl_radius=edl_radius,
+                             return_depth=return_depth, return_point_ids=return_point_ids)
+        if s > 1:
+            r["image"] = ops.raster_downsample(r["image"], s)
+        for k in out:
+            out[k].append(r[k].cpu().numpy())
+    res = [np.concatenate(out[k]) for k in ["image"] + extras]
+    return res[0] if not extras else tuple(res)
+
+
 # ------------------------------------------------------------------ the command line
 def make_parser():
     """The reference's constants (render_trajectory_dtu.py:93-107, 134) as defaults."""
@@ -266,19 +352,18 @@ def make_parser():
     parser.add_argument("--format", choices=["jpg", "png"], default="jpg")
     parser.add_argument("--quality", type=int, default=90, help="JPEG quality")
     parser.add_argument("--dump_poses", type=str, default=None, help="directory for Open3D pinhole-camera JSON (tmp<i>.json)")
+    parser.add_argument("--pcd_dir", type=str, default=None, help="render the point clouds <pcd_dir>/scan<N>.ply instead of meshes")
+    parser.add_argument("--ply", type=str, nargs="+", default=None,
+                        help="render these point-cloud files instead of scan<N>.ply, each to <out_dir>/<file stem>/")
+    parser.add_argument("--point_radius", type=int, default=1, choices=[0, 1, 2, 3, 4], help="pixels round a point's projection")
+    parser.add_argument("--edl", type=float, default=DEFAULT_EDL,
+                        help="eye-dome lighting strength of a point cloud (0: none); the default is derived -- a 1 %% depth step "
+                             "at one neighbour halves the brightness -- not tuned on a real scan")
     return parser
 
 
-def render_scan(mesh_path, root_dir, out_dir, views=VIEWS, num_views=NUM_VIEWS, img_wh=IMG_WH, original_img_wh=ORIGINAL_IMG_WH,
-                offset_dist=OFFSET_DIST, supersample=1, flat=False, color="uniform", ambient=0.25, fmt="jpg", quality=90,
-                dump_poses=None):
-    """One scan: the frames ``<out_dir>/render_<i>.<fmt>`` of ``mesh_path`` along the path through ``views``.  Returns the
-    (num_views,4,4) camera-to-world matrices."""
-    from PIL import Image
-
-    verts, faces, colors = read_ply(mesh_path, with_colors=True)
-    if faces is None:
-        faces = np.zeros((0, 3), np.int32)
+def _scan_cameras(root_dir, views, num_views, img_wh, original_img_wh, offset_dist, dump_poses):
+    """(K float64 3x3, c2ws (num_views,4,4), H, W) of a path through ``views``; writes the pose files when asked"""
     if len(views) < 2:
         raise ValueError(f"render_scan: views {views}: at least two key views are needed")
     K0, w2cs = key_poses(root_dir, views, offset_dist)
@@ -290,8 +375,12 @@ def render_scan(mesh_path, root_dir, out_dir, views=VIEWS, num_views=NUM_VIEWS, 
         for i, c2w in enumerate(c2ws):
             with open(os.path.join(dump_poses, "tmp%d.json" % i), "w") as f:
                 json.dump(pinhole_json(K, c2w, H, W), f, indent=4)
-    images = render_mesh(verts, faces, K, c2ws, H, W, colors=colors if color == "vertex" else None, smooth=not flat,
-                         ambient=ambient, supersample=supersample)
+    return K, c2ws, H, W
+
+
+def _write_frames(images, out_dir, fmt, quality):
+    from PIL import Image
+
     os.makedirs(out_dir, exist_ok=True)
     for i, img in enumerate(images):
         path = os.path.join(out_dir, "render_%d.%s" % (i, fmt))
@@ -299,11 +388,53 @@ def render_scan(mesh_path, root_dir, out_dir, views=VIEWS, num_views=NUM_VIEWS, 
             Image.fromarray(img).save(path, quality=quality)
         else:
             Image.fromarray(img).save(path)
+
+
+def render_scan(mesh_path, root_dir, out_dir, views=VIEWS, num_views=NUM_VIEWS, img_wh=IMG_WH, original_img_wh=ORIGINAL_IMG_WH,
+                offset_dist=OFFSET_DIST, supersample=1, flat=False, color="uniform", ambient=0.25, fmt="jpg", quality=90,
+                dump_poses=None):
+    """One scan: the frames ``<out_dir>/render_<i>.<fmt>`` of ``mesh_path`` along the path through ``views``.  Returns the
+    (num_views,4,4) camera-to-world matrices."""
+    verts, faces, colors = read_ply(mesh_path, with_colors=True)
+    if faces is None:
+        faces = np.zeros((0, 3), np.int32)
+    K, c2ws, H, W = _scan_cameras(root_dir, views, num_views, img_wh, original_img_wh, offset_dist, dump_poses)
+    images = render_mesh(verts, faces, K, c2ws, H, W, colors=colors if color == "vertex" else None, smooth=not flat,
+                         ambient=ambient, supersample=supersample)
+    _write_frames(images, out_dir, fmt, quality)
+    return c2ws
+
+
+def render_cloud(ply_path, root_dir, out_dir, views=VIEWS, num_views=NUM_VIEWS, img_wh=IMG_WH, original_img_wh=ORIGINAL_IMG_WH,
+                 offset_dist=OFFSET_DIST, supersample=1, color="uniform", point_radius=1, edl=DEFAULT_EDL, fmt="jpg", quality=90,
+                 dump_poses=None):
+    """``render_scan`` for a point cloud: the vertices of ``ply_path`` (its faces, if any, are ignored) splatted along the same
+    path into the same files.  ``color="uniform"`` paints the cloud white and leaves the shading to eye-dome lighting alone
+    (a cloud from ``tsdf`` without ``--integrate_color`` carries black vertices); ``"vertex"`` uses the PLY's colours."""
+    points, _, colors = read_ply(ply_path, with_colors=True)
+    K, c2ws, H, W = _scan_cameras(root_dir, views, num_views, img_wh, original_img_wh, offset_dist, dump_poses)
+    images = render_points(points, K, c2ws, H, W, colors=colors if color == "vertex" else None, radius=point_radius,
+                           edl_strength=edl, supersample=supersample)
+    _write_frames(images, out_dir, fmt, quality)
     return c2ws
 
 
 def main(argv=None):
     args = make_parser().parse_args(argv)
+    if args.pcd_dir is not None or args.ply:
+        if args.ply:
+            jobs = [(os.path.splitext(os.path.basename(p))[0], p) for p in args.ply]
+        else:
+            jobs = [("scan%d" % scan, os.path.join(args.pcd_dir, "scan%d.ply" % scan)) for scan in args.scans]
+        for name, path in jobs:
+            if not os.path.exists(path):
+                print("%s: no point cloud at %s" % (name, path))
+                continue
+            print("rendering %s (points)" % name)
+            render_cloud(path, args.root_dir, os.path.join(args.out_dir, name), args.views, args.num_views, args.img_wh,
+                         args.original_img_wh, args.offset_dist, args.supersample, args.color, args.point_radius, args.edl,
+                         args.format, args.quality, args.dump_poses)
+        return
     for scan in args.scans:
         mesh = os.path.join(args.mesh_dir, "scan%d.ply" % scan)
         if not os.path.exists(mesh):
