@@ -918,6 +918,51 @@ int ufr_view_pair_scores(const int64_t* offsets, const int32_t* obs, const int32
                          int64_t M, const double* centres, int32_t N, double theta0, double sigma1, double sigma2, double* score,
                          void* workspace, size_t workspace_bytes, ufr_stream stream);
 
+/* ---- undistortion of a custom scene's pictures (ABI 507, additive) -------------------------------------------
+ * What the reference leaves to COLMAP's own undistorter, which is expected to run before its colmap2mvsnet.py: the pictures
+ * of a camera with lens distortion, resampled to a pinhole camera.  uforecon_amd/colmap2mvsnet.py (--undistort) is the caller,
+ * uforecon_amd/undistort.py has the host form.  The rule below restates COLMAP's public camera models; it was compared with
+ * neither COLMAP nor OpenCV: the rule written here is the rule.
+ *
+ * ufr_image_undistort_u8: src = n interleaved images (n,Hs,Ws,C) uint8, device, C = 1 .. 4, all taken by ONE camera -> dst
+ *   (n,H,W,C) uint8, device; valid (H,W) uint8, device, nullable: 255 where the output pixel has a source, else 0 (one map for
+ *   the n images: it is computed once per output pixel).  model: COLMAP's camera model id; params: HOST double[], that model's
+ *   COLMAP parameter list; k_out: HOST double[4] = fx' fy' cx' cy' of the output pinhole camera; both are read before the call
+ *   returns.  Per output pixel (x, y), everything in fp64, each product, sum and quotient rounded on its own (no fused
+ *   multiply-add), in the order the parentheses give; fx fy cx cy are the source camera's (fy = fx for a one-focal model):
+ *     xn = ((x + 0.5) - cx') / fx'                     yn = ((y + 0.5) - cy') / fy'
+ *     (xd, yd) = distort(xn, yn)                       (below)
+ *     u = ((fx * xd) + cx) - 0.5                       v = ((fy * yd) + cy) - 0.5        (COLMAP: pixel centres at +0.5)
+ *     ok = 0 <= u <= Ws - 1 and 0 <= v <= Hs - 1       (a NaN is not ok)
+ *     x0 = min(floor(u), Ws - 1), x1 = min(x0 + 1, Ws - 1), a = u - x0;   y0, y1, b likewise from v and Hs
+ *     top = ((1 - a) * S[y0][x0]) + (a * S[y0][x1]),  bot = ((1 - a) * S[y1][x0]) + (a * S[y1][x1])
+ *     val = ((1 - b) * top) + (b * bot),  dst = (uint8) rint(val), round half to even     (per image and channel)
+ *   A pixel that is not ok reads nothing and gets 0 in every channel of every image and 0 in valid.
+ *   distort, with xx = x * x, yy = y * y, r2 = xx + yy, r4 = r2 * r2, r6 = r4 * r2, xy = x * y and COLMAP's parameter order;
+ *   a coefficient that a model does not have is 0 (adding a zero term changes no finite result, so each line is every
+ *   one of its models' own formula):
+ *     SIMPLE_PINHOLE 0 (f cx cy), PINHOLE 1 (fx fy cx cy), SIMPLE_RADIAL 2 (f cx cy k1), RADIAL 3 (f cx cy k1 k2),
+ *     OPENCV 4 (fx fy cx cy k1 k2 p1 p2):
+ *       rad = (k1 * r2) + (k2 * r4)
+ *       tx = ((2 * p1) * xy) + (p2 * (r2 + (2 * xx)))      ty = ((2 * p2) * xy) + (p1 * (r2 + (2 * yy)))
+ *       xd = (x + (x * rad)) + tx                          yd = (y + (y * rad)) + ty
+ *       (the two pinhole models come out as the identity)
+ *     FULL_OPENCV 6 (fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6): tx, ty as above,
+ *       rad = (((1 + (k1 * r2)) + (k2 * r4)) + (k3 * r6)) / (((1 + (k4 * r2)) + (k5 * r4)) + (k6 * r6))
+ *       xd = (x * rad) + tx                                yd = (y * rad) + ty
+ *     OPENCV_FISHEYE 5 (fx fy cx cy k1 k2 k3 k4), SIMPLE_RADIAL_FISHEYE 8 (f cx cy k1), RADIAL_FISHEYE 9 (f cx cy k1 k2):
+ *       r = sqrt(r2), t = atan(r), t2 = t * t, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4
+ *       s = (t * ((((1 + (k1 * t2)) + (k2 * t4)) + (k3 * t6)) + (k4 * t8))) / r,  and s = 1 where r < 1e-8
+ *       xd = x * s                                         yd = y * s
+ *       (sqrt is correctly rounded; atan is the math library's and may differ between libraries in the last place)
+ *     FOV 7 and THIN_PRISM_FISHEYE 10 are refused.
+ *   One thread per output pixel; no workspace; enqueues one kernel and synchronises nowhere.
+ *   Errors: a null src, dst, params or k_out; n, Hs, Ws, H or W < 1; C outside 1 .. 4; a model that is unknown or refused; a
+ *   parameter of the model or of k_out that is not finite; fx' or fy' <= 0; Hs * Ws or H * W >= 2^31 -- each UFR_ERR_ARG with
+ *   the reason in the thread's last-error text.                                                                          */
+int ufr_image_undistort_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, int32_t C, int32_t model, const double* params,
+                           const double* k_out, int32_t H, int32_t W, uint8_t* dst, uint8_t* valid, ufr_stream stream);
+
 /* ---- the optimizer update and the ray draw of a training step (ABI 507, additive) ----------------------------
  * What UFORecon.training_step / configure_optimizers (code1/model.py:72-87, 537) run around the ray path, each as one call.
  * Neither synchronises; every argument error is UFR_ERR_ARG with the reason in the thread's last-error text.

@@ -181,6 +181,7 @@ SIGNATURES = {
     "ufr_view_pair_scores_workspace_bytes": (sz, [i32, i64]),
     "ufr_view_pair_scores": (C.c_int, [C.POINTER(i64), vp, C.POINTER(i32), i64, vp, i64, vp, i32, C.c_double, C.c_double, C.c_double,
                                        vp, vp, sz, vp]),
+    "ufr_image_undistort_u8": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, i32, vp, vp, vp]),
     "ufr_adam_table_capacity": (i32, []),
     "ufr_adam_step": (C.c_int, [C.POINTER(AdamTensor), i32, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     "ufr_select_rays_workspace_bytes": (sz, [i32, i32]),

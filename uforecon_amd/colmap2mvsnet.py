@@ -32,6 +32,26 @@ reference gets NaN when rounding carries it past 1); ``--test`` does what its he
 ignores it); an image without a valid observation is an error that names the image (the reference raises IndexError); with
 ``--convert_format`` the pictures AND the masks are re-encoded through PIL (the reference re-encodes the pictures through cv2
 and forgets the masks) -- those bytes are not comparable with cv2's.
+
+Lens distortion.  `intrinsic_of` keeps fx, fy, cx, cy of a camera and drops its distortion coefficients, as the
+reference does: it expects COLMAP's own undistorter to have run.  For a model straight out of COLMAP's mapper (its default camera
+is SIMPLE_RADIAL) that is wrong by the distortion, so the command names the model in one line on stderr, and
+
+    python -m uforecon_amd.colmap2mvsnet --dense_folder SCENE --undistort [--undistort_fit inside|keep]
+
+resamples the pictures to pinhole cameras itself (`undistort.undistort_images`; on the device, ufr_image_undistort_u8 of
+csrc/undistort.hip, in groups of at most 8 pictures that share a camera).  Per camera the output keeps the source size and
+cx, cy; fx' = z fx, fy' = z fy.  ``keep`` is z = 1 and leaves blank pixels where the output looks past the source picture;
+``inside`` (the default) is the smallest z in [1, 4] for which every border pixel of the output has a source: 1 if that holds
+already, else 40 bisections of that predicate on [1, 4], taking the upper end -- a longer focal length at the same size only
+ever crops, so the search evaluates the distortion and never needs its inverse; a camera for which z = 4 does not suffice ends
+the command with one line that names it.  ``cams/%08d_cam.txt`` carries K', and `depth_num`'s one-pixel-baseline formula uses
+K' too; ``pair.txt`` does not depend on K.  ``images/%08d.jpg`` and ``masks/%08d_mask.jpg`` are written through PIL as JPEG of
+quality 95 without chroma subsampling (`JPEG_OPTIONS`); the mask is the undistorted ``masks/<name>.png``, or 255 where there is
+none, and 0 wherever an output pixel has no source, so ``GeneralScan --use_mask`` ignores blank pixels.  SIMPLE_PINHOLE and
+PINHOLE cameras are copied as without the flag; FOV and THIN_PRISM_FISHEYE end the command with one line.  Without the flag every
+written file is what it was before the flag existed.  The rule restates COLMAP's public camera models and was compared with
+neither COLMAP nor OpenCV, and no real scene has been run through it.
 """
 from __future__ import annotations
 
@@ -53,6 +73,9 @@ CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3, True), 1: ("PINHOLE", 4, False), 2: ("
                  4: ("OPENCV", 8, False), 5: ("OPENCV_FISHEYE", 8, False), 6: ("FULL_OPENCV", 12, False), 7: ("FOV", 5, False),
                  8: ("SIMPLE_RADIAL_FISHEYE", 4, True), 9: ("RADIAL_FISHEYE", 5, True), 10: ("THIN_PRISM_FISHEYE", 12, False)}
 MODEL_IDS = {name: k for k, (name, _, _) in CAMERA_MODELS.items()}
+PINHOLE_MODELS = ("SIMPLE_PINHOLE", "PINHOLE")      # no distortion: --undistort copies their pictures
+UNDISTORT_FITS = ("inside", "keep")
+JPEG_OPTIONS = {"quality": 95, "subsampling": 0}    # of the files --undistort writes (4:4:4 chroma; PIL's default is 75, 4:2:0)
 TOP_VIEWS = 10       # colmap2mvsnet.py:408
 
 
@@ -250,11 +273,37 @@ def read_pair_text(text):
     return rows
 
 
-def convert(dense_folder, max_d=0, interval_scale=1, theta0=5, sigma1=1, sigma2=10, write=True, convert_format=False, device="cuda"):
+def camera_zooms(cameras, images, fit):
+    """{camera id: zoom} for ``--undistort``: 1 for a pinhole camera and for ``fit`` "keep", else `undistort.fit_zoom`."""
+    from . import undistort as U
+
+    zooms = {}
+    for cid in sorted({im.camera_id for im in images.values()}):
+        cam = cameras[cid]
+        if cam.model not in U.SUPPORTED_MODELS:
+            raise ColmapError(f"--undistort: camera {cid} has the model {cam.model}, which is not supported "
+                              f"(supported: {', '.join(U.SUPPORTED_MODELS)})")
+        try:
+            U.split_params(cam.model, cam.params)
+            keep = fit == "keep" or cam.model in PINHOLE_MODELS
+            zooms[cid] = 1.0 if keep else U.fit_zoom(cam.model, cam.params, intrinsic_of(cam), int(cam.height), int(cam.width))
+        except ValueError as e:
+            raise ColmapError(f"--undistort: camera {cid} ({cam.model}): {e}") from None
+    return zooms
+
+
+def convert(dense_folder, max_d=0, interval_scale=1, theta0=5, sigma1=1, sigma2=10, write=True, convert_format=False, device="cuda",
+            undistort=False, undistort_fit="inside"):
     """The conversion in memory; with ``write`` also on disk.  Returns a dict: ``intrinsics`` (N,3,3), ``extrinsics`` (N,4,4),
     ``depth_ranges`` (N,4) = (min, interval, number, max), ``score`` (N,N), ``view_sel`` (per image the up to 10 (image,
-    score) pairs, best first), ``names``, and the file texts ``cam_texts`` / ``pair_text``; image k of the output is COLMAP's
-    image k + 1."""
+    score) pairs, best first), ``names``, the file texts ``cam_texts`` / ``pair_text``, ``intrinsics_source`` (N,3,3, what
+    `intrinsic_of` reads from the model), ``zoom`` (N) and ``distorted_models`` (the names of the models in use that have lens
+    distortion); image k of the output is COLMAP's image k + 1.
+
+    With ``undistort`` the pictures are resampled to pinhole cameras (the module text): ``intrinsics``, the camera files and the
+    depth ranges then describe those cameras, K' = K with both focal lengths times ``zoom``.  With ``write=False`` the dict also
+    holds the arrays that would have been written: ``images`` (per image (H,W,3) uint8), ``masks`` and ``valid`` (per image
+    (H,W) uint8), each None for an image of a pinhole camera, whose files are copied."""
     cameras, images, points3d = read_model(os.path.join(dense_folder, "sparse", "0"))
     N = len(images)
     if N < 1 or sorted(images) != list(range(1, N + 1)):
@@ -264,7 +313,16 @@ def convert(dense_folder, max_d=0, interval_scale=1, theta0=5, sigma1=1, sigma2=
             raise ColmapError(f"image {im.id} ({im.name}) names camera {im.camera_id}, which cameras.bin does not hold")
     if not (sigma1 > 0 and sigma2 > 0):
         raise ColmapError(f"--sigma1 {sigma1} --sigma2 {sigma2}: both must be positive")
-    K = [intrinsic_of(cameras[images[i + 1].camera_id]) for i in range(N)]
+    if undistort_fit not in UNDISTORT_FITS:
+        raise ColmapError(f"--undistort_fit {undistort_fit}: must be one of {', '.join(UNDISTORT_FITS)}")
+    K_source = [intrinsic_of(cameras[images[i + 1].camera_id]) for i in range(N)]
+    K, zoom = K_source, np.ones(N)
+    if undistort:
+        from .undistort import zoomed
+
+        zooms = camera_zooms(cameras, images, undistort_fit)
+        zoom = np.array([zooms[images[i + 1].camera_id] for i in range(N)])
+        K = [zoomed(K_source[i], zoom[i]) for i in range(N)]
     E = [extrinsic_of(images[i + 1]) for i in range(N)]
     offsets, obs, points = observation_lists(images, points3d)
     ranges = []
@@ -287,10 +345,65 @@ def convert(dense_folder, max_d=0, interval_scale=1, theta0=5, sigma1=1, sigma2=
         view_sel.append([(int(k), score[i, k]) for k in order[:TOP_VIEWS]])
     out = {"intrinsics": np.stack(K), "extrinsics": np.stack(E), "depth_ranges": np.array(ranges, np.float64), "score": score,
            "view_sel": view_sel, "names": [images[i + 1].name for i in range(N)],
-           "cam_texts": [cam_text(E[i], K[i], ranges[i]) for i in range(N)], "pair_text": pair_text(view_sel)}
+           "cam_texts": [cam_text(E[i], K[i], ranges[i]) for i in range(N)], "pair_text": pair_text(view_sel),
+           "intrinsics_source": np.stack(K_source), "zoom": zoom,
+           "distorted_models": sorted({cameras[im.camera_id].model for im in images.values()} - set(PINHOLE_MODELS))}
+    if undistort and not write:
+        out["images"], out["masks"], out["valid"] = [None] * N, [None] * N, [None] * N
+        for idx, dst, masks, valid in undistorted_groups(dense_folder, cameras, images, zoom, device):
+            for j, i in enumerate(idx):
+                out["images"][i], out["masks"][i], out["valid"][i] = dst[j], masks[j], valid
     if write:
-        _write(dense_folder, out, convert_format)
+        resampled = {i for i in range(N) if undistort and cameras[images[i + 1].camera_id].model not in PINHOLE_MODELS}
+        if resampled and {"%08d.jpg" % i for i in range(N)} & set(out["names"]):
+            raise ColmapError("--undistort: a picture's name is one of the names the converter writes (%08d.jpg): it would overwrite "
+                              "a source it still has to read")
+        _write(dense_folder, out, convert_format, set(range(N)) - resampled)
+        if resampled:
+            _write_undistorted(dense_folder, undistorted_groups(dense_folder, cameras, images, zoom, device))
     return out
+
+
+def undistorted_groups(dense_folder, cameras, images, zoom, device):
+    """``--undistort``: yields (image indices, pictures (n,H,W,3) uint8, masks (n,H,W) uint8, valid (H,W) uint8) for groups of at
+    most 8 images that share a camera with lens distortion -- its pictures and, where there are any, their masks through
+    `undistort.undistort_images` (so through ufr_image_undistort_u8 on a GPU).  An image without a mask file gets 255; every
+    mask is 0 where ``valid`` is.  Images of pinhole cameras are in no group."""
+    from . import undistort as U
+    from .host_forms import imread_gray, imread_rgb
+
+    image_dir, mask_dir = os.path.join(dense_folder, "images"), os.path.join(dense_folder, "masks")
+    by_camera = {}
+    for i in range(len(images)):
+        by_camera.setdefault(images[i + 1].camera_id, []).append(i)
+    for cid, members in sorted(by_camera.items()):
+        cam = cameras[cid]
+        if cam.model in PINHOLE_MODELS:
+            continue
+        H, W = int(cam.height), int(cam.width)
+        for first in range(0, len(members), U.GROUP):
+            idx = members[first:first + U.GROUP]
+            pictures, masks = [], []
+            for i in idx:
+                name = images[i + 1].name
+                src = os.path.join(image_dir, name)
+                if not os.path.exists(src):
+                    raise ColmapError(f"image {i + 1}: {src} is missing")
+                pictures.append(imread_rgb(src))
+                mask = os.path.join(mask_dir, name + ".png")
+                masks.append(imread_gray(mask) if os.path.exists(mask) else None)
+                for what, a in ((src, pictures[-1]), (mask, masks[-1])):
+                    if a is not None and a.shape[:2] != (H, W):
+                        raise ColmapError(f"image {i + 1}: {what} is {a.shape[1]}x{a.shape[0]}, camera {cid} is {W}x{H}: its "
+                                          "parameters do not describe this file")
+            z = float(zoom[idx[0]])
+            dst, valid, _, _ = U.undistort_images(np.stack(pictures), cam, z, device)
+            if any(m is not None for m in masks):
+                stack = np.stack([np.full((H, W), 255, np.uint8) if m is None else m for m in masks])[..., None]
+                out_masks = U.undistort_images(stack, cam, z, device)[0][..., 0]
+            else:
+                out_masks = np.broadcast_to(valid, (len(idx), H, W)).copy()
+            yield idx, dst, out_masks, valid
 
 
 def _copy(src, dst, convert_format):
@@ -303,7 +416,19 @@ def _copy(src, dst, convert_format):
         shutil.copyfile(src, dst)
 
 
-def _write(dense_folder, out, convert_format):
+def _write_undistorted(dense_folder, groups):
+    from PIL import Image as PilImage
+
+    image_dir, mask_dir = os.path.join(dense_folder, "images"), os.path.join(dense_folder, "masks")
+    os.makedirs(mask_dir, exist_ok=True)
+    for idx, dst, masks, _ in groups:
+        for j, i in enumerate(idx):
+            PilImage.fromarray(dst[j], "RGB").save(os.path.join(image_dir, "%08d.jpg" % i), format="JPEG", **JPEG_OPTIONS)
+            PilImage.fromarray(masks[j], "L").save(os.path.join(mask_dir, "%08d_mask.jpg" % i), format="JPEG", **JPEG_OPTIONS)
+
+
+def _write(dense_folder, out, convert_format, copied=None):
+    """the text files, and the pictures and masks of the images ``copied`` (indices; None = all) under their new names"""
     cam_dir, image_dir, mask_dir = (os.path.join(dense_folder, d) for d in ("cams", "images", "masks"))
     os.makedirs(cam_dir, exist_ok=True)
     for i, text in enumerate(out["cam_texts"]):
@@ -313,6 +438,8 @@ def _write(dense_folder, out, convert_format):
         with open(path, "w") as f:
             f.write(out["pair_text"])
     for i, name in enumerate(out["names"]):
+        if copied is not None and i not in copied:
+            continue
         src = os.path.join(image_dir, name)
         if not os.path.exists(src):
             raise ColmapError(f"image {i + 1}: {src} is missing")
@@ -335,19 +462,32 @@ def make_parser():
     return parser
 
 
-def main(argv=None):
+def make_command_parser():
+    """`make_parser()`, the reference's flags, and ours"""
     parser = make_parser()
+    parser.add_argument("--undistort", action="store_true", default=False,
+                        help="Resample the pictures of cameras with lens distortion to pinhole cameras (COLMAP's undistorter has not run).")
+    parser.add_argument("--undistort_fit", type=str, default="inside",
+                        help="inside: zoom in until no blank pixel is left on the border (default); keep: keep the focal length.")
+    return parser
+
+
+def main(argv=None):
+    parser = make_command_parser()
     args = parser.parse_args(argv)
     if not args.dense_folder:
         parser.error("--dense_folder is required")
     try:
         out = convert(args.dense_folder, args.max_d, args.interval_scale, args.theta0, args.sigma1, args.sigma2, write=not args.test,
-                      convert_format=args.convert_format, device="cuda:0")
+                      convert_format=args.convert_format, device="cuda:0", undistort=args.undistort, undistort_fit=args.undistort_fit)
     except ColmapError as e:
         parser.error(str(e))
     except FileNotFoundError as e:
         parser.error(f"{e.filename} is missing under --dense_folder {args.dense_folder}")
     N = len(out["names"])
+    if not args.undistort and out["distorted_models"]:
+        print("note: the camera model %s has lens distortion, and the camera files written describe pinhole cameras: run COLMAP's "
+              "undistorter first, or pass --undistort" % ", ".join(out["distorted_models"]), file=sys.stderr)
     print("%d images, depth range of image 0: %f .. %f in %f steps; best views of image 0: %s%s" % (
         N, out["depth_ranges"][0][0], out["depth_ranges"][0][3], out["depth_ranges"][0][2],
         " ".join("%d" % k for k, _ in out["view_sel"][0]), "" if not args.test else " (--test: nothing written)"))

@@ -1,7 +1,7 @@
 // extern "C" surface of libufr.so (include/ufr.h), part 5 of 7: the encoder -- correlation volumes and view weights, the
 // 3-D convolutions of the frustum U-Nets, the 2-D and deformable convolutions of the feature backbone, the FMT layer, and
 // what a scan loader feeds them (image planes from 8-bit pictures, with or without a foreground mask; the per-pixel ray tables)
-// and what a COLMAP model's converter asks before any of it (the pair scores of the view selection).
+// and what a COLMAP model's converter asks before any of it (the pair scores of the view selection, the undistorted pictures).
 #include "api_common.h"
 
 using namespace ufr;
@@ -303,6 +303,28 @@ int ufr_image_resize_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, i
 int ufr_image_resize_mask_u8(const uint8_t* src, const uint8_t* mask, int32_t n, int32_t Hs, int32_t Ws, int32_t H, int32_t W,
                              const int32_t* clip4, float* dst, ufr_stream stream) {
   return image_resize("ufr_image_resize_mask_u8", "image_resize_mask_u8", src, mask, true, n, Hs, Ws, H, W, clip4, dst, stream);
+}
+
+int ufr_image_undistort_u8(const uint8_t* src, int32_t n, int32_t Hs, int32_t Ws, int32_t C, int32_t model, const double* params,
+                           const double* k_out, int32_t H, int32_t W, uint8_t* dst, uint8_t* valid, ufr_stream stream) {
+  const char* who = "ufr_image_undistort_u8";
+  // parameters per COLMAP model id; 0 = not supported (FOV 7, THIN_PRISM_FISHEYE 10)
+  static const int kParams[11] = {3, 4, 4, 5, 8, 8, 12, 0, 4, 5, 0};
+  UFR_REQUIRE(src && dst && params && k_out, "%s: null argument", who);
+  UFR_REQUIRE(n >= 1 && Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1, "%s: n %d, source %dx%d, output %dx%d (each must be >= 1)", who, n, Hs,
+              Ws, H, W);
+  UFR_REQUIRE(C >= 1 && C <= 4, "%s: C %d (1 .. 4 channels)", who, C);
+  UFR_REQUIRE(model >= 0 && model <= 10 && kParams[model] > 0,
+              "%s: camera model %d is not supported (COLMAP ids 0 .. 6, 8, 9; FOV 7 and THIN_PRISM_FISHEYE 10 are refused)", who, model);
+  for (int k = 0; k < kParams[model]; ++k)
+    UFR_REQUIRE(std::isfinite(params[k]), "%s: parameter %d of camera model %d is not finite (%g)", who, k, model, params[k]);
+  for (int k = 0; k < 4; ++k) UFR_REQUIRE(std::isfinite(k_out[k]), "%s: k_out[%d] is not finite (%g)", who, k, k_out[k]);
+  UFR_REQUIRE(k_out[0] > 0.0 && k_out[1] > 0.0, "%s: output focal lengths %g %g (each must be > 0)", who, k_out[0], k_out[1]);
+  UFR_REQUIRE((long long)Hs * Ws < (1ll << 31) && (long long)H * W < (1ll << 31), "%s: an image of %dx%d or %dx%d has 2^31 pixels or more",
+              who, Hs, Ws, H, W);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("image_undistort_u8", s, launch_image_undistort(src, n, Hs, Ws, C, model, params, k_out, H, W, dst, valid, s));
+  return UFR_OK;
 }
 
 // ------------------------------------------------------------------ view selection of a COLMAP model

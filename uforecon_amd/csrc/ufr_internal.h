@@ -211,6 +211,10 @@ hipError_t launch_image_resize_u8(const unsigned char* src, const unsigned char*
 hipError_t launch_view_pair_scores(const long long* offsets_host, const int* obs, const double* points, long long M,
                                    const double* centres, int N, double theta0, double sigma1, double sigma2, double* score,
                                    long long* offsets_dev, int* sorted, hipStream_t s);
+// undistort.hip: n pictures of one COLMAP camera resampled to a pinhole camera (see the file header)
+// (model: one of the nine ids the file header lists; params, k_out: host fp64, checked by the entry point)
+hipError_t launch_image_undistort(const unsigned char* src, int n, int Hs, int Ws, int C, int model, const double* params,
+                                  const double* k_out, int H, int W, unsigned char* dst, unsigned char* valid, hipStream_t s);
 hipError_t launch_pixel_rays(const float* m_inv, const float* origin, int H, int W, float* dir, hipStream_t s);
 hipError_t launch_depth_gt(const float* pfm, int Hs, int Ws, int bottom_up, int y0, int x0, int H, int W, float scale_factor,
                            const double* cam_ray_z, float* depth, hipStream_t s);

@@ -1428,6 +1428,37 @@ def view_pair_scores(offsets, obs, points, centres, theta0: float = 5.0, sigma1:
     return out
 
 
+def image_undistort_u8(src: torch.Tensor, model, params, k_out, H: int, W: int, want_valid: bool = True):
+    """ufr_image_undistort_u8: (n,Hs,Ws,C) CUDA uint8 pictures of ONE COLMAP camera (C = 1 .. 4) -> ``(dst, valid)``: dst
+    (n,H,W,C) uint8, the pictures as the pinhole camera ``k_out`` = (fx', fy', cx', cy') sees them, and valid (H,W) uint8, 255
+    where an output pixel has a source and 0 where it does not (None without ``want_valid``).  ``model`` is COLMAP's model
+    name or id, ``params`` that model's parameter list (host values).  The rule is stated in include/ufr.h;
+    uforecon_amd.undistort has the host form.  Does not synchronise."""
+    import numpy as np
+
+    from .colmap2mvsnet import CAMERA_MODELS, MODEL_IDS
+
+    p = _dev(src, "src", torch.uint8)
+    if src.dim() != 4:
+        raise UfrError(f"src: expected shape (n, Hs, Ws, C), got {tuple(src.shape)}")
+    model_id = MODEL_IDS.get(model, -1) if isinstance(model, str) else int(model)
+    par = np.ascontiguousarray(np.asarray(params, np.float64).reshape(-1))
+    if model_id in CAMERA_MODELS and par.size != CAMERA_MODELS[model_id][1]:
+        raise UfrError(f"image_undistort_u8: {par.size} parameters for camera model {CAMERA_MODELS[model_id][0]}, which has {CAMERA_MODELS[model_id][1]}")
+    ko = np.ascontiguousarray(np.asarray(k_out, np.float64).reshape(-1))
+    if ko.size != 4:
+        raise UfrError(f"image_undistort_u8: k_out {tuple(np.shape(k_out))} (fx', fy', cx', cy')")
+    n, Hs, Ws, Cn = (int(s) for s in src.shape)
+    H, W = int(H), int(W)
+    dst = torch.empty((n, max(H, 0), max(W, 0), Cn), dtype=torch.uint8, device=src.device)
+    valid = torch.empty((max(H, 0), max(W, 0)), dtype=torch.uint8, device=src.device) if want_valid else None
+    dp = C.POINTER(C.c_double)
+    _lib.check(_lib.load().ufr_image_undistort_u8(p, n, Hs, Ws, Cn, model_id, par.ctypes.data_as(dp), ko.ctypes.data_as(dp), H, W,
+                                                  dst.data_ptr(), valid.data_ptr() if want_valid else None, _stream()),
+               "ufr_image_undistort_u8")
+    return dst, valid
+
+
 def pixel_rays(m_inv, H: int, W: int, origin=None, device="cuda") -> torch.Tensor:
     """ufr_pixel_rays: (3,H*W) float32 unit vectors on ``device``; ``m_inv`` 4x4 and ``origin`` (3 values or None): host
     arrays, narrowed to float32.  Per pixel, in float64: p = (2x/(W-1) - 1, 2y/(H-1) - 1, 1, 1), v = (m_inv p)[:3] - origin,
