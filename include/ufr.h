@@ -850,6 +850,58 @@ int ufr_splat_frames(const double* points, int64_t N, const uint8_t* colors, con
                      double edl_strength, int32_t edl_radius, uint8_t* image, float* depth, int32_t* point_id, void* workspace,
                      size_t workspace_bytes, ufr_stream stream);
 
+/* ---- point-cloud filtering (ABI 507, additive) ----------------------------------------------------------------
+ * The cleanup between depth fusion and scoring that an MVS pipeline expects (voxel downsampling, statistical and radius
+ * outlier removal, normal estimation); the reference leaves it to Open3D.  uforecon_amd/pcd_filter.py is the caller,
+ * tests/pcd_ref.py the numpy statement of every rule below.  The rules follow the public descriptions of PCL's and Open3D's
+ * filters; neither library was compared against: the rule written here is the rule.  All positions and distances are fp64,
+ * every product and sum rounded on its own (no fused multiply-add); there is no floating-point atomic, so a rerun gives the
+ * same bits.  Every count nq, nr, n below is 1 .. 2^31 - 1.  None of the three takes a point set on the host.
+ *
+ * ufr_points_knn: for every query its k nearest reference points, 1 <= k <= UFR_KNN_MAX_K.  query (nq,3): device, any order
+ *   (a wave is fastest when its queries are neighbours).  ref (nr,3) with ref_keys (nr): sorted by ufr_points_cell_keys' key,
+ *   with the origin and cell the keys were made with, exactly as ufr_points_nn_dist takes them.  ref_index (nr) int32: the
+ *   caller's index of every sorted point (>= 0).  self_index (nq) int32, nullable: a caller's index that query i skips (a
+ *   point that looks for its neighbours in its own set).  A candidate's key is (d2, ref_index) with
+ *   d2 = (dx*dx + dy*dy) + dz*dz; it is admitted iff d2 <= max_dist*max_dist (max_dist > 0, +inf allowed).  The result is the
+ *   k smallest keys in lexicographic order: ties in distance go to the lower caller's index, whatever the sorted order.
+ *   idx (nq,k) int32: caller's indices; dist (nq,k) fp64 = sqrt(d2), ascending; empty slots get -1 and +inf.  A query with a
+ *   coordinate that is not finite gets only empty slots; a reference point with one is never admitted.  The octree walk
+ *   (depth-first, nearest octant first) drops a node only when its box is strictly farther than the k-th d2 so far, visits
+ *   every node at most once and has a bounded stack: it ends whatever the data.  No workspace.  Does not synchronise.
+ * ufr_points_normals: points (n,3); idx (n,k) int32, 1 <= k <= UFR_KNN_MAX_K: the neighbours of every point, the point itself
+ *   included, as ufr_points_knn writes them; an entry outside 0 .. n-1 is an empty slot.  Per point, over its m non-empty
+ *   slots in slot order: centroid c = the left-to-right sum / m; covariance = the six left-to-right sums of the products of
+ *   (p_j - c), each / m; its eigen-decomposition by eight sweeps of cyclic Jacobi ((0,1), (0,2), (1,2)) in fp64.
+ *   normal (n,3) = the unit eigenvector of the smallest eigenvalue l0; curvature (n) = l0 / (l0 + l1 + l2), 0 when the sum
+ *   is 0; valid (n) uint8 = 1.  With m < 3 (or a result that is not finite) valid = 0 and normal and curvature are 0.
+ *   Orientation: viewpoints (V,3) fp64, device, V >= 0 (nullable when V = 0).  V >= 1: with p the point and c_j the
+ *   viewpoints, the j with the largest |n . (c_j - p)| / |c_j - p| decides, ties to the lowest j: n is negated when
+ *   n . (c_j - p) < 0 (dot products summed left to right).  V = 0: n is negated when its component of largest magnitude is
+ *   negative, ties to the lowest axis.  No workspace.  Does not synchronise.
+ * ufr_points_voxel_mean: points (n,3) with keys (n): sorted by ufr_points_cell_keys' key at cell = the voxel size, by a STABLE
+ *   sort, so that every voxel's points stand in ascending caller's index; the caller puts the origin at min_bound - voxel / 2
+ *   and refuses an extent of more than 2^21 - 4 cells on an axis.  colors (n,3) uint8 and normals (n,3) fp64: nullable, in
+ *   the same order.  Per run of equal keys, in key order: out_points = the left-to-right sum / count; out_colors per channel
+ *   = (2 * sum + count) / (2 * count) in integers (the mean, halves up); out_normals = the left-to-right sum divided by its
+ *   length, 0 when that is 0; count int32 = the run's length.  Outputs have `capacity` rows (device); nothing beyond is
+ *   written, and out_colors / out_normals are needed exactly when their input is given.  *total_host = the number of runs,
+ *   which may exceed capacity.  Run heads are ranked with the ordered compaction's integer scans.  workspace >=
+ *   ufr_points_voxel_mean_workspace_bytes(n) (device).  SYNCHRONISES the stream once, to hand the total to the host.
+ * Every argument error (null pointer, a count outside its range, k outside 1 .. UFR_KNN_MAX_K, max_dist not > 0, a cell or
+ * origin that is not finite, V < 0, a negative capacity, a workspace that is too small) is UFR_ERR_ARG (UFR_ERR_WORKSPACE for
+ * the workspace) with the reason in the thread's last-error text; nothing is launched then.                             */
+#define UFR_KNN_MAX_K 32
+int ufr_points_knn(const double* query, int64_t nq, const double* ref, const int64_t* ref_keys, const int32_t* ref_index,
+                   int64_t nr, const double* origin, double cell, const int32_t* self_index, int32_t k, double max_dist,
+                   int32_t* idx, double* dist, ufr_stream stream);
+int ufr_points_normals(const double* points, int64_t n, const int32_t* idx, int32_t k, const double* viewpoints, int32_t V,
+                       double* normal, double* curvature, uint8_t* valid, ufr_stream stream);
+size_t ufr_points_voxel_mean_workspace_bytes(int64_t n);
+int ufr_points_voxel_mean(const double* points, const int64_t* keys, int64_t n, const uint8_t* colors, const double* normals,
+                          double* out_points, uint8_t* out_colors, double* out_normals, int32_t* count, int64_t capacity,
+                          void* workspace, size_t workspace_bytes, int64_t* total_host, ufr_stream stream);
+
 /* ---- a scan loader's per-pixel work (ABI 507, additive) -----------------------------------------------------
  * What DtuFitSparse (code1/dataset/dtu_test_sparse.py:247-298, 412-429) computes per pixel; uforecon_amd/dtu_scan.py does the
  * 4x4 camera arithmetic on the host and calls these two.  Neither synchronises.

@@ -154,6 +154,10 @@ SIGNATURES = {
     "ufr_points_thin": (C.c_int, [vp, vp, vp, i64, C.c_double, vp, vp, sz, C.POINTER(i32), vp]),
     "ufr_points_nn_dist_workspace_bytes": (sz, [i64]),
     "ufr_points_nn_dist": (C.c_int, [vp, i64, vp, vp, i64, C.POINTER(C.c_double), C.c_double, C.c_double, vp, vp, vp, sz, vp]),
+    "ufr_points_knn": (C.c_int, [vp, i64, vp, vp, vp, i64, C.POINTER(C.c_double), C.c_double, vp, i32, C.c_double, vp, vp, vp]),
+    "ufr_points_normals": (C.c_int, [vp, i64, vp, i32, vp, i32, vp, vp, vp, vp]),
+    "ufr_points_voxel_mean_workspace_bytes": (sz, [i64]),
+    "ufr_points_voxel_mean": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, sz, C.POINTER(i64), vp]),
     "ufr_depth_consistency": (C.c_int, [vp, i32, i32, C.POINTER(vp), C.POINTER(i32), vp, i32, C.c_double, C.c_double, i32,
                                         vp, vp, vp, vp, vp]),
     "ufr_depth_points_workspace_bytes": (sz, [i32, i32]),

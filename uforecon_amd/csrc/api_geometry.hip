@@ -1,5 +1,5 @@
 // extern "C" surface of libufr.so (include/ufr.h), part 6 of 7: geometry after the network -- TSDF fusion, marching cubes,
-// the similarity field, the DTU chamfer evaluation, depth-map fusion, mesh cleaning, mesh rendering and point-cloud rendering.  The count / emit pairs synchronise the
+// the similarity field, the DTU chamfer evaluation, point-cloud filtering, depth-map fusion, mesh cleaning, mesh rendering and point-cloud rendering.  The count / emit pairs synchronise the
 // stream to hand a count to the host; so do the rounds of the two fixpoints (point thinning, face components).
 #include "api_common.h"
 #include "mcubes_table.h"
@@ -80,6 +80,17 @@ NnWs carve_nn_dist(Carver& c, long long nq) {
   NnWs w;
   w.block_sum = c.take<double>(blocks);
   w.block_cnt = c.take<long long>(blocks);
+  return w;
+}
+
+// ---- point-cloud filtering, voxel means: [run heads per block int64 | block offsets int64 | total int64]
+struct VoxelWs { long long *block_tot, *block_off, *total; };
+VoxelWs carve_voxel_mean(Carver& c, long long n) {
+  const size_t blocks = (size_t)points_filter_blocks(n);
+  VoxelWs w;
+  w.block_tot = c.take<long long>(blocks);
+  w.block_off = c.take<long long>(blocks);
+  w.total = c.take<long long>(1);
   return w;
 }
 
@@ -347,6 +358,63 @@ int ufr_points_nn_dist(const double* query, int64_t nq, const double* ref, const
   hipStream_t s = static_cast<hipStream_t>(stream);
   UFR_TIMED("points_nn_dist", s, launch_nn_dist(query, nq, ref, reinterpret_cast<const long long*>(ref_keys), nr, origin, cell, max_dist,
       dist, w.block_sum, w.block_cnt, mean_out, s));
+  return UFR_OK;
+}
+
+// ------------------------------------------------------------------ point-cloud filtering
+int ufr_points_knn(const double* query, int64_t nq, const double* ref, const int64_t* ref_keys, const int32_t* ref_index,
+                   int64_t nr, const double* origin, double cell, const int32_t* self_index, int32_t k, double max_dist,
+                   int32_t* idx, double* dist, ufr_stream stream) {
+  const char* who = "ufr_points_knn";
+  UFR_REQUIRE(query && ref && ref_keys && ref_index && origin && idx && dist, "%s: null argument", who);
+  UFR_REQUIRE(nq >= 1 && nq <= kChMax && nr >= 1 && nr <= kChMax, "%s: nq %lld, nr %lld (each must be 1 .. 2^31 - 1)", who,
+              (long long)nq, (long long)nr);
+  UFR_REQUIRE(k >= 1 && k <= UFR_KNN_MAX_K, "%s: k %d (must be 1 .. %d)", who, k, UFR_KNN_MAX_K);
+  UFR_CHECK(cell_grid_check(who, cell, origin));
+  UFR_REQUIRE(max_dist > 0.0, "%s: max_dist %g (must be positive; +inf for no limit)", who, max_dist);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("points_knn", s, launch_points_knn(query, nq, ref, reinterpret_cast<const long long*>(ref_keys), ref_index, nr, origin,
+      cell, self_index, k, max_dist, idx, dist, s));
+  return UFR_OK;
+}
+
+int ufr_points_normals(const double* points, int64_t n, const int32_t* idx, int32_t k, const double* viewpoints, int32_t V,
+                       double* normal, double* curvature, uint8_t* valid, ufr_stream stream) {
+  const char* who = "ufr_points_normals";
+  UFR_REQUIRE(points && idx && normal && curvature && valid, "%s: null argument", who);
+  UFR_REQUIRE(n >= 1 && n <= kChMax, "%s: n %lld (must be 1 .. 2^31 - 1)", who, (long long)n);
+  UFR_REQUIRE(k >= 1 && k <= UFR_KNN_MAX_K, "%s: k %d (must be 1 .. %d)", who, k, UFR_KNN_MAX_K);
+  UFR_REQUIRE(V >= 0 && (V == 0 || viewpoints), "%s: V %d with %s viewpoints (V must be >= 0)", who, V, viewpoints ? "given" : "null");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("points_normals", s, launch_points_normals(points, n, idx, k, viewpoints, V, normal, curvature, valid, s));
+  return UFR_OK;
+}
+
+size_t ufr_points_voxel_mean_workspace_bytes(int64_t n) {
+  return (n >= 1 && n <= kChMax) ? carved_bytes(carve_voxel_mean, (long long)n) : 0;
+}
+
+int ufr_points_voxel_mean(const double* points, const int64_t* keys, int64_t n, const uint8_t* colors, const double* normals,
+                          double* out_points, uint8_t* out_colors, double* out_normals, int32_t* count, int64_t capacity,
+                          void* workspace, size_t workspace_bytes, int64_t* total_host, ufr_stream stream) {
+  const char* who = "ufr_points_voxel_mean";
+  UFR_REQUIRE(points && keys && workspace && total_host, "%s: null argument", who);
+  UFR_REQUIRE(n >= 1 && n <= kChMax, "%s: n %lld (must be 1 .. 2^31 - 1)", who, (long long)n);
+  UFR_REQUIRE(capacity >= 0, "%s: capacity %lld", who, (long long)capacity);
+  UFR_REQUIRE(capacity == 0 || (out_points && count && (!colors || out_colors) && (!normals || out_normals)),
+              "%s: null argument (an output with capacity %lld)", who, (long long)capacity);
+  Carver c(workspace);
+  const VoxelWs w = carve_voxel_mean(c, n);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long* k64 = reinterpret_cast<const long long*>(keys);
+  UFR_TIMED("points_voxel_count", s, launch_voxel_count(k64, n, w.block_tot, w.block_off, w.total, s));
+  if (capacity > 0)
+    UFR_TIMED("points_voxel_mean", s, launch_voxel_mean(points, k64, n, colors, normals, w.block_off, out_points, out_colors, out_normals,
+        count, capacity, s));
+  long long tot = 0;
+  UFR_CHECK(read_counts(&tot, w.total, 1, s));
+  *total_host = (int64_t)tot;
   return UFR_OK;
 }
 

@@ -19,6 +19,7 @@
 //          distances below max_dist, then one summing block: no float atomics, the mean is the same run after run.
 // Every output store is guarded by the caller's capacity; point and triangle indices are 64-bit.
 #include "compact.h"
+#include "points_octree.h"
 #include "ufr_internal.h"
 
 #pragma clang fp contract(off)
@@ -27,33 +28,6 @@ namespace ufr {
 namespace {
 
 constexpr int kChThreads = 256;
-constexpr int kKeyBits = 21;                       // per axis
-constexpr long long kMaxCell = (1ll << kKeyBits) - 1;
-
-// ------------------------------------------------------------------ Morton keys
-__host__ __device__ inline unsigned long long spread3(unsigned long long x) {
-  x &= 0x1fffffull;
-  x = (x | x << 32) & 0x1f00000000ffffull;
-  x = (x | x << 16) & 0x1f0000ff0000ffull;
-  x = (x | x << 8) & 0x100f00f00f00f00full;
-  x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-  x = (x | x << 2) & 0x1249249249249249ull;
-  return x;
-}
-
-__host__ __device__ inline unsigned long long compact3(unsigned long long x) {
-  x &= 0x1249249249249249ull;
-  x = (x | x >> 2) & 0x10c30c30c30c30c3ull;
-  x = (x | x >> 4) & 0x100f00f00f00f00full;
-  x = (x | x >> 8) & 0x1f0000ff0000ffull;
-  x = (x | x >> 16) & 0x1f00000000ffffull;
-  x = (x | x >> 32) & 0x1fffffull;
-  return x;
-}
-
-__device__ inline long long morton(long long cx, long long cy, long long cz) {
-  return (long long)(spread3((unsigned long long)cx) << 2 | spread3((unsigned long long)cy) << 1 | spread3((unsigned long long)cz));
-}
 
 // cell index along one axis, clamped to the key range (clamping never separates neighbours); NaN -> 0
 __device__ inline long long cell_of(double p, double o, double cell) {
@@ -67,15 +41,6 @@ __global__ void __launch_bounds__(kChThreads) points_cell_keys_kernel(const doub
   const long long i = (long long)blockIdx.x * kChThreads + threadIdx.x;
   if (i >= n) return;
   keys[i] = morton(cell_of(pts[3 * i], ox, cell), cell_of(pts[3 * i + 1], oy, cell), cell_of(pts[3 * i + 2], oz, cell));
-}
-
-// first index in [lo, hi) whose key is >= k
-__device__ inline long long lower_bound(const long long* __restrict__ keys, long long lo, long long hi, long long k) {
-  while (lo < hi) {
-    const long long mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 // ------------------------------------------------------------------ mesh sampling
@@ -207,9 +172,6 @@ __global__ void __launch_bounds__(kChThreads) thin_round_kernel(const double* __
 
 // ------------------------------------------------------------------ nearest neighbour
 constexpr int kNnLeaf = 8;                          // a node with at most this many points is tested point by point
-constexpr int kNnStack = 7 * kKeyBits + 8;
-
-struct NnGrid { double o[3], cell; };
 
 __global__ void __launch_bounds__(kChThreads) nn_dist_kernel(const double* __restrict__ query, long long nq,
                                                               const double* __restrict__ ref, const long long* __restrict__ keys,

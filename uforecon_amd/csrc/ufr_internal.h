@@ -162,6 +162,18 @@ hipError_t launch_thin_round(const double* pts, const long long* keys, const int
 hipError_t launch_nn_dist(const double* query, long long nq, const double* ref, const long long* keys, long long nr,
                           const double* origin, double cell, double max_dist, double* dist, double* block_sum,
                           long long* block_cnt, double* mean_out, hipStream_t s);
+// points_filter.hip: point-cloud filtering in fp64 (k nearest neighbours, normals, voxel means; see the file header)
+long long points_filter_blocks(long long n);   // blocks of the voxel kernels: sizes the per-block workspace arrays
+hipError_t launch_points_knn(const double* query, long long nq, const double* ref, const long long* keys, const int* ref_index,
+                             long long nr, const double* origin, double cell, const int* self_index, int k, double max_dist,
+                             int* idx, double* dist, hipStream_t s);
+hipError_t launch_points_normals(const double* pts, long long n, const int* idx, int k, const double* views, int V, double* normal,
+                                 double* curvature, unsigned char* valid, hipStream_t s);
+hipError_t launch_voxel_count(const long long* keys, long long n, long long* block_tot, long long* block_off, long long* total,
+                              hipStream_t s);
+hipError_t launch_voxel_mean(const double* pts, const long long* keys, long long n, const unsigned char* colors,
+                             const double* normals, const long long* block_off, double* out_pts, unsigned char* out_colors,
+                             double* out_normals, int* out_count, long long capacity, hipStream_t s);
 // depth_fusion.hip: geometric-consistency filtering of depth maps and the ordered compaction of the valid pixels (see the file header)
 long long depth_points_blocks(long long n);   // blocks of the compaction kernels: sizes the per-block workspace arrays
 hipError_t launch_depth_consistency(const float* ref, int H, int W, const float* const* src_depth, const int* src_hw,

@@ -985,6 +985,122 @@ def nn_distance(query: torch.Tensor, ref: torch.Tensor, max_dist: float, return_
     return (dist, sums) if return_sums else dist
 
 
+# ---- point-cloud filtering (csrc/points_filter.hip; uforecon_amd/pcd_filter.py strings these together)
+KNN_MAX_K = 32     # UFR_KNN_MAX_K of include/ufr.h
+
+
+def knn_points(query: torch.Tensor, ref: torch.Tensor, k: int, max_dist: float = float("inf"), exclude_self: bool = False):
+    """The ``k`` nearest ``ref`` points of every ``query`` point ((N,3) CUDA float64 both): ``idx`` (nq,k) int32, indices into
+    ``ref``, and ``dist`` (nq,k) float64, ascending by (distance, index), in the order of ``query``; a slot with no point within
+    ``max_dist`` (inclusive) holds -1 and inf (include/ufr.h, ufr_points_knn).  ``exclude_self``: ``query`` is ``ref`` and
+    point i is left out of its own neighbours."""
+    _points64(query, "query")
+    _points64(ref, "ref")
+    nq, nr = int(query.shape[0]), int(ref.shape[0])
+    k, max_dist = int(k), float(max_dist)
+    if not 1 <= k <= KNN_MAX_K:
+        raise UfrError(f"knn_points: k {k} (must be 1 .. {KNN_MAX_K})")
+    if not max_dist > 0.0:
+        raise UfrError(f"knn_points: max_dist {max_dist}")
+    if exclude_self and query is not ref:
+        raise UfrError("knn_points: exclude_self needs query to be ref (the same tensor)")
+    if nr == 0:
+        raise UfrError("knn_points: empty reference set")
+    idx = torch.empty((nq, k), dtype=torch.int32, device=query.device)
+    dist = torch.empty((nq, k), dtype=torch.float64, device=query.device)
+    if nq == 0:
+        return idx, dist
+    mn, mx = _finite_bounds(ref, "ref")
+    extent = float((mx - mn).max())
+    cell = extent / float(2 ** 20) if extent > 0.0 else 1.0      # the octree is adaptive: the cell only sets its finest level
+    origin = (mn - cell).tolist()
+    rkeys, rperm = torch.sort(cell_keys(ref, origin, cell))
+    rpts = ref[rperm].contiguous()
+    rindex = rperm.to(torch.int32)
+    qperm = rperm if query is ref else torch.sort(cell_keys(query, origin, cell)).indices    # neighbouring queries share a wave
+    qpts = rpts if query is ref else query[qperm].contiguous()
+    self_index = rindex if exclude_self else None
+    i_s = torch.empty_like(idx)
+    d_s = torch.empty_like(dist)
+    o = (C.c_double * 3)(*origin)
+    _lib.check(_lib.load().ufr_points_knn(qpts.data_ptr(), nq, rpts.data_ptr(), rkeys.data_ptr(), rindex.data_ptr(), nr, o, cell,
+                                          None if self_index is None else self_index.data_ptr(), k, max_dist, i_s.data_ptr(),
+                                          d_s.data_ptr(), _stream()), "ufr_points_knn")
+    idx[qperm] = i_s
+    dist[qperm] = d_s
+    return idx, dist
+
+
+def point_normals(points: torch.Tensor, idx: torch.Tensor, viewpoints: Optional[torch.Tensor] = None):
+    """``normal`` (N,3) float64, ``curvature`` (N,) float64 and ``valid`` (N,) uint8 of every point from its neighbour rows
+    ``idx`` ((N,k) CUDA int32 as ``knn_points`` returns them, the point itself included; -1 = empty): the eigenvector of the
+    smallest eigenvalue of the neighbours' covariance, turned towards the ``viewpoints`` ((V,3) CUDA float64) or, without
+    them, so that its largest component is positive (include/ufr.h, ufr_points_normals)."""
+    p = _points64(points, "points")
+    pi = _dev(idx, "idx", torch.int32)
+    N = int(points.shape[0])
+    if idx.dim() != 2 or idx.shape[0] != N or not 1 <= idx.shape[1] <= KNN_MAX_K:
+        raise UfrError(f"idx: expected shape ({N}, 1 .. {KNN_MAX_K}), got {tuple(idx.shape)}")
+    V, pv = 0, None
+    if viewpoints is not None:
+        pv = _points64(viewpoints, "viewpoints")
+        V = int(viewpoints.shape[0])
+        if V and not bool(torch.isfinite(viewpoints).all()):
+            raise UfrError("viewpoints: contains NaN or infinite coordinates")
+    normal = torch.empty((N, 3), dtype=torch.float64, device=points.device)
+    curvature = torch.empty(N, dtype=torch.float64, device=points.device)
+    valid = torch.empty(N, dtype=torch.uint8, device=points.device)
+    if N:
+        _lib.check(_lib.load().ufr_points_normals(p, N, pi, int(idx.shape[1]), pv if V else None, V, normal.data_ptr(),
+                                                  curvature.data_ptr(), valid.data_ptr(), _stream()), "ufr_points_normals")
+    return normal, curvature, valid
+
+
+def voxel_downsample(points: torch.Tensor, voxel: float, colors: Optional[torch.Tensor] = None,
+                     normals: Optional[torch.Tensor] = None):
+    """One point per occupied voxel of the grid with origin ``min_bound - voxel / 2``: the mean position, the rounded mean
+    colour ((N,3) CUDA uint8, optional) and the renormalised sum of the normals ((N,3) CUDA float64, optional) of its points,
+    summed in ascending index order, voxels in Morton-key order (include/ufr.h, ufr_points_voxel_mean).  Returns ``(points,
+    colors or None, normals or None, count)``, count int32.  One host synchronisation (the number of voxels)."""
+    _points64(points, "points")
+    N = int(points.shape[0])
+    voxel = float(voxel)
+    if not (voxel > 0.0 and voxel < float("inf")):
+        raise UfrError(f"voxel_downsample: voxel {voxel}")
+    for t, name, dtype in ((colors, "colors", torch.uint8), (normals, "normals", torch.float64)):
+        if t is not None:
+            _dev(t, name, dtype)
+            if tuple(t.shape) != (N, 3):
+                raise UfrError(f"{name}: expected shape ({N}, 3), got {tuple(t.shape)}")
+    if N == 0:
+        return points.clone(), colors, normals, torch.zeros(0, dtype=torch.int32, device=points.device)
+    mn, mx = _finite_bounds(points, "points")
+    origin = mn - voxel / 2
+    cells = float((torch.floor((mx - origin) / voxel) + 1).max())
+    if not cells <= float(2 ** 21 - 4):
+        raise UfrError(f"voxel_downsample: voxel {voxel} needs {cells:.0f} cells on an axis (at most 2^21 - 4)")
+    keys, perm = torch.sort(cell_keys(points, origin.tolist(), voxel), stable=True)
+    pts = points[perm].contiguous()
+    col = None if colors is None else colors[perm].contiguous()
+    nrm = None if normals is None else normals[perm].contiguous()
+    lib = _lib.load()
+    nbytes = lib.ufr_points_voxel_mean_workspace_bytes(N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+    out_p = torch.empty((N, 3), dtype=torch.float64, device=points.device)
+    out_c = None if col is None else torch.empty((N, 3), dtype=torch.uint8, device=points.device)
+    out_n = None if nrm is None else torch.empty((N, 3), dtype=torch.float64, device=points.device)
+    count = torch.empty(N, dtype=torch.int32, device=points.device)
+    total = C.c_int64(0)
+    _lib.check(lib.ufr_points_voxel_mean(pts.data_ptr(), keys.data_ptr(), N, None if col is None else col.data_ptr(),
+                                         None if nrm is None else nrm.data_ptr(), out_p.data_ptr(),
+                                         None if out_c is None else out_c.data_ptr(), None if out_n is None else out_n.data_ptr(),
+                                         count.data_ptr(), N, ws.data_ptr(), nbytes, C.byref(total), _stream()),
+               "ufr_points_voxel_mean")
+    M = int(total.value)
+    return (out_p[:M].contiguous(), None if out_c is None else out_c[:M].contiguous(),
+            None if out_n is None else out_n[:M].contiguous(), count[:M].contiguous())
+
+
 # ---- depth-map fusion (csrc/depth_fusion.hip; uforecon_amd/depth_fusion.py strings these together)
 DEPTH_MAX_SOURCES = 64     # UFR_DEPTH_MAX_SOURCES of include/ufr.h
 DEPTH_PAIR_DOUBLES = 68    # UFR_DEPTH_PAIR_DOUBLES
