@@ -1124,6 +1124,66 @@ size_t ufr_fmt_layer_workspace_bytes(int32_t N, int32_t S);   /* S: source token
 int ufr_fmt_layer(const ufr_fmt_layer_weights* w, const float* x, const float* src, int32_t N, int32_t T, int32_t S,
                   float* out, void* workspace, ufr_stream stream);
 
+/* ---- Poisson surface reconstruction (ABI 507, additive) -------------------------------------------------------
+ * From an oriented point cloud (what uforecon_amd/pcd_filter.py writes with --normals) to an indicator field on a uniform
+ * grid, whose level set ufr_marching_cubes_* turns into a mesh; the reference leaves this to Open3D.  uforecon_amd/
+ * poisson_mesh.py is the caller, tests/poisson_ref.py the numpy / scipy statement of every rule below.  The rules are a
+ * uniform-grid form of Kazhdan's Poisson reconstruction; neither Open3D nor PoissonRecon was compared against: the rule
+ * written here is the rule.  There is no adaptive octree, no screening term and no multigrid preconditioner.  Everything is
+ * fp64, every product and sum rounded on its own (no fused multiply-add); there is no floating-point atomic and every grid
+ * is a function of the sizes alone, so a rerun gives the same bits.  A volume is (X,Y,Z) = dims[0..2] fp64 on the device, z
+ * fastest: node (i,j,k) at [(i*Y + j)*Z + k], at the position origin + h*(i,j,k).  Every dim is >= 2 and X*Y*Z < 2^31.
+ *
+ * ufr_poisson_grid (host only, no device touched): bound_min / bound_max: the extent of the samples, HOST fp64[3].
+ *   h = max over the axes of (max - min) / resolution; origin[a] = min[a] - pad*h; dims[a] = ceil((max[a] - min[a]) / h) + 1
+ *   + 2*pad.  Refused: resolution < 4; pad < 2 (the splat and the central differences must stay inside the grid); a bound
+ *   that is not finite; max < min; a degenerate extent (h = 0, or h^2 outside the fp64 range); 2^31 nodes or more.
+ * ufr_poisson_splat_keys: points (n,3), 1 <= n < 2^28.  Per point and axis u = (p - origin) / h clamped to [0, dim - 1], the
+ *   cell c = min(floor(u), dim - 2), the offset t = u - c.  keys (8n) int64: keys[8p + 4a + 2b + g] = the linear index of the
+ *   node c + (a,b,g).  A point with a coordinate that is not finite gets eight keys of -1.
+ * ufr_poisson_splat: keys (8n) sorted ascending by a STABLE sort and rows (8n) int64 = the sort's permutation (rows[s] = the
+ *   unsorted position 8p + corner of sorted row s), so that the rows of a node stand in ascending sample index.  The weight
+ *   of corner (a,b,g) is (wx*wy)*wz with wx = a ? t[0] : 1 - t[0] and so on.  Per node, summed left to right along its run:
+ *   V[c][node] = sum w*normal[c] (V is PLANAR: (3,X,Y,Z)) and W[node] = sum w; a node without a row gets 0.  Rows with a key
+ *   outside 0 .. XYZ-1 are skipped.  normals (n,3): the caller has dropped samples whose normal is not finite or is 0.
+ * ufr_poisson_divergence: b = ((dx + dy) + dz) / (2h), dx = Vx[i+1] - Vx[i-1] and so on, V = 0 outside the grid.
+ * ufr_poisson_laplacian: one application of A: q = (6*p - (((p[i-1] + p[i+1]) + (p[j-1] + p[j+1])) + (p[k-1] + p[k+1]))) /
+ *   (h*h), p = 0 outside the grid: the negated 7-point Laplacian with Dirichlet walls one node outside, symmetric positive
+ *   definite.  q must not alias p.
+ * ufr_poisson_solve: x = the solution of A x = -b by plain conjugate gradients from x = 0 (r = p = -b; per iteration q = A p,
+ *   alpha = r.r / p.q, x += alpha p, r -= alpha q, beta = r'.r' / r.r, p = r + beta p; a quotient whose denominator is 0 is
+ *   0).  A dot product is per-block partial sums (at most UFR_POISSON_MAX_PARTIALS) that every block of the next kernel adds
+ *   up in the same fixed order; the scalars stay on the device.  After every check_every iterations (and after the last)
+ *   the host reads r.r: one 8-byte copy and one stream synchronisation; one more such look follows the set-up (b.b).  The
+ *   iteration ends when sqrt(r.r) <= tol * sqrt(b.b), seen at a look, or after max_iter iterations.  *iterations_host = the
+ *   iterations run, *residual_host = sqrt(r.r / b.b) of the recurrence at the last look, *converged_host = 1 / 0; reaching
+ *   max_iter is not an error.  b = 0: x = 0, 0 iterations, residual 0, converged.  tol >= 0, max_iter >= 1, check_every >=
+ *   1.  workspace >= ufr_poisson_workspace_bytes(dims) (device; three volumes and the partial sums); no allocation.
+ * ufr_poisson_sample: values[p] = the trilinear value of vol at point p (cell, offsets and weights as in the splat, the eight
+ *   terms added in corner order 0 .. 7); NaN for a point that is not finite.  mean_out (device fp64, nullable): the sum of
+ *   the values through the same partial sums, divided by n.  1 <= n < 2^31.  workspace >=
+ *   ufr_poisson_sample_workspace_bytes(n) (device).  Does not synchronise.
+ * Only ufr_poisson_solve synchronises.  Every argument error (null pointer, a dim below 2, 2^31 nodes or more, h or h*h not
+ * positive and finite, an origin that is not finite, a count outside its range, a workspace that is too small) is
+ * UFR_ERR_ARG (UFR_ERR_WORKSPACE for the workspace) with the reason in the thread's last-error text; nothing is launched
+ * then.  b with a value that is not finite is UFR_ERR_ARG after the set-up kernel.                                     */
+#define UFR_POISSON_MAX_PARTIALS 1024
+int ufr_poisson_grid(const double* bound_min, const double* bound_max, int32_t resolution, int32_t pad, double* origin, double* h,
+                     int32_t* dims);
+int ufr_poisson_splat_keys(const double* points, int64_t n, const double* origin, double h, const int32_t* dims, int64_t* keys,
+                           ufr_stream stream);
+int ufr_poisson_splat(const double* points, const double* normals, int64_t n, const double* origin, double h, const int32_t* dims,
+                      const int64_t* keys, const int64_t* rows, double* V, double* W, ufr_stream stream);
+int ufr_poisson_divergence(const double* V, const int32_t* dims, double h, double* b, ufr_stream stream);
+int ufr_poisson_laplacian(const double* p, const int32_t* dims, double h, double* q, ufr_stream stream);
+size_t ufr_poisson_workspace_bytes(const int32_t* dims);
+int ufr_poisson_solve(const double* b, const int32_t* dims, double h, double tol, int32_t max_iter, int32_t check_every, double* x,
+                      void* workspace, size_t workspace_bytes, int32_t* iterations_host, double* residual_host,
+                      int32_t* converged_host, ufr_stream stream);
+size_t ufr_poisson_sample_workspace_bytes(int64_t n);
+int ufr_poisson_sample(const double* vol, const int32_t* dims, const double* origin, double h, const double* points, int64_t n,
+                       double* values, double* mean_out, void* workspace, size_t workspace_bytes, ufr_stream stream);
+
 void ufr_profile_enable(int on);
 int ufr_profile_read(const char** names, float* ms, int32_t* launches, int cap);
 

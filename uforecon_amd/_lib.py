@@ -158,6 +158,17 @@ SIGNATURES = {
     "ufr_points_normals": (C.c_int, [vp, i64, vp, i32, vp, i32, vp, vp, vp, vp]),
     "ufr_points_voxel_mean_workspace_bytes": (sz, [i64]),
     "ufr_points_voxel_mean": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, sz, C.POINTER(i64), vp]),
+    "ufr_poisson_grid": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), i32, i32, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), C.POINTER(i32)]),
+    "ufr_poisson_splat_keys": (C.c_int, [vp, i64, C.POINTER(C.c_double), C.c_double, C.POINTER(i32), vp, vp]),
+    "ufr_poisson_splat": (C.c_int, [vp, vp, i64, C.POINTER(C.c_double), C.c_double, C.POINTER(i32), vp, vp, vp, vp, vp]),
+    "ufr_poisson_divergence": (C.c_int, [vp, C.POINTER(i32), C.c_double, vp, vp]),
+    "ufr_poisson_laplacian": (C.c_int, [vp, C.POINTER(i32), C.c_double, vp, vp]),
+    "ufr_poisson_workspace_bytes": (sz, [C.POINTER(i32)]),
+    "ufr_poisson_solve": (C.c_int, [vp, C.POINTER(i32), C.c_double, C.c_double, i32, i32, vp, vp, sz, C.POINTER(i32),
+                                    C.POINTER(C.c_double), C.POINTER(i32), vp]),
+    "ufr_poisson_sample_workspace_bytes": (sz, [i64]),
+    "ufr_poisson_sample": (C.c_int, [vp, C.POINTER(i32), C.POINTER(C.c_double), C.c_double, vp, i64, vp, vp, vp, sz, vp]),
     "ufr_depth_consistency": (C.c_int, [vp, i32, i32, C.POINTER(vp), C.POINTER(i32), vp, i32, C.c_double, C.c_double, i32,
                                         vp, vp, vp, vp, vp]),
     "ufr_depth_points_workspace_bytes": (sz, [i32, i32]),

@@ -699,3 +699,192 @@ int ufr_splat_frames(const double* points, int64_t N, const uint8_t* colors, con
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ Poisson surface reconstruction
+namespace {
+
+int poisson_dims_check(const char* who, const int32_t* dims) {
+  UFR_REQUIRE(dims, "%s: null argument (dims)", who);
+  UFR_REQUIRE(dims[0] >= 2 && dims[1] >= 2 && dims[2] >= 2, "%s: grid %dx%dx%d (every dim must be >= 2)", who, dims[0], dims[1],
+              dims[2]);
+  UFR_REQUIRE((long long)dims[0] * dims[1] * dims[2] < (1ll << 31), "%s: grid %dx%dx%d has 2^31 nodes or more", who, dims[0], dims[1],
+              dims[2]);
+  return UFR_OK;
+}
+
+int poisson_grid_check(const char* who, const int32_t* dims, const double* origin, double h) {
+  UFR_CHECK(poisson_dims_check(who, dims));
+  UFR_REQUIRE(origin, "%s: null argument (origin)", who);
+  return cell_grid_check(who, h, origin);
+}
+
+int poisson_h_check(const char* who, double h) {
+  UFR_REQUIRE(h > 0.0 && std::isfinite(h) && std::isfinite(1.0 / (h * h)) && h * h > 0.0, "%s: h %g (must be positive and finite, and so must h^2)", who, h);
+  return UFR_OK;
+}
+
+// solver: [r | p | q, one volume each | partials of p.q | partials of r.r | state fp64 x 4]
+struct PoissonWs { double *r, *p, *q, *pq_part, *rr_part, *state; };
+PoissonWs carve_poisson(Carver& c, long long n) {
+  PoissonWs w;
+  w.r = c.take<double>((size_t)n);
+  w.p = c.take<double>((size_t)n);
+  w.q = c.take<double>((size_t)n);
+  w.pq_part = c.take<double>(kPsMaxBlocks);
+  w.rr_part = c.take<double>(kPsMaxBlocks);
+  w.state = c.take<double>(4);
+  return w;
+}
+
+// samples: [partials fp64]
+double* carve_poisson_sample(Carver& c) { return c.take<double>(kPsMaxBlocks); }
+
+bool poisson_dims_ok(const int32_t* dims) {
+  return dims && dims[0] >= 2 && dims[1] >= 2 && dims[2] >= 2 && (long long)dims[0] * dims[1] * dims[2] < (1ll << 31);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ufr_poisson_grid(const double* bound_min, const double* bound_max, int32_t resolution, int32_t pad, double* origin, double* h,
+                     int32_t* dims) {
+  const char* who = "ufr_poisson_grid";
+  UFR_REQUIRE(bound_min && bound_max && origin && h && dims, "%s: null argument", who);
+  UFR_REQUIRE(resolution >= 4, "%s: resolution %d (must be >= 4)", who, resolution);
+  UFR_REQUIRE(pad >= 2, "%s: pad %d (must be >= 2: the splat and the central differences stay inside the grid)", who, pad);
+  double extent = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    UFR_REQUIRE(std::isfinite(bound_min[a]) && std::isfinite(bound_max[a]), "%s: the bounds are not finite (axis %d: %g .. %g)", who, a,
+                bound_min[a], bound_max[a]);
+    UFR_REQUIRE(bound_max[a] >= bound_min[a], "%s: axis %d: max %g < min %g", who, a, bound_max[a], bound_min[a]);
+    const double e = bound_max[a] - bound_min[a];
+    if (e > extent) extent = e;
+  }
+  const double hh = extent / (double)resolution;
+  UFR_REQUIRE(hh > 0.0 && std::isfinite(hh) && hh * hh > 0.0 && std::isfinite(1.0 / (hh * hh)),
+              "%s: degenerate extent %g (the samples span no axis, or h^2 leaves the fp64 range)", who, extent);
+  long long d[3], nodes = 1;
+  for (int a = 0; a < 3; ++a) {
+    d[a] = (long long)ceil((bound_max[a] - bound_min[a]) / hh) + 1 + 2ll * pad;
+    UFR_REQUIRE(d[a] < (1ll << 31), "%s: %lld nodes on axis %d", who, d[a], a);
+    nodes *= d[a];
+    UFR_REQUIRE(nodes < (1ll << 31), "%s: resolution %d, pad %d: 2^31 nodes or more", who, resolution, pad);
+  }
+  for (int a = 0; a < 3; ++a) {
+    origin[a] = bound_min[a] - (double)pad * hh;
+    dims[a] = (int32_t)d[a];
+  }
+  *h = hh;
+  return UFR_OK;
+}
+
+int ufr_poisson_splat_keys(const double* points, int64_t n, const double* origin, double h, const int32_t* dims, int64_t* keys,
+                           ufr_stream stream) {
+  const char* who = "ufr_poisson_splat_keys";
+  UFR_REQUIRE(points && keys, "%s: null argument", who);
+  UFR_REQUIRE(n >= 1 && n < (1ll << 28), "%s: n %lld (must be 1 .. 2^28 - 1)", who, (long long)n);
+  UFR_CHECK(poisson_grid_check(who, dims, origin, h));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("poisson_splat_keys", s, launch_poisson_splat_keys(points, n, origin, h, dims, reinterpret_cast<long long*>(keys), s));
+  return UFR_OK;
+}
+
+int ufr_poisson_splat(const double* points, const double* normals, int64_t n, const double* origin, double h, const int32_t* dims,
+                      const int64_t* keys, const int64_t* rows, double* V, double* W, ufr_stream stream) {
+  const char* who = "ufr_poisson_splat";
+  UFR_REQUIRE(points && normals && keys && rows && V && W, "%s: null argument", who);
+  UFR_REQUIRE(n >= 1 && n < (1ll << 28), "%s: n %lld (must be 1 .. 2^28 - 1)", who, (long long)n);
+  UFR_CHECK(poisson_grid_check(who, dims, origin, h));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("poisson_splat", s, launch_poisson_splat_sum(points, normals, n, origin, h, dims, reinterpret_cast<const long long*>(keys),
+      reinterpret_cast<const long long*>(rows), V, W, s));
+  return UFR_OK;
+}
+
+int ufr_poisson_divergence(const double* V, const int32_t* dims, double h, double* b, ufr_stream stream) {
+  const char* who = "ufr_poisson_divergence";
+  UFR_REQUIRE(V && b, "%s: null argument", who);
+  UFR_CHECK(poisson_dims_check(who, dims));
+  UFR_CHECK(poisson_h_check(who, h));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("poisson_divergence", s, launch_poisson_divergence(V, dims, h, b, s));
+  return UFR_OK;
+}
+
+int ufr_poisson_laplacian(const double* p, const int32_t* dims, double h, double* q, ufr_stream stream) {
+  const char* who = "ufr_poisson_laplacian";
+  UFR_REQUIRE(p && q && p != q, "%s: null argument, or q aliases p", who);
+  UFR_CHECK(poisson_dims_check(who, dims));
+  UFR_CHECK(poisson_h_check(who, h));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("poisson_laplacian", s, launch_poisson_laplace(p, dims, h, q, nullptr, s));
+  return UFR_OK;
+}
+
+size_t ufr_poisson_workspace_bytes(const int32_t* dims) {
+  return poisson_dims_ok(dims) ? carved_bytes(carve_poisson, (long long)dims[0] * dims[1] * dims[2]) : 0;
+}
+
+int ufr_poisson_solve(const double* b, const int32_t* dims, double h, double tol, int32_t max_iter, int32_t check_every, double* x,
+                      void* workspace, size_t workspace_bytes, int32_t* iterations_host, double* residual_host,
+                      int32_t* converged_host, ufr_stream stream) {
+  const char* who = "ufr_poisson_solve";
+  UFR_REQUIRE(b && x && workspace && iterations_host && residual_host && converged_host, "%s: null argument", who);
+  UFR_CHECK(poisson_dims_check(who, dims));
+  UFR_CHECK(poisson_h_check(who, h));
+  UFR_REQUIRE(tol >= 0.0 && std::isfinite(tol), "%s: tol %g (must be >= 0 and finite)", who, tol);
+  UFR_REQUIRE(max_iter >= 1 && check_every >= 1, "%s: max_iter %d, check_every %d (each must be >= 1)", who, max_iter, check_every);
+  const long long n = (long long)dims[0] * dims[1] * dims[2];
+  Carver c(workspace);
+  const PoissonWs w = carve_poisson(c, n);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("poisson_cg_init", s, launch_poisson_cg_init(b, n, x, w.r, w.p, w.rr_part, w.state, s));
+  double rr = 0.0;
+  UFR_HIP(hipMemcpyAsync(&rr, w.state, sizeof(double), hipMemcpyDeviceToHost, s));
+  UFR_HIP(hipStreamSynchronize(s));
+  UFR_REQUIRE(std::isfinite(rr), "%s: b.b = %g (b holds values that are not finite, or its square sum leaves the fp64 range)", who, rr);
+  const double bnorm = sqrt(rr);
+  int it = 0, conv = 0;
+  if (rr == 0.0) {           // b = 0: x = 0 is the answer, and no quotient is formed
+    conv = 1;
+  } else {
+    int slot = 0;
+    while (it < max_iter && !conv) {
+      UFR_TIMED("poisson_cg_iteration", s, launch_poisson_cg_iteration(dims, h, x, w.r, w.p, w.q, w.pq_part, w.rr_part, w.state, slot, s));
+      slot ^= 1;
+      ++it;
+      if (it % check_every == 0 || it == max_iter) {       // the look: one 8-byte copy, one synchronisation
+        UFR_HIP(hipMemcpyAsync(&rr, w.state + slot, sizeof(double), hipMemcpyDeviceToHost, s));
+        UFR_HIP(hipStreamSynchronize(s));
+        if (!(rr == rr)) return fail(UFR_ERR_HIP, "%s: the residual became NaN at iteration %d", who, it);
+        conv = sqrt(rr) <= tol * bnorm;
+      }
+    }
+  }
+  *iterations_host = it;
+  *residual_host = bnorm > 0.0 ? sqrt(rr) / bnorm : 0.0;
+  *converged_host = conv;
+  return UFR_OK;
+}
+
+size_t ufr_poisson_sample_workspace_bytes(int64_t n) {
+  return (n >= 1 && n <= kChMax) ? carved_bytes(carve_poisson_sample) : 0;
+}
+
+int ufr_poisson_sample(const double* vol, const int32_t* dims, const double* origin, double h, const double* points, int64_t n,
+                       double* values, double* mean_out, void* workspace, size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_poisson_sample";
+  UFR_REQUIRE(vol && points && values && workspace, "%s: null argument", who);
+  UFR_REQUIRE(n >= 1 && n <= kChMax, "%s: n %lld (must be 1 .. 2^31 - 1)", who, (long long)n);
+  UFR_CHECK(poisson_grid_check(who, dims, origin, h));
+  Carver c(workspace);
+  double* part = carve_poisson_sample(c);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("poisson_sample", s, launch_poisson_sample(vol, dims, origin, h, points, n, values, mean_out, part, s));
+  return UFR_OK;
+}
+
+}  // extern "C"

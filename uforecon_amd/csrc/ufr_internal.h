@@ -230,6 +230,23 @@ hipError_t launch_image_undistort(const unsigned char* src, int n, int Hs, int W
 hipError_t launch_pixel_rays(const float* m_inv, const float* origin, int H, int W, float* dir, hipStream_t s);
 hipError_t launch_depth_gt(const float* pfm, int Hs, int Ws, int bottom_up, int y0, int x0, int H, int W, float scale_factor,
                            const double* cam_ray_z, float* depth, hipStream_t s);
+// poisson.hip: uniform-grid Poisson reconstruction -- splat, divergence, q = A p, conjugate gradients, samples (see the file header)
+constexpr int kPsTileX = 8, kPsTileY = 4, kPsTileZ = 64;   // nodes one block of the q = A p kernel owns at a time (x marched)
+constexpr int kPsMaxBlocks = UFR_POISSON_MAX_PARTIALS;                       // most partial sums one dot product leaves in the workspace
+long long poisson_tiles(const int* dims);
+int poisson_blocks(long long work_items);
+hipError_t launch_poisson_splat_keys(const double* pts, long long n, const double* origin, double h, const int* dims, long long* keys,
+                                     hipStream_t s);
+hipError_t launch_poisson_splat_sum(const double* pts, const double* nrm, long long n, const double* origin, double h, const int* dims,
+                                    const long long* keys, const long long* rows, double* V, double* W, hipStream_t s);
+hipError_t launch_poisson_divergence(const double* V, const int* dims, double h, double* b, hipStream_t s);
+hipError_t launch_poisson_laplace(const double* p, const int* dims, double h, double* q, double* part, hipStream_t s);
+hipError_t launch_poisson_cg_init(const double* b, long long n, double* x, double* r, double* p, double* part, double* state,
+                                  hipStream_t s);
+hipError_t launch_poisson_cg_iteration(const int* dims, double h, double* x, double* r, double* p, double* q, double* pq_part,
+                                       double* rr_part, double* state, int slot, hipStream_t s);
+hipError_t launch_poisson_sample(const double* vol, const int* dims, const double* origin, double h, const double* pts, long long n,
+                                 double* values, double* mean_out, double* part, hipStream_t s);
 // frame_metrics.hip: the scores and 8-bit previews of a validation frame (see the file header)
 constexpr int kFrameMetricsBlocks = 256;   // most partial rows one frame leaves in the workspace
 hipError_t launch_frame_metrics(const float* rgb_c, const float* rgb_f, const float* rgb_gt, const float* depth_c, const float* depth_f,

@@ -30,11 +30,12 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "double": "f8", "float64": "f8"}
 
 
-def read_ply(path: str, with_colors: bool = False):
+def read_ply(path: str, with_colors: bool = False, with_normals: bool = False):
     """(vertices (V,3) float64, faces (F,3) int32 or None) of an ASCII or binary_little_endian PLY file: vertex x / y / z as
     float or double (other vertex properties are skipped), faces as ``list uchar int|uint`` triangles.  Elements after the
     faces are ignored.  ``with_colors``: a third item, the vertex properties red / green / blue (uchar) as (V,3) uint8, or None
-    when the file has none."""
+    when the file has none.  ``with_normals``: one more item, the vertex properties nx / ny / nz (float or double) as (V,3)
+    float64, or None when the file has none."""
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.find(b"end_header")
@@ -59,7 +60,7 @@ def read_ply(path: str, with_colors: bool = False):
                 elements[-1][2].append(("scalar", t[1], t[2]))
     if fmt not in ("ascii", "binary_little_endian"):
         raise ValueError(f"{path}: PLY format {fmt!r} is not supported (ascii and binary_little_endian are)")
-    verts, faces, colors = None, None, None
+    verts, faces, colors, normals = None, None, None, None
     tokens = raw[body_at:].split() if fmt == "ascii" else None
     pos = 0 if fmt == "ascii" else body_at
     for name, count, props in elements:
@@ -74,11 +75,15 @@ def read_ply(path: str, with_colors: bool = False):
                 raise ValueError(f"{path}: x, y, z must be float or double")
             rgb = ("red", "green", "blue")
             has_rgb = all(a in names and _PLY_TYPES.get(props[names.index(a)][1]) == "u1" for a in rgb)
+            nxyz = ("nx", "ny", "nz")
+            has_n = with_normals and all(a in names and _PLY_TYPES.get(props[names.index(a)][1]) in ("f4", "f8") for a in nxyz)
             if fmt == "ascii":
                 rows = np.array(tokens[pos:pos + count * len(props)], dtype="S").astype(np.float64).reshape(count, len(props))
                 verts = rows[:, cols] if count else np.zeros((0, 3))
                 if has_rgb:
                     colors = rows[:, [names.index(a) for a in rgb]].astype(np.uint8) if count else np.zeros((0, 3), np.uint8)
+                if has_n:
+                    normals = rows[:, [names.index(a) for a in nxyz]] if count else np.zeros((0, 3))
                 pos += count * len(props)
             else:
                 dt = np.dtype([(n, "<" + _PLY_TYPES[t]) for _, t, n in props])
@@ -86,6 +91,8 @@ def read_ply(path: str, with_colors: bool = False):
                 verts = np.stack([rec[a].astype(np.float64) for a in "xyz"], 1) if count else np.zeros((0, 3))
                 if has_rgb:
                     colors = np.stack([rec[a] for a in rgb], 1) if count else np.zeros((0, 3), np.uint8)
+                if has_n:
+                    normals = np.stack([rec[a].astype(np.float64) for a in nxyz], 1) if count else np.zeros((0, 3))
                 pos += count * dt.itemsize
         elif name == "face":
             if len(props) != 1 or props[0][0] != "list" or _PLY_TYPES.get(props[0][1][1]) not in ("i4", "u4"):
@@ -110,7 +117,7 @@ def read_ply(path: str, with_colors: bool = False):
             break
     if verts is None:
         raise ValueError(f"{path}: no vertex element")
-    return (verts, faces, colors) if with_colors else (verts, faces)
+    return (verts, faces) + ((colors,) if with_colors else ()) + ((normals,) if with_normals else ())
 
 
 def _load_arrays(path: str, names):

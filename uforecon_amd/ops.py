@@ -1101,6 +1101,138 @@ def voxel_downsample(points: torch.Tensor, voxel: float, colors: Optional[torch.
             None if out_n is None else out_n[:M].contiguous(), count[:M].contiguous())
 
 
+# ---- Poisson surface reconstruction (csrc/poisson.hip; uforecon_amd/poisson_mesh.py strings these together)
+POISSON_TILE = (8, 4, 64)        # kPsTileX / Y / Z of csrc/ufr_internal.h: the nodes one block of q = A p owns at a time
+POISSON_MAX_PARTIALS = 1024      # UFR_POISSON_MAX_PARTIALS of include/ufr.h
+
+
+def _poisson_dims(dims, who: str):
+    d = tuple(int(v) for v in dims)
+    if len(d) != 3:
+        raise UfrError(f"{who}: dims {dims!r}: expected three ints")
+    return d, (C.c_int32 * 3)(*d)
+
+
+def _poisson_volume(t: torch.Tensor, name: str, shape) -> int:
+    p = _dev(t, name, torch.float64)
+    if tuple(t.shape) != tuple(shape):
+        raise UfrError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return p
+
+
+def poisson_grid(points: torch.Tensor, resolution: int = 256, pad: int = 4):
+    """The grid of a Poisson reconstruction over ``points`` ((N,3) CUDA float64): ``(origin, h, dims)`` with h = the largest
+    extent / ``resolution``, origin = min - pad h and dims = ceil(extent / h) + 1 + 2 pad nodes per axis (include/ufr.h,
+    ufr_poisson_grid).  Raises UfrError for resolution < 4, pad < 2, coordinates that are not finite, a cloud without extent
+    and a grid of 2^31 nodes or more."""
+    _points64(points, "points")
+    if int(points.shape[0]) == 0:
+        raise UfrError("poisson_grid: empty cloud")
+    mn, mx = _finite_bounds(points, "points")
+    lo, hi = (C.c_double * 3)(*mn.tolist()), (C.c_double * 3)(*mx.tolist())
+    origin, h, dims = (C.c_double * 3)(), C.c_double(0.0), (C.c_int32 * 3)()
+    _lib.check(_lib.load().ufr_poisson_grid(lo, hi, int(resolution), int(pad), origin, C.byref(h), dims), "ufr_poisson_grid")
+    return tuple(origin), float(h.value), tuple(int(d) for d in dims)
+
+
+def poisson_splat(points: torch.Tensor, normals: torch.Tensor, origin, h: float, dims):
+    """``V`` (3,X,Y,Z) and ``W`` (X,Y,Z) float64: the trilinear splat of ``normals`` and of 1 from ``points`` ((N,3) CUDA
+    float64 both) onto the grid, every node's sum taken in ascending sample index (include/ufr.h, ufr_poisson_splat): eight
+    (node, row) pairs per sample, one stable sort, and the head of every run sums it left to right."""
+    pp, pn = _points64(points, "points"), _points64(normals, "normals")
+    N = int(points.shape[0])
+    if tuple(normals.shape) != (N, 3):
+        raise UfrError(f"normals: expected shape ({N}, 3), got {tuple(normals.shape)}")
+    d, cd = _poisson_dims(dims, "poisson_splat")
+    o = (C.c_double * 3)(*[float(v) for v in origin])
+    lib = _lib.load()
+    if not 1 <= N < 2 ** 28:
+        raise UfrError(f"poisson_splat: {N} samples (must be 1 .. 2^28 - 1)")
+    keys = torch.empty(8 * N, dtype=torch.int64, device=points.device)
+    _lib.check(lib.ufr_poisson_splat_keys(pp, N, o, float(h), cd, keys.data_ptr(), _stream()), "ufr_poisson_splat_keys")
+    keys, rows = torch.sort(keys, stable=True)
+    V = torch.empty((3,) + d, dtype=torch.float64, device=points.device)
+    W = torch.empty(d, dtype=torch.float64, device=points.device)
+    _lib.check(lib.ufr_poisson_splat(pp, pn, N, o, float(h), cd, keys.data_ptr(), rows.data_ptr(), V.data_ptr(), W.data_ptr(),
+                                     _stream()), "ufr_poisson_splat")
+    return V, W
+
+
+def poisson_divergence(V: torch.Tensor, h: float) -> torch.Tensor:
+    """``b`` (X,Y,Z) = div ``V`` ((3,X,Y,Z) CUDA float64) by central differences over 2 h, V = 0 outside the grid."""
+    if not isinstance(V, torch.Tensor) or V.dim() != 4 or V.shape[0] != 3:
+        raise UfrError("V: expected a (3, X, Y, Z) tensor")
+    d, cd = _poisson_dims(V.shape[1:], "poisson_divergence")
+    b = torch.empty(d, dtype=torch.float64, device=V.device)
+    _lib.check(_lib.load().ufr_poisson_divergence(_dev(V, "V", torch.float64), cd, float(h), b.data_ptr(), _stream()),
+               "ufr_poisson_divergence")
+    return b
+
+
+def poisson_laplacian(p: torch.Tensor, h: float) -> torch.Tensor:
+    """One application of the solver's matrix: ``A p`` for ``p`` (X,Y,Z) CUDA float64, A = the negated 7-point Laplacian over
+    h^2 with zeros outside the grid (include/ufr.h, ufr_poisson_laplacian)."""
+    if not isinstance(p, torch.Tensor) or p.dim() != 3:
+        raise UfrError("p: expected an (X, Y, Z) tensor")
+    d, cd = _poisson_dims(p.shape, "poisson_laplacian")
+    q = torch.empty(d, dtype=torch.float64, device=p.device)
+    _lib.check(_lib.load().ufr_poisson_laplacian(_dev(p, "p", torch.float64), cd, float(h), q.data_ptr(), _stream()),
+               "ufr_poisson_laplacian")
+    return q
+
+
+def poisson_workspace_bytes(dims) -> int:
+    """Bytes of the solver's workspace for a grid of ``dims`` nodes (0: the library refuses the grid)."""
+    return int(_lib.load().ufr_poisson_workspace_bytes(_poisson_dims(dims, "poisson_workspace_bytes")[1]))
+
+
+def poisson_solve(b: torch.Tensor, h: float, tol: float = 1e-6, max_iter: Optional[int] = None, check_every: int = 16,
+                  workspace: Optional[torch.Tensor] = None):
+    """``(x, info)``: the solution of A x = -b by conjugate gradients from 0 (include/ufr.h, ufr_poisson_solve), ``b`` (X,Y,Z)
+    CUDA float64; ``info`` = dict(iterations, residual = |r| / |b| of the recurrence, converged).  The host looks at the
+    residual every ``check_every`` iterations; ``max_iter`` defaults to 8 max(dims) and reaching it is reported, not raised.
+    ``workspace``: a CUDA uint8 tensor of at least ``poisson_workspace_bytes(dims)`` bytes (allocated when None)."""
+    if not isinstance(b, torch.Tensor) or b.dim() != 3:
+        raise UfrError("b: expected an (X, Y, Z) tensor")
+    d, cd = _poisson_dims(b.shape, "poisson_solve")
+    pb = _dev(b, "b", torch.float64)
+    lib = _lib.load()
+    nbytes = lib.ufr_poisson_workspace_bytes(cd)
+    if nbytes == 0:
+        raise UfrError(f"poisson_solve: grid {d} unsupported (every dim >= 2, fewer than 2^31 nodes)")
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
+    pw = _dev(workspace, "workspace", torch.uint8)
+    if max_iter is None:
+        max_iter = 8 * max(d)
+    x = torch.empty(d, dtype=torch.float64, device=b.device)
+    it, res, conv = C.c_int32(0), C.c_double(0.0), C.c_int32(0)
+    _lib.check(lib.ufr_poisson_solve(pb, cd, float(h), float(tol), int(max_iter), int(check_every), x.data_ptr(), pw,
+                                     workspace.numel(), C.byref(it), C.byref(res), C.byref(conv), _stream()), "ufr_poisson_solve")
+    return x, dict(iterations=int(it.value), residual=float(res.value), converged=bool(conv.value))
+
+
+def poisson_sample(vol: torch.Tensor, origin, h: float, points: torch.Tensor, return_mean: bool = False):
+    """The trilinear value of ``vol`` ((X,Y,Z) CUDA float64, node (i,j,k) at origin + h (i,j,k)) at every point ((N,3) CUDA
+    float64), positions clamped to the grid (include/ufr.h, ufr_poisson_sample).  ``return_mean``: also their mean, a CUDA
+    float64 scalar summed in a fixed order."""
+    if not isinstance(vol, torch.Tensor) or vol.dim() != 3:
+        raise UfrError("vol: expected an (X, Y, Z) tensor")
+    d, cd = _poisson_dims(vol.shape, "poisson_sample")
+    pv, pp = _dev(vol, "vol", torch.float64), _points64(points, "points")
+    N = int(points.shape[0])
+    values = torch.empty(N, dtype=torch.float64, device=vol.device)
+    mean = torch.zeros((), dtype=torch.float64, device=vol.device)
+    if N:
+        lib = _lib.load()
+        nbytes = lib.ufr_poisson_sample_workspace_bytes(N)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+        o = (C.c_double * 3)(*[float(v) for v in origin])
+        _lib.check(lib.ufr_poisson_sample(pv, cd, o, float(h), pp, N, values.data_ptr(), mean.data_ptr() if return_mean else None,
+                                          ws.data_ptr(), nbytes, _stream()), "ufr_poisson_sample")
+    return (values, mean) if return_mean else values
+
+
 # ---- depth-map fusion (csrc/depth_fusion.hip; uforecon_amd/depth_fusion.py strings these together)
 DEPTH_MAX_SOURCES = 64     # UFR_DEPTH_MAX_SOURCES of include/ufr.h
 DEPTH_PAIR_DOUBLES = 68    # UFR_DEPTH_PAIR_DOUBLES
