@@ -850,6 +850,68 @@ int ufr_splat_frames(const double* points, int64_t N, const uint8_t* colors, con
                      double edl_strength, int32_t edl_radius, uint8_t* image, float* depth, int32_t* point_id, void* workspace,
                      size_t workspace_bytes, ufr_stream stream);
 
+/* ---- mesh colouring (ABI 507, additive) -----------------------------------------------------------------------
+ * Per-vertex colour from the photographs, visibility-aware: the last stage of the chain, between clean_mesh and
+ * render_trajectory; the reference has no such stage.  uforecon_amd/color_mesh.py is the caller, tests/color_mesh_ref.py the
+ * numpy statement of every rule below.  Neither Open3D nor MVS-texturing was compared against: the rule written here is the
+ * rule.  Everything is fp64, every product and sum rounded on its own (no fused multiply-add), sums taken left to right;
+ * there is no floating-point atomic, so a rerun gives the same bits.
+ *
+ * ufr_color_vertices: verts (V,3) fp64, device; normals (V,3) fp64, device, nullable; images (n_views,H,W,3) uint8,
+ *   device, all views of one size; depth (n_views,H,W) fp32, device, nullable: the z-depth ufr_raster_frames writes, 0 = no
+ *   hit.  Cameras: HOST fp64 row-major, the convention of ufr_splat_frames: k (n_views,3,3), already divided by k[2][2];
+ *   w2c (n_views,4,4); centre (n_views,3), the camera centres in world coordinates.  1 <= n_views <= UFR_MESH_MAX_VIEWS;
+ *   H, W >= 2, H * W < 2^31; 1 <= V <= 2^31 - 1.  z_min >= 0, depth_tol >= 0 (both finite), min_cos in 0..1, power in 0..8,
+ *   mode UFR_MESH_COLOR_MEAN or UFR_MESH_COLOR_BEST, fill HOST uint8[3].  Outputs (device): colors (V,3) uint8, views_used
+ *   (V) uint8.  One thread owns vertex p and walks the views k in ascending order:
+ *     c = w2c[:3,:3] p + w2c[:3,3] (the three products, then the translation).  The view is skipped when a coordinate of p
+ *       or c is not finite, or not c.z > z_min.
+ *     q = k c, x = q.x / q.z, y = q.y / q.z; pixel centres are the integers, as in ufr_mesh_first_hit.
+ *     x0 = floor(x), y0 = floor(y), fx = x - x0, fy = y - y0.  The view is skipped unless 0 <= x0, x0 + 1 <= W - 1, 0 <= y0
+ *       and y0 + 1 <= H - 1: all four texels lie in the picture.
+ *     Occlusion (depth given): the four depths D(y0..y0+1, x0..x0+1) must all be > 0 and c.z <= (1 + depth_tol) * min(D), D
+ *       widened, 1 + depth_tol rounded once.  Conservative on purpose: a vertex whose footprint touches a pixel without a
+ *       hit, or a pixel nearer than it, takes no colour from that view, so neither the picture's background nor a nearer
+ *       surface bleeds onto it.
+ *     Angle (normals given): e = p - centre, d = e / sqrt((e.x*e.x + e.y*e.y) + e.z*e.z), cosv = |(N.x*d.x + N.y*d.y) +
+ *       N.z*d.z|: two-sided, as the rasteriser shades, because the winding is not trusted.  The view is skipped unless cosv
+ *       >= min_cos and cosv > 0: a zero normal is never seen.  Without normals cosv = 1.
+ *     Weight: w = 1, then w = w * cosv, power times (no pow: its last bit differs between libraries).
+ *     Sample, per channel, I the widened bytes at (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1):
+ *       s = (1 - fy) * ((1 - fx) * I00 + fx * I01) + fy * ((1 - fx) * I10 + fx * I11).
+ *     Mode mean: A += w * s per channel and Wsum += w, in view order; colour = rint(A / Wsum), round half to even, clamped
+ *       to 0..255 (not a number: 0).  Mode best: the view of largest w wins, ties to the lowest view index; colour = rint(s)
+ *       of that view, clamped likewise.
+ *   views_used = the number of views not skipped; when it is 0 the vertex gets fill.  workspace >=
+ *   ufr_color_vertices_workspace_bytes(n_views) (device; the camera table, which travels there as kernel arguments of
+ *   small upload kernels: no copy, no allocation).  A camera that is not finite or whose w2c[:3,:3] is singular fails
+ *   before anything is launched.  Does not synchronise.
+ * ufr_color_fill_round: one Jacobi round that gives colour to empty vertices from their neighbours.  faces (F,3) int32,
+ *   sorted_slots (3F) and run_starts (V+1) int64 as ufr_raster_vertex_normals takes them; colors_in (V,3) uint8; state_in (V)
+ *   uint8, 0 = empty.  A vertex with state_in != 0 is copied (colour and state).  For an empty vertex its corner run is
+ *   walked in ascending position; for each slot 3f + e the face's other two corners are visited in the order (e + 1) % 3,
+ *   (e + 2) % 3, and every visited corner with state_in != 0 adds its three channels to integer sums and 1 to a count.  A
+ *   neighbour shared by two faces counts twice: that is the rule.  count > 0: each channel = sum / count rounded half to
+ *   even in integers (q = sum / count, r = sum % count, q + 1 iff 2r > count, or 2r == count and q is odd: the rule of
+ *   ufr_raster_downsample), state_out = 1 and *filled (device int32, the caller zeroes it) += 1 by an integer atomic.  count
+ *   = 0: the vertex stays empty, colour copied.  A slot outside 0..3F-1, a slot whose corner is not the vertex and a corner
+ *   outside 0..V-1 contribute nothing.  colors_out / state_out must not alias the inputs: the round is double-buffered, so
+ *   it does not depend on scheduling.  Integers only.  F <= (2^31 - 1) / 3.  Does not synchronise.
+ * Every argument error (null pointer, a size or count out of range, z_min or depth_tol negative or not finite, min_cos
+ * outside 0..1, power outside 0..8, an unknown mode, a workspace that is too small) is UFR_ERR_ARG with the reason in the
+ * thread's last-error text; nothing is launched then.                                                                  */
+#define UFR_MESH_COLOR_MEAN 0
+#define UFR_MESH_COLOR_BEST 1
+#define UFR_MESH_COLOR_MAX_POWER 8
+size_t ufr_color_vertices_workspace_bytes(int32_t n_views);
+int ufr_color_vertices(const double* verts, const double* normals, int64_t V, const uint8_t* images, const float* depth,
+                           const double* k, const double* w2c, const double* centre, int32_t n_views, int32_t H, int32_t W,
+                           double z_min, double depth_tol, double min_cos, int32_t power, int32_t mode, const uint8_t* fill,
+                           uint8_t* colors, uint8_t* views_used, void* workspace, size_t workspace_bytes, ufr_stream stream);
+int ufr_color_fill_round(const int32_t* faces, int64_t V, int64_t F, const int64_t* sorted_slots, const int64_t* run_starts,
+                              const uint8_t* colors_in, const uint8_t* state_in, uint8_t* colors_out, uint8_t* state_out,
+                              int32_t* filled, ufr_stream stream);
+
 /* ---- point-cloud filtering (ABI 507, additive) ----------------------------------------------------------------
  * The cleanup between depth fusion and scoring that an MVS pipeline expects (voxel downsampling, statistical and radius
  * outlier removal, normal estimation); the reference leaves it to Open3D.  uforecon_amd/pcd_filter.py is the caller,

@@ -190,6 +190,11 @@ SIGNATURES = {
     "ufr_splat_frames_workspace_bytes": (sz, [i32, i32]),
     "ufr_splat_frames": (C.c_int, [vp, i64, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, i32, i32, i32, C.c_double,
                                    C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_double, i32, vp, vp, vp, vp, sz, vp]),
+    "ufr_color_vertices_workspace_bytes": (sz, [i32]),
+    "ufr_color_vertices": (C.c_int, [vp, vp, i64, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i32,
+                                         i32, i32, C.c_double, C.c_double, C.c_double, i32, i32, C.POINTER(C.c_uint8), vp, vp, vp, sz,
+                                         vp]),
+    "ufr_color_fill_round": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ufr_image_resize_u8": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),
     "ufr_pixel_rays": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, vp, vp]),
     "ufr_image_resize_mask_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),

@@ -698,6 +698,65 @@ int ufr_splat_frames(const double* points, int64_t N, const uint8_t* colors, con
   return UFR_OK;
 }
 
+// ------------------------------------------------------------------ mesh colouring
+// [camera table: one MeshColorCam per view]
+MeshColorCam* carve_mesh_colors(Carver& c, int n_views) { return c.take<MeshColorCam>((size_t)n_views); }
+
+size_t ufr_color_vertices_workspace_bytes(int32_t n_views) {
+  return (n_views >= 1 && n_views <= UFR_MESH_MAX_VIEWS) ? carved_bytes(carve_mesh_colors, (int)n_views) : 0;
+}
+
+int ufr_color_vertices(const double* verts, const double* normals, int64_t V, const uint8_t* images, const float* depth,
+                           const double* k, const double* w2c, const double* centre, int32_t n_views, int32_t H, int32_t W,
+                           double z_min, double depth_tol, double min_cos, int32_t power, int32_t mode, const uint8_t* fill,
+                           uint8_t* colors, uint8_t* views_used, void* workspace, size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_color_vertices";
+  UFR_REQUIRE(verts && images && k && w2c && centre && fill && colors && views_used && workspace, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax, "%s: V %lld (must be 1 .. 2^31 - 1)", who, (long long)V);
+  UFR_REQUIRE(n_views >= 1 && n_views <= UFR_MESH_MAX_VIEWS, "%s: n_views %d (must be 1 .. %d)", who, n_views, UFR_MESH_MAX_VIEWS);
+  UFR_REQUIRE(H >= 2 && W >= 2, "%s: image %dx%d (H and W must be >= 2)", who, H, W);
+  UFR_CHECK(depth_image_check(who, H, W));
+  UFR_REQUIRE(z_min >= 0.0 && std::isfinite(z_min), "%s: z_min %g (must be >= 0 and finite)", who, z_min);
+  UFR_REQUIRE(depth_tol >= 0.0 && std::isfinite(depth_tol), "%s: depth_tol %g (must be >= 0 and finite)", who, depth_tol);
+  UFR_REQUIRE(min_cos >= 0.0 && min_cos <= 1.0, "%s: min_cos %g (must be 0 .. 1)", who, min_cos);
+  UFR_REQUIRE(power >= 0 && power <= UFR_MESH_COLOR_MAX_POWER, "%s: power %d (must be 0 .. %d)", who, power, UFR_MESH_COLOR_MAX_POWER);
+  UFR_REQUIRE(mode == UFR_MESH_COLOR_MEAN || mode == UFR_MESH_COLOR_BEST, "%s: unknown mode %d", who, mode);
+  Carver cv(workspace);
+  MeshColorCam* table = carve_mesh_colors(cv, n_views);
+  UFR_REQUIRE(workspace_bytes >= cv.off, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, cv.off);
+  MeshColorCam cams[UFR_MESH_MAX_VIEWS];
+  for (int32_t f = 0; f < n_views; ++f) {   // all, before any launch
+    const double *kk = k + 9 * (size_t)f, *m = w2c + 16 * (size_t)f, *cc = centre + 3 * (size_t)f;
+    for (int i = 0; i < 9; ++i) UFR_REQUIRE(std::isfinite(kk[i]), "%s: view %d: k is not finite", who, f);
+    for (int i = 0; i < 16; ++i) UFR_REQUIRE(std::isfinite(m[i]), "%s: view %d: w2c is not finite", who, f);
+    for (int i = 0; i < 3; ++i) UFR_REQUIRE(std::isfinite(cc[i]), "%s: view %d: the camera centre is not finite", who, f);
+    const double r3[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
+    double inv[9];
+    UFR_REQUIRE(invert3(r3, inv), "%s: view %d: w2c is singular", who, f);
+    for (int i = 0; i < 9; ++i) cams[f].k[i] = kk[i], cams[f].r[i] = r3[i];
+    for (int i = 0; i < 3; ++i) cams[f].t[i] = m[4 * i + 3], cams[f].c[i] = cc[i];
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_color_cams", s, launch_mesh_color_cams(cams, n_views, table, s));
+  UFR_TIMED("mesh_vertex_colors", s, launch_mesh_vertex_colors(verts, normals, V, images, depth, table, n_views, H, W, z_min, depth_tol,
+      min_cos, power, mode, fill, colors, views_used, s));
+  return UFR_OK;
+}
+
+int ufr_color_fill_round(const int32_t* faces, int64_t V, int64_t F, const int64_t* sorted_slots, const int64_t* run_starts,
+                              const uint8_t* colors_in, const uint8_t* state_in, uint8_t* colors_out, uint8_t* state_out,
+                              int32_t* filled, ufr_stream stream) {
+  const char* who = "ufr_color_fill_round";
+  UFR_REQUIRE(faces && sorted_slots && run_starts && colors_in && state_in && colors_out && state_out && filled, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax / 3, "%s: V %lld, F %lld (V must be 1 .. 2^31 - 1, F 1 .. (2^31 - 1) / 3)",
+              who, (long long)V, (long long)F);
+  UFR_REQUIRE(colors_out != colors_in && state_out != state_in, "%s: the round is double-buffered: out must not alias in", who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_color_fill_round", s, launch_mesh_color_fill_round(faces, V, F, reinterpret_cast<const long long*>(sorted_slots),
+      reinterpret_cast<const long long*>(run_starts), colors_in, state_in, colors_out, state_out, filled, s));
+  return UFR_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ Poisson surface reconstruction

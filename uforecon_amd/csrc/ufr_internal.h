@@ -247,6 +247,20 @@ hipError_t launch_poisson_cg_iteration(const int* dims, double h, double* x, dou
                                        double* rr_part, double* state, int slot, hipStream_t s);
 hipError_t launch_poisson_sample(const double* vol, const int* dims, const double* origin, double h, const double* pts, long long n,
                                  double* values, double* mean_out, double* part, hipStream_t s);
+// mesh_color.hip: per-vertex colour from the photographs and the neighbour fill (see the file header)
+constexpr int kColorThreads = 256;         // vertices a block owns (ops.MESH_COLOR_BLOCK says the same to the tests)
+constexpr int kColorCamsPerLaunch = 16;    // camera records one upload launch carries in its argument segment
+struct MeshColorCam {
+  double k[9], r[9], t[3], c[3];           // intrinsics, w2c's rotation and translation, the centre in world coordinates
+};
+hipError_t launch_mesh_color_cams(const MeshColorCam* cams_host, int n_views, MeshColorCam* table, hipStream_t s);
+hipError_t launch_mesh_vertex_colors(const double* verts, const double* normals, long long V, const unsigned char* images,
+                                     const float* depth, const MeshColorCam* table, int n_views, int H, int W, double z_min,
+                                     double depth_tol, double min_cos, int power, int mode, const unsigned char* fill,
+                                     unsigned char* colors, unsigned char* views_used, hipStream_t s);
+hipError_t launch_mesh_color_fill_round(const int* faces, long long V, long long F, const long long* slots, const long long* runs,
+                                        const unsigned char* colors_in, const unsigned char* state_in, unsigned char* colors_out,
+                                        unsigned char* state_out, int* filled, hipStream_t s);
 // frame_metrics.hip: the scores and 8-bit previews of a validation frame (see the file header)
 constexpr int kFrameMetricsBlocks = 256;   // most partial rows one frame leaves in the workspace
 hipError_t launch_frame_metrics(const float* rgb_c, const float* rgb_f, const float* rgb_gt, const float* depth_c, const float* depth_f,

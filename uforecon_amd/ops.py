@@ -1600,6 +1600,123 @@ def splat_frames(points: torch.Tensor, k, w2cs, H: int, W: int, colors: Optional
     return out
 
 
+# ---- mesh colouring (csrc/mesh_color.hip; uforecon_amd/color_mesh.py strings these together)
+MESH_COLOR_BLOCK = 256           # kColorThreads of csrc/ufr_internal.h: the vertices one block owns
+MESH_COLOR_MAX_POWER = 8         # UFR_MESH_COLOR_MAX_POWER of include/ufr.h
+MESH_COLOR_MODES = {"mean": 0, "best": 1}   # UFR_MESH_COLOR_MEAN / _BEST
+
+
+def mesh_vertex_colors(verts: torch.Tensor, normals: Optional[torch.Tensor], images: torch.Tensor, depth: Optional[torch.Tensor],
+                       k, w2c, centre, z_min: float = 0.0, depth_tol: float = 0.005, min_cos: float = 0.2, power: int = 2,
+                       mode: str = "mean", fill=(128, 128, 128)):
+    """ufr_color_vertices: per-vertex colour from ``n`` photographs (include/ufr.h states every rule).  ``verts`` (V,3) CUDA
+    float64; ``normals`` (V,3) CUDA float64 or None (every view weighs 1); ``images`` (n,H,W,3) CUDA uint8; ``depth`` (n,H,W)
+    CUDA float32 z-depth of the mesh from the same cameras (``raster_frames(return_depth=True)``; 0: no hit) or None (no
+    occlusion test); ``k`` (n,3,3), ``w2c`` (n,4,4), ``centre`` (n,3): host float64 arrays, ``k`` already divided by
+    ``k[2,2]``.  ``mode`` "mean" (weights cos^power) or "best" (the view of largest weight).  Returns ``colors`` (V,3) uint8
+    and ``views_used`` (V,) uint8; a vertex no view saw gets ``fill``.  Synchronises nowhere."""
+    import numpy as np
+
+    pv = _points64(verts, "verts")
+    V = int(verts.shape[0])
+    pn = pd = None
+    if normals is not None:
+        pn = _points64(normals, "normals")
+        if normals.shape[0] != V:
+            raise UfrError(f"normals: expected shape ({V}, 3), got {tuple(normals.shape)}")
+    pi = _dev(images, "images", torch.uint8)
+    if images.dim() != 4 or images.shape[3] != 3:
+        raise UfrError(f"images: expected shape (n, H, W, 3), got {tuple(images.shape)}")
+    n, H, W = (int(s) for s in images.shape[:3])
+    if not 1 <= n <= MESH_MAX_VIEWS:
+        raise UfrError(f"mesh_vertex_colors: {n} views (must be 1 .. {MESH_MAX_VIEWS})")
+    if H < 2 or W < 2 or H * W >= 2 ** 31:
+        raise UfrError(f"mesh_vertex_colors: image {H}x{W} (H, W >= 2, H * W < 2^31)")
+    if depth is not None:
+        pd = _dev(depth, "depth", torch.float32)
+        if tuple(depth.shape) != (n, H, W):
+            raise UfrError(f"depth: expected shape ({n}, {H}, {W}), got {tuple(depth.shape)}")
+    kk = np.ascontiguousarray(np.asarray(k, np.float64))
+    wc = np.ascontiguousarray(np.asarray(w2c, np.float64))
+    cc = np.ascontiguousarray(np.asarray(centre, np.float64))
+    if kk.shape != (n, 3, 3) or wc.shape != (n, 4, 4) or cc.shape != (n, 3):
+        raise UfrError(f"mesh_vertex_colors: k {kk.shape}, w2c {wc.shape}, centre {cc.shape}: expected ({n}, 3, 3), ({n}, 4, 4) "
+                       f"and ({n}, 3)")
+    if not (float(z_min) >= 0.0 and float(z_min) < float("inf")):
+        raise UfrError(f"mesh_vertex_colors: z_min {z_min} (must be >= 0 and finite)")
+    if not (float(depth_tol) >= 0.0 and float(depth_tol) < float("inf")):
+        raise UfrError(f"mesh_vertex_colors: depth_tol {depth_tol} (must be >= 0 and finite)")
+    if not 0.0 <= float(min_cos) <= 1.0:
+        raise UfrError(f"mesh_vertex_colors: min_cos {min_cos} (must be 0 .. 1)")
+    if int(power) != power or not 0 <= int(power) <= MESH_COLOR_MAX_POWER:
+        raise UfrError(f"mesh_vertex_colors: power {power} (an integer in 0 .. {MESH_COLOR_MAX_POWER})")
+    if mode not in MESH_COLOR_MODES:
+        raise UfrError(f"mesh_vertex_colors: mode {mode!r} (one of {sorted(MESH_COLOR_MODES)})")
+    fl = np.ascontiguousarray(np.asarray(fill).reshape(-1))
+    if fl.shape != (3,) or not ((fl >= 0) & (fl <= 255) & (fl == np.rint(fl))).all():
+        raise UfrError(f"mesh_vertex_colors: fill {fill!r} (three integers in 0 .. 255)")
+    fl = np.ascontiguousarray(fl.astype(np.uint8))
+    dev = verts.device
+    colors = torch.empty((V, 3), dtype=torch.uint8, device=dev)
+    used = torch.empty(V, dtype=torch.uint8, device=dev)
+    if V == 0:
+        return colors, used
+    lib = _lib.load()
+    nbytes = lib.ufr_color_vertices_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    dp = C.POINTER(C.c_double)
+    _lib.check(lib.ufr_color_vertices(pv, pn, V, pi, pd, kk.ctypes.data_as(dp), wc.ctypes.data_as(dp), cc.ctypes.data_as(dp), n, H,
+                                          W, float(z_min), float(depth_tol), float(min_cos), int(power), MESH_COLOR_MODES[mode],
+                                          fl.ctypes.data_as(C.POINTER(C.c_uint8)), colors.data_ptr(), used.data_ptr(), ws.data_ptr(),
+                                          nbytes, _stream()), "ufr_color_vertices")
+    return colors, used
+
+
+def mesh_color_fill(faces: torch.Tensor, colors: torch.Tensor, views_used: torch.Tensor, rounds: int):
+    """Up to ``rounds`` rounds of ufr_color_fill_round: a vertex without colour (``views_used`` == 0) takes the mean of
+    its coloured neighbours, a neighbour once per face that shares the edge, rounded half to even; one round reaches one
+    edge further.  ``faces`` (F,3) CUDA int32, ``colors`` (V,3) CUDA uint8, ``views_used`` (V,) CUDA uint8.  Returns
+    ``colors`` (V,3) uint8, ``state`` (V,) uint8 (0: still empty) and the rounds run -- a round that fills nothing is the
+    last, and is counted.  The corner slots are sorted by vertex here, once (stable).  A face index out of range raises.
+    One host read per round, and one for the index check."""
+    pf = _dev(faces, "faces", torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
+    _dev(colors, "colors", torch.uint8)
+    _dev(views_used, "views_used", torch.uint8)
+    V, F = int(views_used.shape[0]), int(faces.shape[0])
+    if tuple(colors.shape) != (V, 3) or views_used.dim() != 1:
+        raise UfrError(f"mesh_color_fill: colors {tuple(colors.shape)}, views_used {tuple(views_used.shape)}: expected (V, 3) and (V,)")
+    rounds = int(rounds)
+    if rounds < 0:
+        raise UfrError(f"mesh_color_fill: rounds {rounds} (must be >= 0)")
+    if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise UfrError(f"mesh_color_fill: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
+    if 3 * F >= 2 ** 31:
+        raise UfrError(f"mesh_color_fill: {F} faces: (2^31 - 1) / 3 or more")
+    dev = colors.device
+    cur, state = colors.clone(), (views_used != 0).to(torch.uint8)
+    if rounds == 0 or V == 0 or F == 0:
+        return cur, state, 0
+    corner = faces.reshape(-1).to(torch.int64)
+    svert, slots = torch.sort(corner, stable=True)
+    slots = slots.contiguous()
+    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=dev)).contiguous()
+    nxt, nstate = torch.empty_like(cur), torch.empty_like(state)
+    filled = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib, run = _lib.load(), 0
+    while run < rounds:
+        filled.zero_()
+        _lib.check(lib.ufr_color_fill_round(pf, V, F, slots.data_ptr(), runs.data_ptr(), cur.data_ptr(), state.data_ptr(),
+                                                 nxt.data_ptr(), nstate.data_ptr(), filled.data_ptr(), _stream()),
+                   "ufr_color_fill_round")
+        cur, nxt, state, nstate = nxt, cur, nstate, state
+        run += 1
+        if int(filled.item()) == 0:
+            break
+    return cur, state, run
+
+
 # ---- a scan loader's per-pixel work (csrc/frame_input.hip; uforecon_amd/dtu_scan.py is the caller)
 def image_resize_u8(images: torch.Tensor, H: int, W: int, clip=(0, 0, 0, 0)) -> torch.Tensor:
     """ufr_image_resize_u8: (n,Hs,Ws,3) CUDA uint8 RGB -> (n,3,Ho,Wo) float32 planes in [0,1]: every image resized to ``H`` x
