@@ -912,6 +912,91 @@ int ufr_color_fill_round(const int32_t* faces, int64_t V, int64_t F, const int64
                               const uint8_t* colors_in, const uint8_t* state_in, uint8_t* colors_out, uint8_t* state_out,
                               int32_t* filled, ufr_stream stream);
 
+/* ---- mesh simplification (ABI 507, additive) -----------------------------------------------------------------
+ * Vertex clustering with quadric placement: the thinning stage of the mesh route, as ufr_points_voxel_mean is the point
+ * route's; the reference leaves it to Open3D and trimesh.  uforecon_amd/simplify_mesh.py is the caller, ops.mesh_simplify
+ * strings the calls together, tests/simplify_ref.py is the numpy statement of every rule below.  Open3D was not compared
+ * against: the rule written here is the rule.  There is no edge-collapse decimation and no topology guarantee (clustering
+ * can pinch a thin part into non-manifold edges); normals are not carried.  Everything is fp64, every product and sum
+ * rounded on its own (no fused multiply-add), sums taken left to right; there is no floating-point atomic, so a rerun gives
+ * the same bits.  All arrays live on the device unless marked HOST.  V, F, the cluster count C: each 1 .. 2^31 - 1.
+ *
+ * Clusters.  With h the cell edge, the caller puts the origin o at min_bound - h / 2, refuses more than 2^21 - 4 cells on
+ *   an axis, takes the keys of ufr_points_cell_keys at cell = h and sorts them with a STABLE sort: exactly the setup of
+ *   ufr_points_voxel_mean, which then gives, per occupied cell in key order, the vertex count, the mean position xm (summed
+ *   in ascending vertex index) and the rounded mean colour.  A cluster's cell (i0, i1, i2) is its key's Morton triple and
+ *   its centre is m_a = o_a + ((double)i_a + 0.5) * h.  Quadrics live in coordinates relative to m, so they stay well scaled.
+ * ufr_simplify_clusters: sorted_keys (V) and order (V) int64 as the stable sort returns them (order[i] = the input index of
+ *   sorted row i).  cluster (V) int32: the cluster of every INPUT vertex = the number of run heads before its row;
+ *   cluster_key (capacity) int64: the key of every cluster.  *total_host = C.  SYNCHRONISES the stream once.
+ * ufr_simplify_face_keys: keys (3F) int64.  With (ca, cb, cc) the clusters of face f's corners: keys[3f] = ca << 32 | f;
+ *   keys[3f+1] = cb << 32 | f if cb != ca; keys[3f+2] = cc << 32 | f if cc != ca and cc != cb; an unused slot (and every
+ *   slot of a face with a corner outside 0 .. V-1) holds 2^63 - 1.  A face with two corners in one cluster so contributes
+ *   once to it.  The caller sorts the keys (one stable sort): every cluster's faces then stand in ascending face index.
+ * ufr_simplify_quadrics: sorted_keys (3F) from above; quadrics (C,10) fp64 and n_faces (C) int32 are zeroed, then the head
+ *   of every run of equal key >> 32 sums its run left to right.  For face f with corner positions pa, pb, pc and the run's
+ *   cluster centre m:  u = pb - pa, v = pc - pa,  n0 = u1*v2 - u2*v1, n1 = u2*v0 - u0*v2, n2 = u0*v1 - u1*v0 (the
+ *   unnormalised normal: area-squared weighting, as in Lindstrom's out-of-core simplification);  r = pa - m,
+ *   d = -((n0*r0 + n1*r1) + n2*r2);  the ten terms, in the order stored:  A00 = n0*n0, A01 = n0*n1, A02 = n0*n2, A11 = n1*n1,
+ *   A12 = n1*n2, A22 = n2*n2, b0 = n0*d, b1 = n1*d, b2 = n2*d, c = d*d.  n_faces = the run's length.
+ * ufr_simplify_place: mean (C,3) = xm; position (C,3) fp64 and placed (C) uint8 out.  placement UFR_SIMPLIFY_MEAN, or a
+ *   cluster with n_faces = 0: position = xm, placed = 0.  UFR_SIMPLIFY_QUADRIC:  xb = xm - m;  w = 2^-10 * ((A00 + A11) + A22);
+ *   A'kk = Akk + w;  b'k = bk - w * xbk;  c' = c + w * ((xb0*xb0 + xb1*xb1) + xb2*xb2): the quadric regularised towards the
+ *   mean.  2^-10 is a stated choice, not a tuned one; it plays the part of Lindstrom's 1e-3 singular-value cut-off, costs no
+ *   rounding, and makes A' positive definite wherever a face contributes, so a planar or crease cluster's minimiser slides
+ *   to the mean along its free directions.  A' x = -b' by cofactors:
+ *     C00 = A'11*A'22 - A12*A12,  C01 = A02*A12 - A01*A'22,  C02 = A01*A12 - A02*A'11,
+ *     C11 = A'00*A'22 - A02*A02,  C12 = A01*A02 - A'00*A12,  C22 = A'00*A'11 - A01*A01,
+ *     det = (A'00*C00 + A01*C01) + A02*C02,  rk = -b'k,
+ *     x0 = ((C00*r0 + C01*r1) + C02*r2) / det,  x1 = ((C01*r0 + C11*r1) + C12*r2) / det,  x2 = ((C02*r0 + C12*r1) + C22*r2) / det.
+ *   E'(y) = (((y0*g0 + y1*g1) + y2*g2) + 2 * ((b'0*y0 + b'1*y1) + b'2*y2)) + c' with g0 = (A'00*y0 + A01*y1) + A02*y2,
+ *   g1 = (A01*y0 + A'11*y1) + A12*y2, g2 = (A02*y0 + A12*y1) + A'22*y2.  x is taken iff x0, x1, x2 are finite, every
+ *   |xk| <= 0.5 * h, and E'(x) <= E'(xb):  position = m + x, placed = 1.  Otherwise position = xm, placed = 0.
+ * ufr_simplify_face_triples: triples (F,3) int32, key_a (F) and key_bc (F) int64.  A face whose corners do not lie in three
+ *   different clusters (or with a corner outside 0 .. V-1) is collapsed: triple (-1,-1,-1), both keys 2^63 - 1.  The others
+ *   are rotated so that the smallest cluster number stands first, (a, b, c), orientation kept: key_a = a, key_bc = b << 32 | c.
+ *   The caller sorts stably by key_bc, then stably by key_a: equal triples then stand together in ascending face index.
+ * ufr_simplify_face_heads: order (F) int64 = the input index of every row after both sorts.  keep (F) uint8, by INPUT index:
+ *   1 for the first row of every run of equal (key_a, key_bc) that is not collapsed, else 0: among faces with the same
+ *   rotated triple the lowest input index survives.  (a,b,c) and (a,c,b) are different triples; both stay.
+ * ufr_simplify_compact_faces: the kept triples in ascending input index (the ordered compaction of marching cubes):
+ *   out_faces (capacity,3) int32 in CLUSTER numbers, face_map (capacity) int32 = the input index of every output face;
+ *   referenced (C) uint8 is zeroed, then set to 1 for every cluster a kept face names.  *total_host = F', which may exceed
+ *   capacity (nothing beyond is written).  SYNCHRONISES the stream once.
+ * ufr_simplify_compact_vertices: the referenced clusters, renumbered in key order: cluster_vertex (C) int32 = the output
+ *   vertex of every cluster or -1; out_verts / out_colors (nullable with colors) / out_placed / out_count (capacity rows)
+ *   = position / colors / placed / count of the referenced clusters; vertex_map (V) int32 = cluster_vertex[cluster[v]];
+ *   faces (n_faces,3) int32 are rewritten IN PLACE from cluster numbers to output vertices (n_faces may be 0, faces then
+ *   nullable).  *total_host = V'.  SYNCHRONISES the stream once.
+ * workspace >= ufr_simplify_workspace_bytes(n) (device) with n >= the call's V, F or C, whichever it scans.
+ * Every argument error (null pointer, a count outside its range, a cell or origin that is not finite or a cell <= 0, an
+ * unknown placement, a negative capacity, a workspace that is too small) is UFR_ERR_ARG (UFR_ERR_WORKSPACE for the
+ * workspace) with the reason in the thread's last-error text; nothing is launched then.                              */
+#define UFR_SIMPLIFY_QUADRIC 0
+#define UFR_SIMPLIFY_MEAN 1
+size_t ufr_simplify_workspace_bytes(int64_t n);
+int ufr_simplify_clusters(const int64_t* sorted_keys, const int64_t* order, int64_t V, int32_t* cluster, int64_t* cluster_key,
+                          int64_t capacity, void* workspace, size_t workspace_bytes, int64_t* total_host, ufr_stream stream);
+int ufr_simplify_face_keys(const int32_t* faces, const int32_t* cluster, int64_t V, int64_t F, int64_t* keys, ufr_stream stream);
+int ufr_simplify_quadrics(const double* verts, const int32_t* faces, const int64_t* cluster_key, int64_t V, int64_t F, int64_t C,
+                          const double* origin, double cell, const int64_t* sorted_keys, double* quadrics, int32_t* n_faces,
+                          ufr_stream stream);
+int ufr_simplify_place(const double* quadrics, const int32_t* n_faces, const double* mean, const int64_t* cluster_key, int64_t C,
+                       const double* origin, double cell, int32_t placement, double* position, uint8_t* placed,
+                       ufr_stream stream);
+int ufr_simplify_face_triples(const int32_t* faces, const int32_t* cluster, int64_t V, int64_t F, int32_t* triples,
+                              int64_t* key_a, int64_t* key_bc, ufr_stream stream);
+int ufr_simplify_face_heads(const int64_t* key_a, const int64_t* key_bc, const int64_t* order, int64_t F, uint8_t* keep,
+                            ufr_stream stream);
+int ufr_simplify_compact_faces(const int32_t* triples, const uint8_t* keep, int64_t F, int64_t C, int32_t* out_faces,
+                               int32_t* face_map, int64_t capacity, uint8_t* referenced, void* workspace,
+                               size_t workspace_bytes, int64_t* total_host, ufr_stream stream);
+int ufr_simplify_compact_vertices(const uint8_t* referenced, int64_t C, const double* position, const uint8_t* colors,
+                                  const uint8_t* placed, const int32_t* count, const int32_t* cluster, int64_t V, int32_t* faces,
+                                  int64_t n_faces, double* out_verts, uint8_t* out_colors, uint8_t* out_placed,
+                                  int32_t* out_count, int64_t capacity, int32_t* cluster_vertex, int32_t* vertex_map,
+                                  void* workspace, size_t workspace_bytes, int64_t* total_host, ufr_stream stream);
+
 /* ---- point-cloud filtering (ABI 507, additive) ----------------------------------------------------------------
  * The cleanup between depth fusion and scoring that an MVS pipeline expects (voxel downsampling, statistical and radius
  * outlier removal, normal estimation); the reference leaves it to Open3D.  uforecon_amd/pcd_filter.py is the caller,

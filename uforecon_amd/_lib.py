@@ -195,6 +195,16 @@ SIGNATURES = {
                                          i32, i32, C.c_double, C.c_double, C.c_double, i32, i32, C.POINTER(C.c_uint8), vp, vp, vp, sz,
                                          vp]),
     "ufr_color_fill_round": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ufr_simplify_workspace_bytes": (sz, [i64]),
+    "ufr_simplify_clusters": (C.c_int, [vp, vp, i64, vp, vp, i64, vp, sz, C.POINTER(i64), vp]),
+    "ufr_simplify_face_keys": (C.c_int, [vp, vp, i64, i64, vp, vp]),
+    "ufr_simplify_quadrics": (C.c_int, [vp, vp, vp, i64, i64, i64, C.POINTER(C.c_double), C.c_double, vp, vp, vp, vp]),
+    "ufr_simplify_place": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(C.c_double), C.c_double, i32, vp, vp, vp]),
+    "ufr_simplify_face_triples": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp]),
+    "ufr_simplify_face_heads": (C.c_int, [vp, vp, vp, i64, vp, vp]),
+    "ufr_simplify_compact_faces": (C.c_int, [vp, vp, i64, i64, vp, vp, i64, vp, vp, sz, C.POINTER(i64), vp]),
+    "ufr_simplify_compact_vertices": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, sz,
+                                                C.POINTER(i64), vp]),
     "ufr_image_resize_u8": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),
     "ufr_pixel_rays": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, vp, vp]),
     "ufr_image_resize_mask_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),

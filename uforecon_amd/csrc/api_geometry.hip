@@ -947,3 +947,158 @@ int ufr_poisson_sample(const double* vol, const int32_t* dims, const double* ori
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ mesh simplification
+namespace {
+
+// every scanning call: [flags per block int64 | block offsets int64 | total int64]
+struct SimplifyWs { long long *block_tot, *block_off, *total; };
+SimplifyWs carve_simplify(Carver& c, long long n) {
+  const size_t blocks = (size_t)simplify_blocks(n);
+  SimplifyWs w;
+  w.block_tot = c.take<long long>(blocks);
+  w.block_off = c.take<long long>(blocks);
+  w.total = c.take<long long>(1);
+  return w;
+}
+
+int simplify_counts_check(const char* who, int64_t V, int64_t F) {
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax, "%s: V %lld, F %lld (each must be 1 .. 2^31 - 1)", who, (long long)V,
+              (long long)F);
+  return UFR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ufr_simplify_workspace_bytes(int64_t n) { return (n >= 1 && n <= kChMax) ? carved_bytes(carve_simplify, (long long)n) : 0; }
+
+int ufr_simplify_clusters(const int64_t* sorted_keys, const int64_t* order, int64_t V, int32_t* cluster, int64_t* cluster_key,
+                          int64_t capacity, void* workspace, size_t workspace_bytes, int64_t* total_host, ufr_stream stream) {
+  const char* who = "ufr_simplify_clusters";
+  UFR_REQUIRE(sorted_keys && order && cluster && cluster_key && workspace && total_host, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax, "%s: V %lld (must be 1 .. 2^31 - 1)", who, (long long)V);
+  UFR_REQUIRE(capacity >= 0, "%s: capacity %lld", who, (long long)capacity);
+  Carver c(workspace);
+  const SimplifyWs w = carve_simplify(c, V);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("simplify_clusters", s, launch_simplify_clusters(reinterpret_cast<const long long*>(sorted_keys),
+      reinterpret_cast<const long long*>(order), V, cluster, reinterpret_cast<long long*>(cluster_key), capacity, w.block_tot,
+      w.block_off, w.total, s));
+  long long tot = 0;
+  UFR_CHECK(read_counts(&tot, w.total, 1, s));
+  *total_host = (int64_t)tot;
+  return UFR_OK;
+}
+
+int ufr_simplify_face_keys(const int32_t* faces, const int32_t* cluster, int64_t V, int64_t F, int64_t* keys, ufr_stream stream) {
+  const char* who = "ufr_simplify_face_keys";
+  UFR_REQUIRE(faces && cluster && keys, "%s: null argument", who);
+  UFR_CHECK(simplify_counts_check(who, V, F));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("simplify_face_keys", s, launch_simplify_face_keys(faces, cluster, V, F, reinterpret_cast<long long*>(keys), s));
+  return UFR_OK;
+}
+
+int ufr_simplify_quadrics(const double* verts, const int32_t* faces, const int64_t* cluster_key, int64_t V, int64_t F, int64_t C,
+                          const double* origin, double cell, const int64_t* sorted_keys, double* quadrics, int32_t* n_faces,
+                          ufr_stream stream) {
+  const char* who = "ufr_simplify_quadrics";
+  UFR_REQUIRE(verts && faces && cluster_key && origin && sorted_keys && quadrics && n_faces, "%s: null argument", who);
+  UFR_CHECK(simplify_counts_check(who, V, F));
+  UFR_REQUIRE(C >= 1 && C <= V, "%s: C %lld (must be 1 .. V)", who, (long long)C);
+  UFR_CHECK(cell_grid_check(who, cell, origin));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("simplify_quadrics", s, launch_simplify_quadrics(verts, faces, reinterpret_cast<const long long*>(cluster_key), V, F, C,
+      origin, cell, reinterpret_cast<const long long*>(sorted_keys), quadrics, n_faces, s));
+  return UFR_OK;
+}
+
+int ufr_simplify_place(const double* quadrics, const int32_t* n_faces, const double* mean, const int64_t* cluster_key, int64_t C,
+                       const double* origin, double cell, int32_t placement, double* position, uint8_t* placed,
+                       ufr_stream stream) {
+  const char* who = "ufr_simplify_place";
+  UFR_REQUIRE(quadrics && n_faces && mean && cluster_key && origin && position && placed, "%s: null argument", who);
+  UFR_REQUIRE(C >= 1 && C <= kChMax, "%s: C %lld (must be 1 .. 2^31 - 1)", who, (long long)C);
+  UFR_CHECK(cell_grid_check(who, cell, origin));
+  UFR_REQUIRE(placement == UFR_SIMPLIFY_QUADRIC || placement == UFR_SIMPLIFY_MEAN, "%s: unknown placement %d", who, placement);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("simplify_place", s, launch_simplify_place(quadrics, n_faces, mean, reinterpret_cast<const long long*>(cluster_key), C,
+      origin, cell, placement, position, placed, s));
+  return UFR_OK;
+}
+
+int ufr_simplify_face_triples(const int32_t* faces, const int32_t* cluster, int64_t V, int64_t F, int32_t* triples,
+                              int64_t* key_a, int64_t* key_bc, ufr_stream stream) {
+  const char* who = "ufr_simplify_face_triples";
+  UFR_REQUIRE(faces && cluster && triples && key_a && key_bc, "%s: null argument", who);
+  UFR_CHECK(simplify_counts_check(who, V, F));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("simplify_face_triples", s, launch_simplify_face_triples(faces, cluster, V, F, triples,
+      reinterpret_cast<long long*>(key_a), reinterpret_cast<long long*>(key_bc), s));
+  return UFR_OK;
+}
+
+int ufr_simplify_face_heads(const int64_t* key_a, const int64_t* key_bc, const int64_t* order, int64_t F, uint8_t* keep,
+                            ufr_stream stream) {
+  const char* who = "ufr_simplify_face_heads";
+  UFR_REQUIRE(key_a && key_bc && order && keep, "%s: null argument", who);
+  UFR_REQUIRE(F >= 1 && F <= kChMax, "%s: F %lld (must be 1 .. 2^31 - 1)", who, (long long)F);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("simplify_face_heads", s, launch_simplify_face_heads(reinterpret_cast<const long long*>(key_a),
+      reinterpret_cast<const long long*>(key_bc), reinterpret_cast<const long long*>(order), F, keep, s));
+  return UFR_OK;
+}
+
+int ufr_simplify_compact_faces(const int32_t* triples, const uint8_t* keep, int64_t F, int64_t C, int32_t* out_faces,
+                               int32_t* face_map, int64_t capacity, uint8_t* referenced, void* workspace,
+                               size_t workspace_bytes, int64_t* total_host, ufr_stream stream) {
+  const char* who = "ufr_simplify_compact_faces";
+  UFR_REQUIRE(triples && keep && referenced && workspace && total_host, "%s: null argument", who);
+  UFR_REQUIRE(F >= 1 && F <= kChMax && C >= 1 && C <= kChMax, "%s: F %lld, C %lld (each must be 1 .. 2^31 - 1)", who, (long long)F,
+              (long long)C);
+  UFR_REQUIRE(capacity >= 0, "%s: capacity %lld", who, (long long)capacity);
+  UFR_REQUIRE(capacity == 0 || (out_faces && face_map), "%s: null argument (an output with capacity %lld)", who, (long long)capacity);
+  Carver c(workspace);
+  const SimplifyWs w = carve_simplify(c, F);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("simplify_compact_faces", s, launch_simplify_compact_faces(triples, keep, F, C, out_faces, face_map, capacity, referenced,
+      w.block_tot, w.block_off, w.total, s));
+  long long tot = 0;
+  UFR_CHECK(read_counts(&tot, w.total, 1, s));
+  *total_host = (int64_t)tot;
+  return UFR_OK;
+}
+
+int ufr_simplify_compact_vertices(const uint8_t* referenced, int64_t C, const double* position, const uint8_t* colors,
+                                  const uint8_t* placed, const int32_t* count, const int32_t* cluster, int64_t V, int32_t* faces,
+                                  int64_t n_faces, double* out_verts, uint8_t* out_colors, uint8_t* out_placed,
+                                  int32_t* out_count, int64_t capacity, int32_t* cluster_vertex, int32_t* vertex_map,
+                                  void* workspace, size_t workspace_bytes, int64_t* total_host, ufr_stream stream) {
+  const char* who = "ufr_simplify_compact_vertices";
+  UFR_REQUIRE(referenced && position && placed && count && cluster && cluster_vertex && vertex_map && workspace && total_host,
+              "%s: null argument", who);
+  UFR_REQUIRE(C >= 1 && C <= kChMax && V >= 1 && V <= kChMax, "%s: C %lld, V %lld (each must be 1 .. 2^31 - 1)", who, (long long)C,
+              (long long)V);
+  UFR_REQUIRE(n_faces >= 0 && n_faces <= kChMax && (n_faces == 0 || faces), "%s: n_faces %lld (must be 0 .. 2^31 - 1, faces given)", who,
+              (long long)n_faces);
+  UFR_REQUIRE(capacity >= 0, "%s: capacity %lld", who, (long long)capacity);
+  UFR_REQUIRE(capacity == 0 || (out_verts && out_placed && out_count && (!colors || out_colors)),
+              "%s: null argument (an output with capacity %lld)", who, (long long)capacity);
+  Carver c(workspace);
+  const SimplifyWs w = carve_simplify(c, C);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("simplify_compact_vertices", s, launch_simplify_compact_vertices(referenced, C, position, colors, placed, count, cluster, V,
+      faces, n_faces, out_verts, out_colors, out_placed, out_count, capacity, cluster_vertex, vertex_map, w.block_tot, w.block_off,
+      w.total, s));
+  long long tot = 0;
+  UFR_CHECK(read_counts(&tot, w.total, 1, s));
+  *total_host = (int64_t)tot;
+  return UFR_OK;
+}
+
+}  // extern "C"

@@ -261,6 +261,32 @@ hipError_t launch_mesh_vertex_colors(const double* verts, const double* normals,
 hipError_t launch_mesh_color_fill_round(const int* faces, long long V, long long F, const long long* slots, const long long* runs,
                                         const unsigned char* colors_in, const unsigned char* state_in, unsigned char* colors_out,
                                         unsigned char* state_out, int* filled, hipStream_t s);
+// mesh_simplify.hip: vertex clustering with quadric placement (see the file header)
+constexpr int kSimplifyThreads = 256;      // items a block owns (ops.SIMPLIFY_BLOCK says the same to the tests)
+long long simplify_blocks(long long n);    // blocks of the scanning kernels: sizes the per-block workspace arrays
+hipError_t launch_simplify_clusters(const long long* keys, const long long* order, long long V, int* cluster,
+                                    long long* cluster_key, long long capacity, long long* block_tot, long long* block_off,
+                                    long long* total, hipStream_t s);
+hipError_t launch_simplify_face_keys(const int* faces, const int* cluster, long long V, long long F, long long* keys, hipStream_t s);
+hipError_t launch_simplify_quadrics(const double* verts, const int* faces, const long long* cluster_key, long long V, long long F,
+                                    long long C, const double* origin, double cell, const long long* sorted_keys,
+                                    double* quadrics, int* n_faces, hipStream_t s);
+hipError_t launch_simplify_place(const double* quadrics, const int* n_faces, const double* mean, const long long* cluster_key,
+                                 long long C, const double* origin, double cell, int placement, double* position,
+                                 unsigned char* placed, hipStream_t s);
+hipError_t launch_simplify_face_triples(const int* faces, const int* cluster, long long V, long long F, int* triples,
+                                        long long* key_a, long long* key_bc, hipStream_t s);
+hipError_t launch_simplify_face_heads(const long long* key_a, const long long* key_bc, const long long* order, long long F,
+                                      unsigned char* keep, hipStream_t s);
+hipError_t launch_simplify_compact_faces(const int* triples, const unsigned char* keep, long long F, long long C, int* out_faces,
+                                         int* face_map, long long capacity, unsigned char* referenced, long long* block_tot,
+                                         long long* block_off, long long* total, hipStream_t s);
+hipError_t launch_simplify_compact_vertices(const unsigned char* referenced, long long C, const double* position,
+                                            const unsigned char* colors, const unsigned char* placed, const int* count,
+                                            const int* cluster, long long V, int* faces, long long n_faces, double* out_verts,
+                                            unsigned char* out_colors, unsigned char* out_placed, int* out_count,
+                                            long long capacity, int* cluster_vertex, int* vertex_map, long long* block_tot,
+                                            long long* block_off, long long* total, hipStream_t s);
 // frame_metrics.hip: the scores and 8-bit previews of a validation frame (see the file header)
 constexpr int kFrameMetricsBlocks = 256;   // most partial rows one frame leaves in the workspace
 hipError_t launch_frame_metrics(const float* rgb_c, const float* rgb_f, const float* rgb_gt, const float* depth_c, const float* depth_f,

@@ -1717,6 +1717,299 @@ def mesh_color_fill(faces: torch.Tensor, colors: torch.Tensor, views_used: torch
     return cur, state, run
 
 
+# ---- mesh simplification (csrc/mesh_simplify.hip; uforecon_amd/simplify_mesh.py is the caller)
+SIMPLIFY_BLOCK = 256             # kSimplifyThreads of csrc/ufr_internal.h: the items one block of a scanning kernel owns
+SIMPLIFY_PLACEMENTS = {"quadric": 0, "mean": 1}   # UFR_SIMPLIFY_QUADRIC / _MEAN
+SIMPLIFY_MAX_CELLS = 2 ** 21 - 4                  # cells on an axis, as voxel_downsample refuses them
+SIMPLIFY_BISECTION_STEPS = 32
+
+
+def _simplify_ws(n: int, device):
+    nbytes = _lib.load().ufr_simplify_workspace_bytes(int(n))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def _origin3(origin):
+    return (C.c_double * 3)(*[float(v) for v in origin])
+
+
+def simplify_clusters(sorted_keys: torch.Tensor, order: torch.Tensor):
+    """ufr_simplify_clusters: ``sorted_keys`` and ``order`` (V,) CUDA int64 as a stable sort of the cell keys returns them.
+    Returns ``cluster`` (V,) int32, the cluster of every input vertex, and ``cluster_key`` (C,) int64.  One synchronisation."""
+    pk, po = _dev(sorted_keys, "sorted_keys", torch.int64), _dev(order, "order", torch.int64)
+    V = int(sorted_keys.shape[0])
+    if sorted_keys.dim() != 1 or tuple(order.shape) != (V,) or not 1 <= V < 2 ** 31:
+        raise UfrError(f"simplify_clusters: sorted_keys {tuple(sorted_keys.shape)}, order {tuple(order.shape)}: expected (V,) twice, "
+                       f"V in 1 .. 2^31 - 1")
+    dev = sorted_keys.device
+    cluster = torch.empty(V, dtype=torch.int32, device=dev)
+    ckey = torch.empty(V, dtype=torch.int64, device=dev)
+    ws, nbytes = _simplify_ws(V, dev)
+    total = C.c_int64(0)
+    _lib.check(_lib.load().ufr_simplify_clusters(pk, po, V, cluster.data_ptr(), ckey.data_ptr(), V, ws.data_ptr(), nbytes,
+                                                 C.byref(total), _stream()), "ufr_simplify_clusters")
+    return cluster, ckey[:int(total.value)].contiguous()
+
+
+def simplify_face_keys(faces: torch.Tensor, cluster: torch.Tensor) -> torch.Tensor:
+    """ufr_simplify_face_keys: (3F,) int64, up to three ``cluster << 32 | face`` rows per face, 2^63 - 1 in the unused slots."""
+    pf, pc = _dev(faces, "faces", torch.int32), _dev(cluster, "cluster", torch.int32)
+    V, F = int(cluster.shape[0]), int(faces.shape[0])
+    keys = torch.empty(3 * F, dtype=torch.int64, device=faces.device)
+    _lib.check(_lib.load().ufr_simplify_face_keys(pf, pc, V, F, keys.data_ptr(), _stream()), "ufr_simplify_face_keys")
+    return keys
+
+
+def simplify_quadrics(verts: torch.Tensor, faces: torch.Tensor, cluster_key: torch.Tensor, origin, cell: float,
+                      sorted_keys: torch.Tensor):
+    """ufr_simplify_quadrics: ``quadrics`` (C,10) float64 and ``n_faces`` (C,) int32, every cluster's ten sums taken over its
+    faces in ascending face index; ``sorted_keys`` (3F,) = the sorted rows of ``simplify_face_keys``."""
+    pv, pf = _points64(verts, "verts"), _dev(faces, "faces", torch.int32)
+    pk, ps = _dev(cluster_key, "cluster_key", torch.int64), _dev(sorted_keys, "sorted_keys", torch.int64)
+    V, F, Cn = int(verts.shape[0]), int(faces.shape[0]), int(cluster_key.shape[0])
+    if tuple(sorted_keys.shape) != (3 * F,):
+        raise UfrError(f"sorted_keys: expected shape ({3 * F},), got {tuple(sorted_keys.shape)}")
+    q = torch.empty((Cn, 10), dtype=torch.float64, device=verts.device)
+    nf = torch.empty(Cn, dtype=torch.int32, device=verts.device)
+    _lib.check(_lib.load().ufr_simplify_quadrics(pv, pf, pk, V, F, Cn, _origin3(origin), float(cell), ps, q.data_ptr(), nf.data_ptr(),
+                                                 _stream()), "ufr_simplify_quadrics")
+    return q, nf
+
+
+def simplify_place(quadrics: torch.Tensor, n_faces: torch.Tensor, mean: torch.Tensor, cluster_key: torch.Tensor, origin, cell: float,
+                   placement: str = "quadric"):
+    """ufr_simplify_place: ``position`` (C,3) float64 and ``placed`` (C,) uint8 (1: the regularised quadric's minimiser was
+    taken, 0: the mean)."""
+    if placement not in SIMPLIFY_PLACEMENTS:
+        raise UfrError(f"simplify_place: placement {placement!r} (one of {sorted(SIMPLIFY_PLACEMENTS)})")
+    pq, pn = _dev(quadrics, "quadrics", torch.float64), _dev(n_faces, "n_faces", torch.int32)
+    pm, pk = _points64(mean, "mean"), _dev(cluster_key, "cluster_key", torch.int64)
+    Cn = int(mean.shape[0])
+    if tuple(quadrics.shape) != (Cn, 10) or tuple(n_faces.shape) != (Cn,) or tuple(cluster_key.shape) != (Cn,):
+        raise UfrError(f"simplify_place: quadrics {tuple(quadrics.shape)}, n_faces {tuple(n_faces.shape)}, cluster_key "
+                       f"{tuple(cluster_key.shape)}: expected ({Cn}, 10), ({Cn},) and ({Cn},)")
+    pos = torch.empty((Cn, 3), dtype=torch.float64, device=mean.device)
+    placed = torch.empty(Cn, dtype=torch.uint8, device=mean.device)
+    _lib.check(_lib.load().ufr_simplify_place(pq, pn, pm, pk, Cn, _origin3(origin), float(cell), SIMPLIFY_PLACEMENTS[placement],
+                                              pos.data_ptr(), placed.data_ptr(), _stream()), "ufr_simplify_place")
+    return pos, placed
+
+
+def simplify_face_triples(faces: torch.Tensor, cluster: torch.Tensor):
+    """ufr_simplify_face_triples: ``triples`` (F,3) int32 in cluster numbers, smallest first ((-1,-1,-1): collapsed), and the
+    two sort keys ``key_a``, ``key_bc`` (F,) int64 (2^63 - 1: collapsed)."""
+    pf, pc = _dev(faces, "faces", torch.int32), _dev(cluster, "cluster", torch.int32)
+    V, F = int(cluster.shape[0]), int(faces.shape[0])
+    dev = faces.device
+    tri = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    ka, kbc = torch.empty(F, dtype=torch.int64, device=dev), torch.empty(F, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().ufr_simplify_face_triples(pf, pc, V, F, tri.data_ptr(), ka.data_ptr(), kbc.data_ptr(), _stream()),
+               "ufr_simplify_face_triples")
+    return tri, ka, kbc
+
+
+def simplify_face_heads(key_a: torch.Tensor, key_bc: torch.Tensor) -> torch.Tensor:
+    """The two stable sorts (by ``key_bc``, then by ``key_a``) and ufr_simplify_face_heads: ``keep`` (F,) uint8 by input index,
+    1 for the lowest input index of every distinct rotated triple."""
+    pa, pb = _dev(key_a, "key_a", torch.int64), _dev(key_bc, "key_bc", torch.int64)
+    F = int(key_a.shape[0])
+    if tuple(key_bc.shape) != (F,):
+        raise UfrError(f"key_bc: expected shape ({F},), got {tuple(key_bc.shape)}")
+    o1 = torch.sort(key_bc, stable=True).indices
+    o2 = torch.sort(key_a[o1], stable=True).indices
+    order = o1[o2].contiguous()
+    keep = torch.empty(F, dtype=torch.uint8, device=key_a.device)
+    _lib.check(_lib.load().ufr_simplify_face_heads(pa, pb, order.data_ptr(), F, keep.data_ptr(), _stream()), "ufr_simplify_face_heads")
+    return keep
+
+
+def simplify_compact_faces(triples: torch.Tensor, keep: torch.Tensor, n_clusters: int):
+    """ufr_simplify_compact_faces: the kept triples in ascending input index: ``faces`` (F',3) int32 in cluster numbers,
+    ``face_map`` (F',) int32, ``referenced`` (C,) uint8.  One synchronisation."""
+    pt, pk = _dev(triples, "triples", torch.int32), _dev(keep, "keep", torch.uint8)
+    F, Cn = int(keep.shape[0]), int(n_clusters)
+    if tuple(triples.shape) != (F, 3):
+        raise UfrError(f"triples: expected shape ({F}, 3), got {tuple(triples.shape)}")
+    dev = triples.device
+    out = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    fmap = torch.empty(F, dtype=torch.int32, device=dev)
+    ref = torch.empty(Cn, dtype=torch.uint8, device=dev)
+    ws, nbytes = _simplify_ws(F, dev)
+    total = C.c_int64(0)
+    _lib.check(_lib.load().ufr_simplify_compact_faces(pt, pk, F, Cn, out.data_ptr(), fmap.data_ptr(), F, ref.data_ptr(), ws.data_ptr(),
+                                                      nbytes, C.byref(total), _stream()), "ufr_simplify_compact_faces")
+    n = int(total.value)
+    return out[:n].contiguous(), fmap[:n].contiguous(), ref
+
+
+def simplify_compact_vertices(referenced: torch.Tensor, position: torch.Tensor, colors: Optional[torch.Tensor], placed: torch.Tensor,
+                              count: torch.Tensor, cluster: torch.Tensor, faces: torch.Tensor):
+    """ufr_simplify_compact_vertices: the referenced clusters renumbered in key order.  ``faces`` (F',3) int32 in cluster
+    numbers is rewritten IN PLACE to output vertices.  Returns ``verts`` (V',3), ``colors`` or None, ``placed``, ``count`` and
+    ``vertex_map`` (V,) int32.  One synchronisation."""
+    pr, pp = _dev(referenced, "referenced", torch.uint8), _points64(position, "position")
+    pc = None if colors is None else _dev(colors, "colors", torch.uint8)
+    ppl, pcn = _dev(placed, "placed", torch.uint8), _dev(count, "count", torch.int32)
+    pcl, pf = _dev(cluster, "cluster", torch.int32), _dev(faces, "faces", torch.int32)
+    Cn, V, Fp = int(referenced.shape[0]), int(cluster.shape[0]), int(faces.shape[0])
+    if tuple(position.shape) != (Cn, 3) or tuple(placed.shape) != (Cn,) or tuple(count.shape) != (Cn,) or (
+            colors is not None and tuple(colors.shape) != (Cn, 3)) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise UfrError(f"simplify_compact_vertices: shapes do not agree with {Cn} clusters")
+    dev = position.device
+    ov = torch.empty((Cn, 3), dtype=torch.float64, device=dev)
+    oc = None if colors is None else torch.empty((Cn, 3), dtype=torch.uint8, device=dev)
+    op = torch.empty(Cn, dtype=torch.uint8, device=dev)
+    on = torch.empty(Cn, dtype=torch.int32, device=dev)
+    cv = torch.empty(Cn, dtype=torch.int32, device=dev)
+    vmap = torch.empty(V, dtype=torch.int32, device=dev)
+    ws, nbytes = _simplify_ws(Cn, dev)
+    total = C.c_int64(0)
+    _lib.check(_lib.load().ufr_simplify_compact_vertices(pr, Cn, pp, pc, ppl, pcn, pcl, V, pf if Fp else None, Fp, ov.data_ptr(),
+                                                         None if oc is None else oc.data_ptr(), op.data_ptr(), on.data_ptr(), Cn,
+                                                         cv.data_ptr(), vmap.data_ptr(), ws.data_ptr(), nbytes, C.byref(total),
+                                                         _stream()), "ufr_simplify_compact_vertices")
+    n = int(total.value)
+    return ov[:n].contiguous(), None if oc is None else oc[:n].contiguous(), op[:n].contiguous(), on[:n].contiguous(), vmap
+
+
+def _simplify_mesh_args(verts, faces, colors, who: str):
+    _points64(verts, "verts")
+    _dev(faces, "faces", torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if F >= 2 ** 31:
+        raise UfrError(f"{who}: {F} faces: 2^31 or more")
+    if colors is not None:
+        _dev(colors, "colors", torch.uint8)
+        if tuple(colors.shape) != (V, 3):
+            raise UfrError(f"colors: expected shape ({V}, 3), got {tuple(colors.shape)}")
+    mn = mx = None
+    if V:
+        mn, mx = _finite_bounds(verts, "verts")
+    if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise UfrError(f"{who}: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
+    return V, F, mn, mx
+
+
+def _simplify_sorted_keys(verts, mn, mx, cell: float, who: str):
+    origin = mn - cell / 2
+    cells = float((torch.floor((mx - origin) / cell) + 1).max())
+    if not cells <= float(SIMPLIFY_MAX_CELLS):
+        raise UfrError(f"{who}: cell {cell} needs {cells:.0f} cells on an axis (at most 2^21 - 4)")
+    origin = origin.tolist()
+    keys, order = torch.sort(cell_keys(verts, origin, cell), stable=True)
+    return origin, keys, order
+
+
+def simplify_count_cells(verts: torch.Tensor, cell: float, bounds=None) -> int:
+    """The number of occupied cells of the clustering grid at ``cell``: the keys, one sort, and the run-head count of
+    ufr_points_voxel_mean (capacity 0: nothing is summed).  One synchronisation."""
+    _points64(verts, "verts")
+    mn, mx = bounds if bounds is not None else _finite_bounds(verts, "verts")
+    _, keys, _ = _simplify_sorted_keys(verts, mn, mx, float(cell), "simplify_count_cells")
+    V = int(verts.shape[0])
+    lib = _lib.load()
+    nbytes = lib.ufr_points_voxel_mean_workspace_bytes(V)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
+    total = C.c_int64(0)
+    _lib.check(lib.ufr_points_voxel_mean(verts.data_ptr(), keys.data_ptr(), V, None, None, None, None, None, None, 0, ws.data_ptr(),
+                                         nbytes, C.byref(total), _stream()), "ufr_points_voxel_mean")
+    return int(total.value)
+
+
+def simplify_target_cell(verts: torch.Tensor, target_vertices: int, bounds=None) -> float:
+    """The cell edge at which the clustering grid has at most ``target_vertices`` occupied cells: a geometric bisection of
+    exactly 32 steps between ``max_extent * 2^-20`` and ``2 * diagonal`` (one cell holds everything there), ``mid = sqrt(lo *
+    hi)``, ``hi = mid`` when the count at ``mid`` is <= the target, else ``lo = mid``; the result is ``hi``."""
+    import math
+
+    N = int(target_vertices)
+    if N < 1:
+        raise UfrError(f"simplify_target_cell: target_vertices {target_vertices} (must be >= 1)")
+    _points64(verts, "verts")
+    if int(verts.shape[0]) == 0:
+        raise UfrError("simplify_target_cell: no vertices")
+    mn, mx = bounds if bounds is not None else _finite_bounds(verts, "verts")
+    e = (mx - mn).tolist()
+    lo, hi = max(e) * 2.0 ** -20, 2.0 * math.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])
+    if not (lo > 0.0 and hi < float("inf")):
+        raise UfrError(f"simplify_target_cell: the vertices span {e}: no extent to divide")
+    for _ in range(SIMPLIFY_BISECTION_STEPS):
+        mid = math.sqrt(lo * hi)
+        if simplify_count_cells(verts, mid, (mn, mx)) <= N:
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+def mesh_simplify(verts: torch.Tensor, faces: torch.Tensor, colors: Optional[torch.Tensor] = None, cell: Optional[float] = None,
+                  target_vertices: Optional[int] = None, placement: str = "quadric"):
+    """Vertex clustering with quadric placement (include/ufr.h, "mesh simplification", states every rule).  ``verts`` (V,3)
+    CUDA float64, ``faces`` (F,3) CUDA int32, ``colors`` (V,3) CUDA uint8 or None; exactly one of ``cell`` (> 0) and
+    ``target_vertices``; ``placement`` "quadric" or "mean".  Returns a dict: ``verts`` (V',3) float64, ``faces`` (F',3) int32,
+    ``colors`` (V',3) uint8 or None, ``vertex_map`` (V,) int32 (the output vertex of every input vertex or -1), ``face_map``
+    (F',) int32 (the input index of every output face), ``placed`` (V',) uint8 (1: the quadric's minimiser, 0: the mean),
+    ``count`` (V',) int32 (input vertices per output vertex), ``cell`` (0.0: ``target_vertices`` >= V, the mesh came back
+    unchanged), and the counts ``clusters``, ``collapsed_faces``, ``duplicate_faces``.  A vertex that is not finite, a face index
+    outside 0 .. V-1, a cell that is not positive and finite, wrong dtypes or shapes raise UfrError before any kernel of the
+    library runs."""
+    if placement not in SIMPLIFY_PLACEMENTS:
+        raise UfrError(f"mesh_simplify: placement {placement!r} (one of {sorted(SIMPLIFY_PLACEMENTS)})")
+    if (cell is None) == (target_vertices is None):
+        raise UfrError("mesh_simplify: give exactly one of cell and target_vertices")
+    if cell is not None and not (float(cell) > 0.0 and float(cell) < float("inf")):
+        raise UfrError(f"mesh_simplify: cell {cell} (must be positive and finite)")
+    if target_vertices is not None and (int(target_vertices) != target_vertices or int(target_vertices) < 1):
+        raise UfrError(f"mesh_simplify: target_vertices {target_vertices} (an integer >= 1)")
+    V, F, mn, mx = _simplify_mesh_args(verts, faces, colors, "mesh_simplify")
+    dev = verts.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    if target_vertices is not None and V <= int(target_vertices):
+        return dict(verts=verts.clone(), faces=faces.clone(), colors=None if colors is None else colors.clone(),
+                    vertex_map=torch.arange(V, **i32), face_map=torch.arange(F, **i32),
+                    placed=torch.zeros(V, dtype=torch.uint8, device=dev), count=torch.ones(V, **i32), cell=0.0, clusters=V,
+                    collapsed_faces=0, duplicate_faces=0)
+    cell = float(cell) if cell is not None else simplify_target_cell(verts, int(target_vertices), (mn, mx))
+    empty = dict(verts=verts.new_zeros((0, 3)), faces=torch.zeros((0, 3), **i32),
+                 colors=None if colors is None else colors.new_zeros((0, 3)), vertex_map=torch.full((V,), -1, **i32),
+                 face_map=torch.zeros(0, **i32), placed=torch.zeros(0, dtype=torch.uint8, device=dev), count=torch.zeros(0, **i32),
+                 cell=cell, clusters=0, collapsed_faces=F, duplicate_faces=0)
+    if V == 0 or F == 0:
+        return empty
+    origin, keys, order = _simplify_sorted_keys(verts, mn, mx, cell, "mesh_simplify")
+    cluster, ckey = simplify_clusters(keys, order)
+    Cn = int(ckey.shape[0])
+    # the count, the mean and the rounded mean colour of every cluster: the voxel mean of the sorted vertices
+    lib = _lib.load()
+    pts = verts[order].contiguous()
+    col = None if colors is None else colors[order].contiguous()
+    mean = torch.empty((Cn, 3), dtype=torch.float64, device=dev)
+    ccol = None if col is None else torch.empty((Cn, 3), dtype=torch.uint8, device=dev)
+    count = torch.empty(Cn, **i32)
+    nbytes = lib.ufr_points_voxel_mean_workspace_bytes(V)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    total = C.c_int64(0)
+    _lib.check(lib.ufr_points_voxel_mean(pts.data_ptr(), keys.data_ptr(), V, None if col is None else col.data_ptr(), None,
+                                         mean.data_ptr(), None if ccol is None else ccol.data_ptr(), None, count.data_ptr(), Cn,
+                                         ws.data_ptr(), nbytes, C.byref(total), _stream()), "ufr_points_voxel_mean")
+    if int(total.value) != Cn:
+        raise UfrError(f"mesh_simplify: {int(total.value)} voxel means for {Cn} clusters")
+    fkeys = torch.sort(simplify_face_keys(faces, cluster), stable=True).values
+    quadrics, n_faces = simplify_quadrics(verts, faces, ckey, origin, cell, fkeys)
+    position, placed = simplify_place(quadrics, n_faces, mean, ckey, origin, cell, placement)
+    triples, key_a, key_bc = simplify_face_triples(faces, cluster)
+    keep = simplify_face_heads(key_a, key_bc)
+    out_faces, face_map, referenced = simplify_compact_faces(triples, keep, Cn)
+    out_verts, out_colors, out_placed, out_count, vertex_map = simplify_compact_vertices(referenced, position, ccol, placed, count,
+                                                                                         cluster, out_faces)
+    collapsed = int((key_a == 2 ** 63 - 1).sum())
+    return dict(verts=out_verts, faces=out_faces, colors=out_colors, vertex_map=vertex_map, face_map=face_map, placed=out_placed,
+                count=out_count, cell=cell, clusters=Cn, collapsed_faces=collapsed,
+                duplicate_faces=F - collapsed - int(out_faces.shape[0]))
+
+
 # ---- a scan loader's per-pixel work (csrc/frame_input.hip; uforecon_amd/dtu_scan.py is the caller)
 def image_resize_u8(images: torch.Tensor, H: int, W: int, clip=(0, 0, 0, 0)) -> torch.Tensor:
     """ufr_image_resize_u8: (n,Hs,Ws,3) CUDA uint8 RGB -> (n,3,Ho,Wo) float32 planes in [0,1]: every image resized to ``H`` x
