@@ -912,6 +912,57 @@ int ufr_color_fill_round(const int32_t* faces, int64_t V, int64_t F, const int64
                               const uint8_t* colors_in, const uint8_t* state_in, uint8_t* colors_out, uint8_t* state_out,
                               int32_t* filled, ufr_stream stream);
 
+/* ---- mesh smoothing (ABI 507, additive) ------------------------------------------------------------------------
+ * Laplacian and Taubin smoothing with uniform or cotangent weights: the denoising stage of the mesh route, between cleaning
+ * and simplification; the reference leaves it to Open3D and trimesh.  uforecon_amd/smooth_mesh.py is the caller,
+ * ops.mesh_smooth strings the calls together, tests/smooth_ref.py is the numpy statement of every rule below.  Open3D was
+ * not compared against: the rule written here is the rule.  There is no bilateral or feature-preserving filter.  Only vertex
+ * positions change.  Everything is fp64, every product, quotient, square root and sum rounded on its own (no fused
+ * multiply-add), sums taken left to right; there is no floating-point atomic, so a rerun gives the same bits.  All arrays
+ * live on the device unless marked HOST.  V: 1 .. 2^31 - 1, F: 1 .. (2^31 - 1) / 3.
+ *
+ * Rows.  Corner slot s = 3f + e names the vertex faces[f][e].  sorted_slots (3F) and run_starts (V+1) int64 are those of
+ *   ufr_raster_vertex_normals: the slots sorted by the vertex they name with one STABLE sort, and where every vertex's run
+ *   starts.  Row i is sorted slot i; vertex v's rows run_starts[v] .. run_starts[v+1] - 1 are its corners in ascending s.  A row
+ *   in face f at corner e names the two other corners a = faces[f][(e+1)%3], b = faces[f][(e+2)%3].  A face that names a
+ *   vertex twice, or a vertex outside 0 .. V-1, is dead: its three rows contribute nothing anywhere.
+ * Weights (wa, wb) of a row.  UFR_SMOOTH_UNIFORM: (1, 1) -- on a closed manifold the umbrella operator with every neighbour
+ *   counted twice.  UFR_SMOOTH_COTANGENT, from the positions p given to ufr_smooth_rows and fixed for all steps: with
+ *   (c0, c1, c2) the face's corners in its own order, u = p[c1] - p[c0], t = p[c2] - p[c0], n0 = u1*t2 - u2*t1,
+ *   n1 = u2*t0 - u0*t2, n2 = u0*t1 - u1*t0, nf = sqrt((n0*n0 + n1*n1) + n2*n2) -- once per face, the same for its three rows;
+ *   a face with nf = 0 or nf not finite is dead in this mode.  With x.y = (x0*y0 + x1*y1) + x2*y2 and v the row's vertex:
+ *   wa = clamp(((p[v] - p[b]).(p[a] - p[b])) / nf), the cotangent of the angle at b, and wb = clamp(((p[v] - p[a]).(p[b] -
+ *   p[a])) / nf), the cotangent at a; clamp(w) = 0 unless w > 0 (so for a NaN too), then 64 if w > 64.  The bounds are
+ *   derived, not tuned: a negative weight (an obtuse angle) can flip a triangle, and 64 is the cotangent of a sliver angle
+ *   under 0.9 degrees.
+ * Border.  border (V) uint8 = 1 iff some neighbour stands in the vertex's live rows a number of times other than 2 (an open
+ *   edge, a non-manifold edge), else 0; a vertex without live rows gets 0.
+ * ufr_smooth_rows: writes, into the workspace, every row's (a, b) as int32 -- (-1, -1) for a dead row -- and, for
+ *   cotangent weights, its (wa, wb); then border.  Two launches, no synchronisation.
+ * ufr_smooth_steps: n_steps Jacobi steps over the rows a ufr_smooth_rows call with the same V, F, weights and
+ *   workspace left; factors (n_steps) HOST fp64, all finite.  Step i reads pos_a and writes pos_b when i is even, reads pos_b
+ *   and writes pos_a when i is odd: the caller puts the positions into pos_a (V,3) and finds the result in pos_a when n_steps
+ *   is even, in pos_b (V,3) when it is odd.  One step with factor t, for every vertex v with previous position p:
+ *     num_k = 0, den = 0; per row in order:  num_k = num_k + (wa * (p[a]_k - p[v]_k) + wb * (p[b]_k - p[v]_k))  for k = 0, 1, 2,
+ *     den = den + (wa + wb);  then  p'[v]_k = p[v]_k + (t * num_k) / den  when den > 0 and v is not held,
+ *   else p'[v] = p[v], bit for bit.  v is held when border is given and border[v] != 0 (a null border: the border moves like
+ *   the rest) or pinned (V, uint8, nullable) is given and pinned[v] != 0.  Laplacian smoothing is n steps with factor lam;
+ *   Taubin smoothing alternates lam and mu < -lam; the caller writes the factors.  All steps are issued from this one call and
+ *   the host reads nothing between them.  Does not synchronise.
+ * workspace >= ufr_smooth_workspace_bytes (device; 8 bytes a row, 24 with cotangent weights; 0 for arguments out of
+ * range).  Every argument error (null pointer, a count out of range, unknown weights, a factor that is not finite, pos_a ==
+ * pos_b, a workspace that is too small) is UFR_ERR_ARG (UFR_ERR_WORKSPACE for the workspace) with the reason in the thread's
+ * last-error text; nothing is launched then.                                                                           */
+#define UFR_SMOOTH_UNIFORM 0
+#define UFR_SMOOTH_COTANGENT 1
+size_t ufr_smooth_workspace_bytes(int64_t V, int64_t F, int32_t weights);
+int ufr_smooth_rows(const double* verts, const int32_t* faces, int64_t V, int64_t F, const int64_t* sorted_slots,
+                         const int64_t* run_starts, int32_t weights, uint8_t* border, void* workspace, size_t workspace_bytes,
+                         ufr_stream stream);
+int ufr_smooth_steps(int64_t V, int64_t F, const int64_t* run_starts, int32_t weights, const uint8_t* border,
+                          const uint8_t* pinned, const double* factors, int32_t n_steps, double* pos_a, double* pos_b,
+                          const void* workspace, size_t workspace_bytes, ufr_stream stream);
+
 /* ---- mesh simplification (ABI 507, additive) -----------------------------------------------------------------
  * Vertex clustering with quadric placement: the thinning stage of the mesh route, as ufr_points_voxel_mean is the point
  * route's; the reference leaves it to Open3D and trimesh.  uforecon_amd/simplify_mesh.py is the caller, ops.mesh_simplify

@@ -1102,3 +1102,69 @@ int ufr_simplify_compact_vertices(const uint8_t* referenced, int64_t C, const do
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ mesh smoothing
+namespace {
+
+// [neighbour pairs int32 (3F,2) | weight pairs fp64 (3F,2), cotangent weights only], both in row order
+struct SmoothWs { int* nbr; double* wgt; };
+SmoothWs carve_mesh_smooth(Carver& c, long long F, int weights) {
+  SmoothWs w;
+  w.nbr = c.take<int>((size_t)(6 * F));
+  w.wgt = weights == UFR_SMOOTH_COTANGENT ? c.take<double>((size_t)(6 * F)) : nullptr;
+  return w;
+}
+
+int smooth_check(const char* who, int64_t V, int64_t F, int32_t weights) {
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax / 3, "%s: V %lld, F %lld (V must be 1 .. 2^31 - 1, F 1 .. (2^31 - 1) / 3)",
+              who, (long long)V, (long long)F);
+  UFR_REQUIRE(weights == UFR_SMOOTH_UNIFORM || weights == UFR_SMOOTH_COTANGENT, "%s: unknown weights %d", who, weights);
+  return UFR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ufr_smooth_workspace_bytes(int64_t V, int64_t F, int32_t weights) {
+  if (V < 1 || V > kChMax || F < 1 || F > kChMax / 3 || (weights != UFR_SMOOTH_UNIFORM && weights != UFR_SMOOTH_COTANGENT)) return 0;
+  return carved_bytes(carve_mesh_smooth, (long long)F, (int)weights);
+}
+
+int ufr_smooth_rows(const double* verts, const int32_t* faces, int64_t V, int64_t F, const int64_t* sorted_slots,
+                         const int64_t* run_starts, int32_t weights, uint8_t* border, void* workspace, size_t workspace_bytes,
+                         ufr_stream stream) {
+  const char* who = "ufr_smooth_rows";
+  UFR_REQUIRE(verts && faces && sorted_slots && run_starts && border && workspace, "%s: null argument", who);
+  UFR_CHECK(smooth_check(who, V, F, weights));
+  Carver c(workspace);
+  const SmoothWs w = carve_mesh_smooth(c, F, weights);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_smooth_rows", s, launch_mesh_smooth_rows(verts, faces, V, F, reinterpret_cast<const long long*>(sorted_slots),
+      weights == UFR_SMOOTH_COTANGENT, w.nbr, w.wgt, s));
+  UFR_TIMED("mesh_smooth_border", s, launch_mesh_smooth_border(V, F, reinterpret_cast<const long long*>(run_starts), w.nbr, border, s));
+  return UFR_OK;
+}
+
+int ufr_smooth_steps(int64_t V, int64_t F, const int64_t* run_starts, int32_t weights, const uint8_t* border,
+                          const uint8_t* pinned, const double* factors, int32_t n_steps, double* pos_a, double* pos_b,
+                          const void* workspace, size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_smooth_steps";
+  UFR_REQUIRE(run_starts && pos_a && pos_b && workspace && (factors || n_steps == 0), "%s: null argument", who);
+  UFR_REQUIRE(pos_a != pos_b, "%s: pos_a and pos_b are one buffer", who);
+  UFR_CHECK(smooth_check(who, V, F, weights));
+  UFR_REQUIRE(n_steps >= 0, "%s: n_steps %d (must be >= 0)", who, n_steps);
+  for (int i = 0; i < n_steps; ++i)
+    UFR_REQUIRE(std::isfinite(factors[i]), "%s: factor %d is %g (must be finite)", who, i, factors[i]);
+  Carver c(const_cast<void*>(workspace));
+  const SmoothWs w = carve_mesh_smooth(c, F, weights);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i = 0; i < n_steps; ++i)
+    UFR_TIMED("mesh_smooth_step", s, launch_mesh_smooth_step(V, F, reinterpret_cast<const long long*>(run_starts), w.nbr, w.wgt, border,
+        pinned, factors[i], (i & 1) ? pos_b : pos_a, (i & 1) ? pos_a : pos_b, s));
+  return UFR_OK;
+}
+
+}  // extern "C"

@@ -287,6 +287,16 @@ hipError_t launch_simplify_compact_vertices(const unsigned char* referenced, lon
                                             unsigned char* out_colors, unsigned char* out_placed, int* out_count,
                                             long long capacity, int* cluster_vertex, int* vertex_map, long long* block_tot,
                                             long long* block_off, long long* total, hipStream_t s);
+// mesh_smooth.hip: Laplacian and Taubin smoothing with uniform or cotangent weights (see the file header)
+constexpr int kSmoothThreads = 256;        // rows or vertices a block owns (ops.SMOOTH_BLOCK says the same to the tests)
+constexpr int kSmoothChunk = 1024;         // rows a block of the step stages in LDS at a time (ops.SMOOTH_CHUNK)
+hipError_t launch_mesh_smooth_rows(const double* verts, const int* faces, long long V, long long F, const long long* slots,
+                                   int cotangent, int* nbr, double* wgt, hipStream_t s);
+hipError_t launch_mesh_smooth_border(long long V, long long F, const long long* runs, const int* nbr, unsigned char* border,
+                                     hipStream_t s);
+hipError_t launch_mesh_smooth_step(long long V, long long F, const long long* runs, const int* nbr, const double* wgt,
+                                   const unsigned char* border, const unsigned char* pinned, double t, const double* in,
+                                   double* out, hipStream_t s);
 // frame_metrics.hip: the scores and 8-bit previews of a validation frame (see the file header)
 constexpr int kFrameMetricsBlocks = 256;   // most partial rows one frame leaves in the workspace
 hipError_t launch_frame_metrics(const float* rgb_c, const float* rgb_f, const float* rgb_gt, const float* depth_c, const float* depth_f,

@@ -2010,6 +2010,90 @@ def mesh_simplify(verts: torch.Tensor, faces: torch.Tensor, colors: Optional[tor
                 duplicate_faces=F - collapsed - int(out_faces.shape[0]))
 
 
+# ---- mesh smoothing (csrc/mesh_smooth.hip; uforecon_amd/smooth_mesh.py is the caller)
+SMOOTH_BLOCK = 256                                  # kSmoothThreads of csrc/ufr_internal.h: the rows or vertices one block owns
+SMOOTH_CHUNK = 1024                                 # kSmoothChunk: the rows a block of the step stages in LDS at a time
+SMOOTH_WEIGHTS = {"uniform": 0, "cotangent": 1}     # UFR_SMOOTH_UNIFORM / _COTANGENT
+SMOOTH_METHODS = ("taubin", "laplacian")
+SMOOTH_BOUNDARIES = ("fixed", "free")
+SMOOTH_PASS_BAND = 0.1                              # Taubin's k_pb: the default mu is 1 / (k_pb - 1 / lam)
+
+
+def smooth_factors(method: str = "taubin", iterations: int = 10, lam: float = 0.5, mu: Optional[float] = None):
+    """The step factors of a smoothing call, a list of floats: ``iterations`` times ``lam`` ("laplacian") or ``lam, mu``
+    ("taubin"; ``mu`` None: ``1 / (0.1 - 1 / lam)``).  Raises UfrError with one line unless ``0 < lam <= 1``, ``mu < -lam``
+    and ``iterations`` is an integer >= 0."""
+    if method not in SMOOTH_METHODS:
+        raise UfrError(f"mesh_smooth: method {method!r} (one of {sorted(SMOOTH_METHODS)})")
+    if isinstance(iterations, bool) or int(iterations) != iterations or int(iterations) < 0:
+        raise UfrError(f"mesh_smooth: iterations {iterations} (an integer >= 0)")
+    lam = float(lam)
+    if not 0.0 < lam <= 1.0:
+        raise UfrError(f"mesh_smooth: lam {lam} (must be in (0, 1])")
+    if method == "laplacian":
+        return [lam] * int(iterations)
+    mu = 1.0 / (SMOOTH_PASS_BAND - 1.0 / lam) if mu is None else float(mu)
+    if not (mu < -lam and mu > float("-inf")):
+        raise UfrError(f"mesh_smooth: mu {mu} (must be finite and below -lam = {-lam})")
+    return [lam, mu] * int(iterations)
+
+
+def mesh_smooth(verts: torch.Tensor, faces: torch.Tensor, method: str = "taubin", weights: str = "cotangent", iterations: int = 10,
+                lam: float = 0.5, mu: Optional[float] = None, boundary: str = "fixed", pinned: Optional[torch.Tensor] = None):
+    """Laplacian or Taubin smoothing of the vertex positions (include/ufr.h, "mesh smoothing", states every rule).  ``verts``
+    (V,3) CUDA float64, ``faces`` (F,3) CUDA int32; ``method`` "taubin" (every iteration one step with ``lam``, then one with
+    ``mu``) or "laplacian" (``iterations`` steps with ``lam``); ``weights`` "cotangent" (from the input positions, clamped to 0
+    .. 64) or "uniform"; ``boundary`` "fixed" (border vertices stay) or "free"; ``pinned`` (V,) CUDA uint8 or None: further
+    vertices that stay.  Returns a dict: ``verts`` (V,3) float64 (a new tensor; the input's bits when nothing moves) and
+    ``border`` (V,) uint8.  The corner slots are sorted by vertex here, once (stable); all steps go out in one library call.
+    A face index outside 0 .. V-1, ``lam`` outside (0, 1], ``mu`` >= -``lam``, a negative ``iterations``, wrong dtypes or
+    shapes raise UfrError before any kernel of the library runs.  One host synchronisation (the index check)."""
+    if weights not in SMOOTH_WEIGHTS:
+        raise UfrError(f"mesh_smooth: weights {weights!r} (one of {sorted(SMOOTH_WEIGHTS)})")
+    if boundary not in SMOOTH_BOUNDARIES:
+        raise UfrError(f"mesh_smooth: boundary {boundary!r} (one of {sorted(SMOOTH_BOUNDARIES)})")
+    factors = smooth_factors(method, iterations, lam, mu)
+    _points64(verts, "verts")
+    _dev(faces, "faces", torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if pinned is not None:
+        _dev(pinned, "pinned", torch.uint8)
+        if tuple(pinned.shape) != (V,):
+            raise UfrError(f"pinned: expected shape ({V},), got {tuple(pinned.shape)}")
+    if 3 * F >= 2 ** 31:
+        raise UfrError(f"mesh_smooth: {F} faces: (2^31 - 1) / 3 or more")
+    if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise UfrError(f"mesh_smooth: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
+    dev = verts.device
+    border = torch.zeros(V, dtype=torch.uint8, device=dev)
+    pos_a = verts.clone()
+    if V == 0 or F == 0:
+        return dict(verts=pos_a, border=border)
+    mode = SMOOTH_WEIGHTS[weights]
+    corner = faces.reshape(-1).to(torch.int64)
+    svert, slots = torch.sort(corner, stable=True)
+    slots = slots.contiguous()
+    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=dev)).contiguous()
+    lib = _lib.load()
+    nbytes = lib.ufr_smooth_workspace_bytes(V, F, mode)
+    if nbytes == 0:
+        raise UfrError(f"mesh_smooth: V {V}, F {F} unsupported")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.ufr_smooth_rows(verts.data_ptr(), faces.data_ptr(), V, F, slots.data_ptr(), runs.data_ptr(), mode,
+                                        border.data_ptr(), ws.data_ptr(), nbytes, _stream()), "ufr_smooth_rows")
+    n = len(factors)
+    if n == 0:
+        return dict(verts=pos_a, border=border)
+    pos_b = torch.empty_like(pos_a)
+    _lib.check(lib.ufr_smooth_steps(V, F, runs.data_ptr(), mode, border.data_ptr() if boundary == "fixed" else None,
+                                         None if pinned is None else pinned.data_ptr(), (C.c_double * n)(*factors), n,
+                                         pos_a.data_ptr(), pos_b.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+               "ufr_smooth_steps")
+    return dict(verts=pos_a if n % 2 == 0 else pos_b, border=border)
+
+
 # ---- a scan loader's per-pixel work (csrc/frame_input.hip; uforecon_amd/dtu_scan.py is the caller)
 def image_resize_u8(images: torch.Tensor, H: int, W: int, clip=(0, 0, 0, 0)) -> torch.Tensor:
     """ufr_image_resize_u8: (n,Hs,Ws,3) CUDA uint8 RGB -> (n,3,Ho,Wo) float32 planes in [0,1]: every image resized to ``H`` x
