@@ -916,7 +916,7 @@ int ufr_color_fill_round(const int32_t* faces, int64_t V, int64_t F, const int64
  * Laplacian and Taubin smoothing with uniform or cotangent weights: the denoising stage of the mesh route, between cleaning
  * and simplification; the reference leaves it to Open3D and trimesh.  uforecon_amd/smooth_mesh.py is the caller,
  * ops.mesh_smooth strings the calls together, tests/smooth_ref.py is the numpy statement of every rule below.  Open3D was
- * not compared against: the rule written here is the rule.  There is no bilateral or feature-preserving filter.  Only vertex
+ * not compared against: the rule written here is the rule.  The feature-preserving filter is mesh denoising, below.  Only vertex
  * positions change.  Everything is fp64, every product, quotient, square root and sum rounded on its own (no fused
  * multiply-add), sums taken left to right; there is no floating-point atomic, so a rerun gives the same bits.  All arrays
  * live on the device unless marked HOST.  V: 1 .. 2^31 - 1, F: 1 .. (2^31 - 1) / 3.
@@ -962,6 +962,63 @@ int ufr_smooth_rows(const double* verts, const int32_t* faces, int64_t V, int64_
 int ufr_smooth_steps(int64_t V, int64_t F, const int64_t* run_starts, int32_t weights, const uint8_t* border,
                           const uint8_t* pinned, const double* factors, int32_t n_steps, double* pos_a, double* pos_b,
                           const void* workspace, size_t workspace_bytes, ufr_stream stream);
+
+/* ---- mesh denoising (ABI 507, additive) ------------------------------------------------------------------------
+ * Feature-preserving denoising: the local iterative bilateral normal filter of Zheng et al. 2011 ("Bilateral normal filtering
+ * for mesh denoising") followed by the vertex update of Sun et al. 2007 -- a sibling of mesh smoothing, which rounds a crease
+ * like noise.  uforecon_amd/denoise_mesh.py is the caller, ops.mesh_denoise strings the calls together, tests/denoise_ref.py is
+ * the numpy statement of every rule below.  Open3D and MeshLab were not compared against: the rule written here is the rule.
+ * Only vertex positions change.  Everything is fp64, every product, quotient, square root and sum rounded on its own (no
+ * fused multiply-add), sums taken left to right in the order stated; there is no floating-point atomic, so a rerun gives the
+ * same bits.  dot3(x, y) = (x0*y0 + x1*y1) + x2*y2.  All arrays live on the device unless marked HOST.  V: 1 .. 2^31 - 1,
+ * F: 1 .. (2^31 - 1) / 3.  sorted_slots (3F), run_starts (V+1) and "rows" are those of mesh smoothing.
+ *
+ * Face records, from the positions p given to ufr_denoise_faces and fixed for all steps.  With (c0, c1, c2) the face's
+ *   corners in its own order, u = p[c1] - p[c0], t = p[c2] - p[c0], m0 = u1*t2 - u2*t1, m1 = u2*t0 - u0*t2,
+ *   m2 = u0*t1 - u1*t0, nf = sqrt(dot3(m, m)): the face is LIVE when its three indices are in 0 .. V-1 and distinct and nf is
+ *   finite and above 0.  A live face has the unit normal n = m / nf (three divisions), the area A = 0.5 * nf and the centroid
+ *   c_k = ((p[c0]_k + p[c1]_k) + p[c2]_k) / 3.0.  A dead face has zeros for all three, is nobody's neighbour and is never filtered.
+ * Neighbourhood of a live face f, in this order: f itself; then, for corner e = 0, 1, 2, the rows of vertex faces[f][e] in
+ *   ascending slot, each giving g = slot / 3, skipped when g == f, when g is dead, or when g names faces[f][e'] for some
+ *   e' < e (a face across an edge counts once, at the first corner that reaches it).
+ * Weight kernel k(u): x = 1 - u / 256; 0 when !(x > 0) (so from u = 256 on, and for a NaN); otherwise x squared eight times,
+ *   (1 - u/256)^256.  It stands in for exp(-u) -- the largest difference is 1.06e-3, at u = 2 -- without a transcendental call.
+ * One normal step (Jacobi: every read from the previous normals).  acc = 0; for g over the neighbourhood in order:
+ *     dc = c_g - c_f, dn = n_g - n_f, w = (A_g * k(dot3(dc, dc) / two_ss)) * k(dot3(dn, dn) / two_rr),
+ *     acc_k = acc_k + w * n_g[k];
+ *   L = sqrt(dot3(acc, acc)); the next normal is acc / L (three divisions) when L is finite and above 0, else the previous
+ *   normal, bit for bit.  two_ss = 2.0 * (sigma_s * sigma_s) and two_rr = 2.0 * (sigma_r * sigma_r) are computed by the caller.
+ * One vertex step (Jacobi over positions q, the filtered normals fixed), for a vertex v that is not held: s = 0, cnt = 0;
+ *   per row of v in ascending slot whose face g is live, with (a, b, c) g's corners in its own order:
+ *     cg_k = ((q[a]_k + q[b]_k) + q[c]_k) / 3.0, d = dot3(cg - q[v], n_g), s_k = s_k + n_g[k] * d, cnt = cnt + 1;
+ *   q'[v]_k = q[v]_k + s_k / (double)cnt when cnt > 0, else q'[v] = q[v]; a held vertex keeps its bits.  v is held when border
+ *   is given and border[v] != 0 (a null border: the border moves like the rest) or pinned (V, uint8, nullable) is given and
+ *   pinned[v] != 0.
+ * Border.  border (V) uint8 = 1 iff some neighbour stands in the vertex's live rows a number of times other than 2, else 0:
+ *   the border ufr_smooth_rows reports with cotangent weights for the same input.
+ * ufr_denoise_faces: writes the records and the rows into the workspace, every face's own normal into normals (F,3) and
+ *   border.  Three launches, no synchronisation.
+ * ufr_denoise_normals: n_steps normal steps over what a ufr_denoise_faces call with the same V, F and workspace left,
+ *   ping-ponging two record buffers inside the workspace; the last step writes normals (F,3).  n_steps = 0 leaves the faces'
+ *   own normals there.  Call it once per ufr_denoise_faces call.
+ * ufr_denoise_vertices: n_steps vertex steps with normals (F,3) fixed.  Step i reads pos_a and writes pos_b when i is even,
+ *   the other way round when i is odd: the caller puts the positions into pos_a (V,3) and finds the result in pos_a when
+ *   n_steps is even, in pos_b (V,3) when it is odd.
+ * Each phase issues all of its steps from one call and the host reads nothing between them.  Does not synchronise.
+ * workspace >= ufr_denoise_workspace_bytes (device; two records of 64 bytes a face and 20 bytes a row: 188 bytes a face; 0
+ * for arguments out of range).  Every argument error (null pointer, a count out of range, a sigma term that is not finite or
+ * not above 0, a negative n_steps, buffers that alias, a workspace that is too small) is UFR_ERR_ARG (UFR_ERR_WORKSPACE for
+ * the workspace) with the reason in the thread's last-error text; nothing is launched then.  Limits: sigma_r has to grow with
+ * the noise (noise of a third of an edge defeats 0.35); no real scan has been denoised.                                  */
+size_t ufr_denoise_workspace_bytes(int64_t V, int64_t F);
+int ufr_denoise_faces(const double* verts, const int32_t* faces, int64_t V, int64_t F, const int64_t* sorted_slots,
+                      const int64_t* run_starts, double* normals, uint8_t* border, void* workspace, size_t workspace_bytes,
+                      ufr_stream stream);
+int ufr_denoise_normals(const int32_t* faces, int64_t V, int64_t F, const int64_t* run_starts, double two_ss, double two_rr,
+                        int32_t n_steps, double* normals, void* workspace, size_t workspace_bytes, ufr_stream stream);
+int ufr_denoise_vertices(int64_t V, int64_t F, const int64_t* run_starts, const double* normals, const uint8_t* border,
+                         const uint8_t* pinned, int32_t n_steps, double* pos_a, double* pos_b, const void* workspace,
+                         size_t workspace_bytes, ufr_stream stream);
 
 /* ---- mesh simplification (ABI 507, additive) -----------------------------------------------------------------
  * Vertex clustering with quadric placement: the thinning stage of the mesh route, as ufr_points_voxel_mean is the point

@@ -208,6 +208,10 @@ SIGNATURES = {
     "ufr_smooth_workspace_bytes": (sz, [i64, i64, i32]),
     "ufr_smooth_rows": (C.c_int, [vp, vp, i64, i64, vp, vp, i32, vp, vp, sz, vp]),
     "ufr_smooth_steps": (C.c_int, [i64, i64, vp, i32, vp, vp, C.POINTER(C.c_double), i32, vp, vp, vp, sz, vp]),
+    "ufr_denoise_workspace_bytes": (sz, [i64, i64]),
+    "ufr_denoise_faces": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
+    "ufr_denoise_normals": (C.c_int, [vp, i64, i64, vp, C.c_double, C.c_double, i32, vp, vp, sz, vp]),
+    "ufr_denoise_vertices": (C.c_int, [i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
     "ufr_image_resize_u8": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),
     "ufr_pixel_rays": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, vp, vp]),
     "ufr_image_resize_mask_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.POINTER(i32), vp, vp]),

@@ -1168,3 +1168,89 @@ int ufr_smooth_steps(int64_t V, int64_t F, const int64_t* run_starts, int32_t we
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ mesh denoising
+namespace {
+
+// [face records fp64 (F,8), two of them: the normal steps ping-pong | rows int32 (3F,4) | the rows' faces int32 (3F)], in row order
+struct DenoiseWs { double* rec_a; double* rec_b; int* rows; int* row_face; };
+DenoiseWs carve_mesh_denoise(Carver& c, long long F) {
+  DenoiseWs w;
+  w.rec_a = c.take<double>((size_t)(8 * F));
+  w.rec_b = c.take<double>((size_t)(8 * F));
+  w.rows = c.take<int>((size_t)(12 * F));
+  w.row_face = c.take<int>((size_t)(3 * F));
+  return w;
+}
+
+int denoise_check(const char* who, int64_t V, int64_t F) {
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax / 3, "%s: V %lld, F %lld (V must be 1 .. 2^31 - 1, F 1 .. (2^31 - 1) / 3)",
+              who, (long long)V, (long long)F);
+  return UFR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ufr_denoise_workspace_bytes(int64_t V, int64_t F) {
+  if (V < 1 || V > kChMax || F < 1 || F > kChMax / 3) return 0;
+  return carved_bytes(carve_mesh_denoise, (long long)F);
+}
+
+int ufr_denoise_faces(const double* verts, const int32_t* faces, int64_t V, int64_t F, const int64_t* sorted_slots,
+                      const int64_t* run_starts, double* normals, uint8_t* border, void* workspace, size_t workspace_bytes,
+                      ufr_stream stream) {
+  const char* who = "ufr_denoise_faces";
+  UFR_REQUIRE(verts && faces && sorted_slots && run_starts && normals && border && workspace, "%s: null argument", who);
+  UFR_REQUIRE(normals != verts, "%s: normals and verts are one buffer", who);
+  UFR_CHECK(denoise_check(who, V, F));
+  Carver c(workspace);
+  const DenoiseWs w = carve_mesh_denoise(c, F);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_denoise_faces", s, launch_mesh_denoise_faces(verts, faces, V, F, w.rec_a, normals, s));
+  UFR_TIMED("mesh_denoise_rows", s, launch_mesh_denoise_rows(faces, V, F, reinterpret_cast<const long long*>(sorted_slots), w.rec_a,
+      w.rows, w.row_face, s));
+  UFR_TIMED("mesh_denoise_border", s, launch_mesh_denoise_border(V, F, reinterpret_cast<const long long*>(run_starts), w.rows, border, s));
+  return UFR_OK;
+}
+
+int ufr_denoise_normals(const int32_t* faces, int64_t V, int64_t F, const int64_t* run_starts, double two_ss, double two_rr,
+                        int32_t n_steps, double* normals, void* workspace, size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_denoise_normals";
+  UFR_REQUIRE(faces && run_starts && normals && workspace, "%s: null argument", who);
+  UFR_CHECK(denoise_check(who, V, F));
+  UFR_REQUIRE(std::isfinite(two_ss) && two_ss > 0.0, "%s: two_ss %g (must be finite and above 0)", who, two_ss);
+  UFR_REQUIRE(std::isfinite(two_rr) && two_rr > 0.0, "%s: two_rr %g (must be finite and above 0)", who, two_rr);
+  UFR_REQUIRE(n_steps >= 0, "%s: n_steps %d (must be >= 0)", who, n_steps);
+  Carver c(workspace);
+  const DenoiseWs w = carve_mesh_denoise(c, F);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i = 0; i < n_steps; ++i)
+    UFR_TIMED("mesh_denoise_normals", s, launch_mesh_denoise_normals(faces, V, F, reinterpret_cast<const long long*>(run_starts), w.row_face,
+        two_ss, two_rr, (i & 1) ? w.rec_b : w.rec_a, (i & 1) ? w.rec_a : w.rec_b, i == n_steps - 1 ? normals : nullptr, s));
+  return UFR_OK;
+}
+
+int ufr_denoise_vertices(int64_t V, int64_t F, const int64_t* run_starts, const double* normals, const uint8_t* border,
+                         const uint8_t* pinned, int32_t n_steps, double* pos_a, double* pos_b, const void* workspace,
+                         size_t workspace_bytes, ufr_stream stream) {
+  const char* who = "ufr_denoise_vertices";
+  UFR_REQUIRE(run_starts && normals && pos_a && pos_b && workspace, "%s: null argument", who);
+  UFR_REQUIRE(pos_a != pos_b, "%s: pos_a and pos_b are one buffer", who);
+  UFR_REQUIRE(normals != pos_a && normals != pos_b, "%s: normals and a position buffer are one buffer", who);
+  UFR_CHECK(denoise_check(who, V, F));
+  UFR_REQUIRE(n_steps >= 0, "%s: n_steps %d (must be >= 0)", who, n_steps);
+  Carver c(const_cast<void*>(workspace));
+  const DenoiseWs w = carve_mesh_denoise(c, F);
+  UFR_CHECK(check_workspace(who, workspace_bytes, c.off));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i = 0; i < n_steps; ++i)
+    UFR_TIMED("mesh_denoise_vertices", s, launch_mesh_denoise_vertices(V, F, reinterpret_cast<const long long*>(run_starts), w.rows, normals,
+        border, pinned, (i & 1) ? pos_b : pos_a, (i & 1) ? pos_a : pos_b, s));
+  return UFR_OK;
+}
+
+}  // extern "C"

@@ -297,6 +297,20 @@ hipError_t launch_mesh_smooth_border(long long V, long long F, const long long* 
 hipError_t launch_mesh_smooth_step(long long V, long long F, const long long* runs, const int* nbr, const double* wgt,
                                    const unsigned char* border, const unsigned char* pinned, double t, const double* in,
                                    double* out, hipStream_t s);
+// mesh_denoise.hip: bilateral normal filtering and the vertex update that follows the filtered normals (see the file header)
+constexpr int kDenoiseThreads = 256;       // faces, rows or vertices a block owns (ops.DENOISE_BLOCK says the same to the tests)
+constexpr int kDenoiseChunk = 1024;        // rows a block of the vertex step stages in LDS at a time (ops.DENOISE_CHUNK)
+hipError_t launch_mesh_denoise_faces(const double* verts, const int* faces, long long V, long long F, double* rec, double* normals,
+                                     hipStream_t s);
+hipError_t launch_mesh_denoise_rows(const int* faces, long long V, long long F, const long long* slots, const double* rec, int* rows,
+                                    int* row_face, hipStream_t s);
+hipError_t launch_mesh_denoise_border(long long V, long long F, const long long* runs, const int* rows, unsigned char* border,
+                                      hipStream_t s);
+hipError_t launch_mesh_denoise_normals(const int* faces, long long V, long long F, const long long* runs, const int* row_face, double two_ss,
+                                       double two_rr, const double* in, double* out, double* normals, hipStream_t s);
+hipError_t launch_mesh_denoise_vertices(long long V, long long F, const long long* runs, const int* rows, const double* normals,
+                                        const unsigned char* border, const unsigned char* pinned, const double* in, double* out,
+                                        hipStream_t s);
 // frame_metrics.hip: the scores and 8-bit previews of a validation frame (see the file header)
 constexpr int kFrameMetricsBlocks = 256;   // most partial rows one frame leaves in the workspace
 hipError_t launch_frame_metrics(const float* rgb_c, const float* rgb_f, const float* rgb_gt, const float* depth_c, const float* depth_f,

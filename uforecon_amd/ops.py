@@ -2094,6 +2094,88 @@ def mesh_smooth(verts: torch.Tensor, faces: torch.Tensor, method: str = "taubin"
     return dict(verts=pos_a if n % 2 == 0 else pos_b, border=border)
 
 
+# ---- mesh denoising (csrc/mesh_denoise.hip; uforecon_amd/denoise_mesh.py is the caller)
+DENOISE_BLOCK = 256                                 # kDenoiseThreads of csrc/ufr_internal.h: the faces, rows or vertices one block owns
+DENOISE_CHUNK = 1024                                # kDenoiseChunk: the rows a block of the vertex step stages in LDS at a time
+DENOISE_SIGMA_R = 0.35                              # the chord of about 20 degrees: a neighbour turned that far weighs e^-1/2
+
+
+def _denoise_count(name: str, n) -> int:
+    if isinstance(n, bool) or int(n) != n or int(n) < 0 or int(n) >= 2 ** 31:
+        raise UfrError(f"mesh_denoise: {name} {n} (an integer >= 0)")
+    return int(n)
+
+
+def _denoise_sigma(name: str, s) -> float:
+    if s is None:
+        raise UfrError(f"mesh_denoise: {name} is required")
+    s = float(s)
+    two = 2.0 * (s * s)
+    if not (s > 0.0 and 0.0 < two < float("inf")):
+        raise UfrError(f"mesh_denoise: {name} {s} (must be finite and above 0)")
+    return two
+
+
+def mesh_denoise(verts: torch.Tensor, faces: torch.Tensor, normal_iterations: int = 5, vertex_iterations: int = 10,
+                 sigma_s: Optional[float] = None, sigma_r: float = DENOISE_SIGMA_R, boundary: str = "fixed",
+                 pinned: Optional[torch.Tensor] = None):
+    """Feature-preserving denoising of the vertex positions: ``normal_iterations`` steps of the bilateral normal filter, then
+    ``vertex_iterations`` steps that move the vertices to the filtered normals (include/ufr.h, "mesh denoising", states every
+    rule).  ``verts`` (V,3) CUDA float64, ``faces`` (F,3) CUDA int32; ``sigma_s`` (required here; ``denoise_mesh`` defaults it to
+    the mean edge length) scales the distance between centroids and ``sigma_r`` the difference of unit normals; ``boundary``
+    "fixed" (border vertices stay) or "free"; ``pinned`` (V,) CUDA uint8 or None: further vertices that stay.  Returns a
+    dict: ``verts`` (V,3) float64 (a new tensor; the input's bits when ``vertex_iterations`` is 0), ``normals`` (F,3) float64
+    (the filtered face normals, zeros for a dead face) and ``border`` (V,) uint8.  Empty ``faces`` or ``verts`` give the input
+    positions back.  The corner slots are sorted by vertex here, once (stable); each phase goes out in one library call.  A
+    face index outside 0 .. V-1, a sigma that is not finite or not above 0, a negative iteration count, wrong dtypes or shapes
+    raise UfrError before any kernel of the library runs.  One host synchronisation (the index check)."""
+    if boundary not in SMOOTH_BOUNDARIES:
+        raise UfrError(f"mesh_denoise: boundary {boundary!r} (one of {sorted(SMOOTH_BOUNDARIES)})")
+    n_normal = _denoise_count("normal_iterations", normal_iterations)
+    n_vertex = _denoise_count("vertex_iterations", vertex_iterations)
+    two_ss, two_rr = _denoise_sigma("sigma_s", sigma_s), _denoise_sigma("sigma_r", sigma_r)
+    _points64(verts, "verts")
+    _dev(faces, "faces", torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if pinned is not None:
+        _dev(pinned, "pinned", torch.uint8)
+        if tuple(pinned.shape) != (V,):
+            raise UfrError(f"pinned: expected shape ({V},), got {tuple(pinned.shape)}")
+    if 3 * F >= 2 ** 31:
+        raise UfrError(f"mesh_denoise: {F} faces: (2^31 - 1) / 3 or more")
+    if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise UfrError(f"mesh_denoise: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
+    dev = verts.device
+    border = torch.zeros(V, dtype=torch.uint8, device=dev)
+    normals = torch.zeros((F, 3), dtype=torch.float64, device=dev)
+    pos_a = verts.clone()
+    if V == 0 or F == 0:
+        return dict(verts=pos_a, normals=normals, border=border)
+    corner = faces.reshape(-1).to(torch.int64)
+    svert, slots = torch.sort(corner, stable=True)
+    slots = slots.contiguous()
+    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=dev)).contiguous()
+    lib = _lib.load()
+    nbytes = lib.ufr_denoise_workspace_bytes(V, F)
+    if nbytes == 0:
+        raise UfrError(f"mesh_denoise: V {V}, F {F} unsupported")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.ufr_denoise_faces(verts.data_ptr(), faces.data_ptr(), V, F, slots.data_ptr(), runs.data_ptr(), normals.data_ptr(),
+                                     border.data_ptr(), ws.data_ptr(), nbytes, _stream()), "ufr_denoise_faces")
+    if n_normal:
+        _lib.check(lib.ufr_denoise_normals(faces.data_ptr(), V, F, runs.data_ptr(), two_ss, two_rr, n_normal, normals.data_ptr(),
+                                           ws.data_ptr(), nbytes, _stream()), "ufr_denoise_normals")
+    if n_vertex == 0:
+        return dict(verts=pos_a, normals=normals, border=border)
+    pos_b = torch.empty_like(pos_a)
+    _lib.check(lib.ufr_denoise_vertices(V, F, runs.data_ptr(), normals.data_ptr(), border.data_ptr() if boundary == "fixed" else None,
+                                        None if pinned is None else pinned.data_ptr(), n_vertex, pos_a.data_ptr(), pos_b.data_ptr(),
+                                        ws.data_ptr(), nbytes, _stream()), "ufr_denoise_vertices")
+    return dict(verts=pos_a if n_vertex % 2 == 0 else pos_b, normals=normals, border=border)
+
+
 # ---- a scan loader's per-pixel work (csrc/frame_input.hip; uforecon_amd/dtu_scan.py is the caller)
 def image_resize_u8(images: torch.Tensor, H: int, W: int, clip=(0, 0, 0, 0)) -> torch.Tensor:
     """ufr_image_resize_u8: (n,Hs,Ws,3) CUDA uint8 RGB -> (n,3,Ho,Wo) float32 planes in [0,1]: every image resized to ``H`` x

@@ -19,7 +19,7 @@ colours pass through, so the output goes as it stands through ``simplify_mesh``,
    and does not shrink the surface;
 4. a border vertex -- some neighbour does not occur exactly twice -- stays where it is unless ``--boundary free``.
 
-There is no bilateral or feature-preserving filter: an edge is rounded like noise.  Open3D's ``filter_smooth_taubin`` and
+An edge is rounded like noise here: the feature-preserving filter is ``denoise_mesh``.  Open3D's ``filter_smooth_taubin`` and
 ``filter_smooth_laplacian`` were not compared against, and no real scan has been smoothed.
 """
 from __future__ import annotations
