@@ -1,4 +1,4 @@
-// extern "C" surface of libufr.so (include/ufr.h), part 1 of 7: the process- and thread-wide state behind api_common.h --
+// extern "C" surface of libufr.so (include/ufr.h): the process- and thread-wide state behind api_common.h --
 // the error text, the matrix-precision default, the sticky range status and the profiling hooks.  The entry points
 // themselves (api_*.hip) validate arguments, carve workspaces and sequence kernels on the caller's HIP stream: no torch
 // types, no host<->device synchronisation.

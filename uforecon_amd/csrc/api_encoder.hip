@@ -1,4 +1,4 @@
-// extern "C" surface of libufr.so (include/ufr.h), part 5 of 7: the encoder -- correlation volumes and view weights, the
+// extern "C" surface of libufr.so (include/ufr.h): the encoder -- correlation volumes and view weights, the
 // 3-D convolutions of the frustum U-Nets, the 2-D and deformable convolutions of the feature backbone, the FMT layer, and
 // what a scan loader feeds them (image planes from 8-bit pictures, with or without a foreground mask; the per-pixel ray tables)
 // and what a COLMAP model's converter asks before any of it (the pair scores of the view selection, the undistorted pictures).

@@ -1,4 +1,4 @@
-// extern "C" surface of libufr.so (include/ufr.h), part 3 of 7: the forward ray path -- its per-op entry points and the
+// extern "C" surface of libufr.so (include/ufr.h): the forward ray path -- its per-op entry points and the
 // whole-path two-pass renderer with its side streams.
 #include "api_common.h"
 

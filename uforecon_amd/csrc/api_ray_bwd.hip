@@ -1,4 +1,4 @@
-// extern "C" surface of libufr.so (include/ufr.h), part 4 of 7: training -- the compositor's backward and the loss, the
+// extern "C" surface of libufr.so (include/ufr.h): training -- the compositor's backward and the loss, the
 // forwards that record a tape, the streaming backwards of both transformers and the gather's backward.
 #include "api_common.h"
 #include "bwd_tape.h"

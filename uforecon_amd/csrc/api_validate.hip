@@ -1,4 +1,4 @@
-// extern "C" surface of libufr.so (include/ufr.h), part 7 of 7: validation -- a frame's scores and previews, the ground-truth depth of a
+// extern "C" surface of libufr.so (include/ufr.h): validation -- a frame's scores and previews, the ground-truth depth of a
 // training view.
 #include "api_common.h"
 

@@ -1,4 +1,4 @@
-// extern "C" surface of libufr.so (include/ufr.h), part 2 of 7: the packed-weight blob (sizes, pack plans, packing) and
+// extern "C" surface of libufr.so (include/ufr.h): the packed-weight blob (sizes, pack plans, packing) and
 // the preparation of a frame.
 #include "api_common.h"
 #include "ufr_layout_f16.h"

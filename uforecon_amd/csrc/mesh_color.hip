@@ -24,9 +24,7 @@
 //          the out buffers only, so a round does not depend on scheduling.
 //
 // Block shape: kColorThreads (256) threads, no LDS.  Every index read from a caller's array is range-checked before it is used.
-#include "ufr_internal.h"
-
-#pragma clang fp contract(off)
+#include "mesh_rows.h"
 
 namespace ufr {
 namespace {
@@ -150,14 +148,12 @@ __global__ void __launch_bounds__(kColorThreads) color_fill_round_kernel(const i
   if (v >= V) return;
   unsigned char o0 = colors_in[3 * v], o1 = colors_in[3 * v + 1], o2 = colors_in[3 * v + 2], st = state_in[v];
   if (st == 0) {
-    long long i0 = runs[v], i1 = runs[v + 1];
-    if (i0 < 0) i0 = 0;
-    if (i1 > 3 * F) i1 = 3 * F;
+    long long i0, i1;
+    run_of(runs, v, 3 * F, &i0, &i1);
     long long s0 = 0, s1 = 0, s2 = 0, count = 0;
     for (long long i = i0; i < i1; ++i) {
       const long long slot = slots[i];
-      if (slot < 0 || slot >= 3 * F) continue;
-      if ((long long)faces[slot] != v) continue;
+      if (!slot_names(slot, faces, F, v)) continue;
       const long long f = slot / 3;
       const int e = (int)(slot - 3 * f);
 #pragma unroll

@@ -7,7 +7,7 @@
 //   rows     one thread per sorted corner slot (the slots of ufr_raster_vertex_normals): (g, a, b, e) -- the slot's face, its
 //          two other corners and the corner the row stands at -- or (-1, -1, -1, 0) for a row of a dead face; and g once more in
 //          an array of its own, 4 bytes a row, for the normal step.  Run once per call.
-//   border   one thread per vertex, the rule and the double loop of smooth_border_kernel over these rows.
+//   border   mesh_rows.h's border rule over these rows, as smoothing runs it over its own.
 //   normals  one thread per face, the hot path: itself first, then the rows of its three corner vertices in ascending slot,
 //          each row's g read by the thread that uses it (4 bytes; the runs of one face's corners are not one span, so there is
 //          nothing for a block to stage).  At the second and third corner the neighbour's three indices say whether it names an
@@ -15,7 +15,7 @@
 //          area and centroid together.  Reads the previous records only (Jacobi) and writes the whole next record, so the
 //          caller ping-pongs two record buffers; the last step also writes the (F,3) normals.
 //   vertices one thread per vertex walks its rows in order and reads the previous positions only; the rows of a block's 256
-//          vertices are one span, staged in LDS kDenoiseChunk rows at a time exactly as smooth_step_kernel does.  A row's e
+//          vertices are one span, staged in LDS kMeshRowChunk rows at a time by mesh_rows.h's staged walk.  A row's e
 //          gives the face's own corner order back, so the centroid is summed as the rule states without a read of the faces.
 // Every sum is sequential per face or vertex in the header's order: no float atomic, no shuffle tree, a rerun gives the same
 // bits.  A run may be longer than a chunk or a block: its thread's loop is then long, not wrong.  Every index read from
@@ -23,22 +23,12 @@
 // array's size.  k(u) = (1 - u / 256)^256 by eight squarings stands in for exp(-u) without a transcendental call.
 // The shapes of the normal step that were timed are in profiles/mesh_denoise_launch_shapes.md.
 // 256 threads a block everywhere (64, 128 and 512 are 13 %, 6 % and 2 % slower on the normal step).  normals: 58 VGPRs, no LDS.
-// vertices: 60 VGPRs, 16 KiB of LDS (1024 rows of 16 bytes; ten blocks a CU by LDS, eight by waves).  faces 55, rows 12, border
+// vertices: 59 VGPRs, 16 KiB of LDS (1024 rows of 16 bytes; ten blocks a CU by LDS, eight by waves).  faces 55, rows 20, border
 // 37 VGPRs, no LDS.  All five fit eight waves a SIMD.
-#include "ufr_internal.h"
-
-#pragma clang fp contract(off)
+#include "mesh_rows.h"
 
 namespace ufr {
 namespace {
-
-constexpr int kDn = kDenoiseThreads;
-
-unsigned blocks_of(long long n) { return (unsigned)((n + kDn - 1) / kDn); }
-
-__device__ inline double dot3(double x0, double x1, double x2, double y0, double y1, double y2) {
-  return (x0 * y0 + x1 * y1) + x2 * y2;
-}
 
 // (1 - u / 256)^256; 0 from u = 256 on and for a NaN
 __device__ inline double weight_kernel(double u) {
@@ -49,21 +39,13 @@ __device__ inline double weight_kernel(double u) {
   return x;
 }
 
-// the run of vertex v, clipped to the rows there are
-__device__ inline void run_of(const long long* __restrict__ runs, long long v, long long rows, long long* i0, long long* i1) {
-  long long a = runs[v], b = runs[v + 1];
-  if (a < 0) a = 0;
-  if (b > rows) b = rows;
-  *i0 = a, *i1 = b;
-}
-
-__global__ void __launch_bounds__(kDn) denoise_faces_kernel(const double* __restrict__ verts, const int* __restrict__ faces, long long V,
-                                                             long long F, double2* __restrict__ rec, double* __restrict__ normals) {
-  const long long f = (long long)blockIdx.x * kDn + threadIdx.x;
+__global__ void __launch_bounds__(kMeshRowThreads) denoise_faces_kernel(const double* __restrict__ verts, const int* __restrict__ faces, long long V,
+                                                                         long long F, double2* __restrict__ rec, double* __restrict__ normals) {
+  const long long f = (long long)blockIdx.x * kMeshRowThreads + threadIdx.x;
   if (f >= F) return;
   const long long c0 = faces[3 * f], c1 = faces[3 * f + 1], c2 = faces[3 * f + 2];
   double n0 = 0.0, n1 = 0.0, n2 = 0.0, A = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0, flag = 0.0;
-  if (c0 >= 0 && c0 < V && c1 >= 0 && c1 < V && c2 >= 0 && c2 < V && c0 != c1 && c1 != c2 && c0 != c2) {
+  if (corners_live(c0, c1, c2, V)) {
     const double p0 = verts[3 * c0], p1 = verts[3 * c0 + 1], p2 = verts[3 * c0 + 2];
     const double q0 = verts[3 * c1], q1 = verts[3 * c1 + 1], q2 = verts[3 * c1 + 2];
     const double r0 = verts[3 * c2], r1 = verts[3 * c2 + 1], r2 = verts[3 * c2 + 2];
@@ -87,52 +69,24 @@ __global__ void __launch_bounds__(kDn) denoise_faces_kernel(const double* __rest
   normals[3 * f + 2] = n2;
 }
 
-__global__ void __launch_bounds__(kDn) denoise_rows_kernel(const int* __restrict__ faces, long long V, long long F,
-                                                            const long long* __restrict__ slots, const double2* __restrict__ rec,
-                                                            int4* __restrict__ rows, int* __restrict__ row_face) {
-  const long long n = 3 * F;
-  const long long i = (long long)blockIdx.x * kDn + threadIdx.x;
-  if (i >= n) return;
+__global__ void __launch_bounds__(kMeshRowThreads) denoise_rows_kernel(const int* __restrict__ faces, long long V, long long F,
+                                                                        const long long* __restrict__ slots, const double2* __restrict__ rec,
+                                                                        int4* __restrict__ rows, int* __restrict__ row_face) {
+  const long long i = (long long)blockIdx.x * kMeshRowThreads + threadIdx.x;
+  if (i >= 3 * F) return;
   int4 row = make_int4(-1, -1, -1, 0);
-  const long long slot = slots[i];
-  if (slot >= 0 && slot < n) {
-    const long long f = slot / 3;
-    const int e = (int)(slot - 3 * f);
-    if (rec[4 * f + 3].y != 0.0) {                          // live: its corners are in range and distinct
-      const int c0 = faces[3 * f], c1 = faces[3 * f + 1], c2 = faces[3 * f + 2];
-      row = make_int4((int)f, e == 0 ? c1 : e == 1 ? c2 : c0, e == 0 ? c2 : e == 1 ? c0 : c1, e);
-    }
-  }
+  const SlotCorners c = decode_slot(slots[i], faces, V, F);
+  if (c.ok && rec[4 * c.f + 3].y != 0.0)                     // live: its normal is finite too
+    row = make_int4((int)c.f, (int)c.a, (int)c.b, c.e);
   rows[i] = row;
   row_face[i] = row.x;
 }
 
-__global__ void __launch_bounds__(kDn) denoise_border_kernel(long long V, long long F, const long long* __restrict__ runs,
-                                                              const int4* __restrict__ rows, unsigned char* __restrict__ border) {
-  const long long v = (long long)blockIdx.x * kDn + threadIdx.x;
-  if (v >= V) return;
-  long long i0, i1;
-  run_of(runs, v, 3 * F, &i0, &i1);
-  bool open = false;
-  for (long long i = i0; i < i1 && !open; ++i) {
-    const int4 ab = rows[i];
-    if (ab.x < 0) continue;                                 // a dead row: (-1, -1), equal to no neighbour
-    int ca = 0, cb = 0;
-    for (long long k = i0; k < i1; ++k) {
-      const int4 q = rows[k];
-      ca += (q.y == ab.y ? 1 : 0) + (q.z == ab.y ? 1 : 0);
-      cb += (q.y == ab.z ? 1 : 0) + (q.z == ab.z ? 1 : 0);
-    }
-    open = ca != 2 || cb != 2;
-  }
-  border[v] = open ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(kDn) denoise_normal_kernel(const int* __restrict__ faces, long long V, long long F,
-                                                              const long long* __restrict__ runs, const int* __restrict__ row_face,
-                                                              double two_ss, double two_rr, const double2* __restrict__ in,
-                                                              double2* __restrict__ out, double* __restrict__ normals) {
-  const long long f = (long long)blockIdx.x * kDn + threadIdx.x;
+__global__ void __launch_bounds__(kMeshRowThreads) denoise_normal_kernel(const int* __restrict__ faces, long long V, long long F,
+                                                                          const long long* __restrict__ runs, const int* __restrict__ row_face,
+                                                                          double two_ss, double two_rr, const double2* __restrict__ in,
+                                                                          double2* __restrict__ out, double* __restrict__ normals) {
+  const long long f = (long long)blockIdx.x * kMeshRowThreads + threadIdx.x;
   if (f >= F) return;
   const double2 r0 = in[4 * f], r1 = in[4 * f + 1], r2 = in[4 * f + 2], r3 = in[4 * f + 3];
   const double n0 = r0.x, n1 = r0.y, n2 = r1.x, c0 = r2.x, c1 = r2.y, c2 = r3.x;
@@ -180,39 +134,27 @@ __global__ void __launch_bounds__(kDn) denoise_normal_kernel(const int* __restri
   }
 }
 
-__global__ void __launch_bounds__(kDn) denoise_vertex_kernel(long long V, long long F, const long long* __restrict__ runs,
-                                                              const int4* __restrict__ rows, const double* __restrict__ normals,
-                                                              const unsigned char* __restrict__ border,
-                                                              const unsigned char* __restrict__ pinned, const double* __restrict__ in,
-                                                              double* __restrict__ out) {
-  __shared__ int4 s_rows[kDenoiseChunk];
-  const long long n_rows = 3 * F;
-  const long long first = (long long)blockIdx.x * kDn;     // < V: the grid is ceil(V / kDn)
-  const long long last = first + kDn < V ? first + kDn : V;
-  const long long v = first + threadIdx.x;
+__global__ void __launch_bounds__(kMeshRowThreads) denoise_vertex_kernel(long long V, long long F, const long long* __restrict__ runs,
+                                                                          const int4* __restrict__ rows, const double* __restrict__ normals,
+                                                                          const unsigned char* __restrict__ border,
+                                                                          const unsigned char* __restrict__ pinned, const double* __restrict__ in,
+                                                                          double* __restrict__ out) {
+  __shared__ int4 s_rows[kMeshRowChunk];
+  const long long v = (long long)blockIdx.x * kMeshRowThreads + threadIdx.x;
   const bool valid = v < V;
-  long long b0, b1;                                         // the block's rows: the runs of its vertices are one span
-  run_of(runs, first, n_rows, &b0, &b1);
-  b1 = runs[last] > n_rows ? n_rows : runs[last];
   double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-  long long i = 0, i1 = 0;
   bool walk = false;
   if (valid) {
     p0 = in[3 * v], p1 = in[3 * v + 1], p2 = in[3 * v + 2];
-    run_of(runs, v, n_rows, &i, &i1);
     walk = !((border && border[v]) || (pinned && pinned[v]));
   }
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, cnt = 0.0;
-  for (long long base = b0; base < b1; base += kDenoiseChunk) {
-    const int n = (int)(b1 - base < kDenoiseChunk ? b1 - base : kDenoiseChunk);
-    for (int j = threadIdx.x; j < n; j += kDn) s_rows[j] = rows[base + j];      // the chunk's rows, coalesced
-    __syncthreads();
-    if (walk) {
-      if (i < base) i = base;                               // runs that are not ascending: rows outside the span are skipped
-      for (; i < i1 && i < base + n; ++i) {                 // this thread's rows of the chunk, in order
-        const int4 row = s_rows[i - base];
+  for_each_staged_row(
+      runs, V, 3 * F, walk, [&](int j, long long i) { s_rows[j] = rows[i]; },
+      [&](int j) {
+        const int4 row = s_rows[j];
         const long long g = row.x, a = row.y, b = row.z;
-        if (g < 0 || g >= F || a < 0 || a >= V || b < 0 || b >= V || row.w < 0 || row.w > 2) continue;
+        if (g < 0 || g >= F || a < 0 || a >= V || b < 0 || b >= V || row.w < 0 || row.w > 2) return;
         const double a0 = in[3 * a], a1 = in[3 * a + 1], a2 = in[3 * a + 2];
         const double q0 = in[3 * b], q1 = in[3 * b + 1], q2 = in[3 * b + 2];
         const double m0 = normals[3 * g], m1 = normals[3 * g + 1], m2 = normals[3 * g + 2];
@@ -225,10 +167,7 @@ __global__ void __launch_bounds__(kDn) denoise_vertex_kernel(long long V, long l
         s1 += m1 * d;
         s2 += m2 * d;
         cnt += 1.0;
-      }
-    }
-    __syncthreads();
-  }
+      });
   if (!valid) return;
   double o0 = p0, o1 = p1, o2 = p2;
   if (walk && cnt > 0.0) {
@@ -245,26 +184,27 @@ __global__ void __launch_bounds__(kDn) denoise_vertex_kernel(long long V, long l
 
 hipError_t launch_mesh_denoise_faces(const double* verts, const int* faces, long long V, long long F, double* rec, double* normals,
                                      hipStream_t s) {
-  hipLaunchKernelGGL(denoise_faces_kernel, dim3(blocks_of(F)), dim3(kDn), 0, s, verts, faces, V, F, reinterpret_cast<double2*>(rec), normals);
+  hipLaunchKernelGGL(denoise_faces_kernel, dim3(mesh_row_blocks(F)), dim3(kMeshRowThreads), 0, s, verts, faces, V, F, reinterpret_cast<double2*>(rec), normals);
   return hipGetLastError();
 }
 
 hipError_t launch_mesh_denoise_rows(const int* faces, long long V, long long F, const long long* slots, const double* rec, int* rows,
                                     int* row_face, hipStream_t s) {
-  hipLaunchKernelGGL(denoise_rows_kernel, dim3(blocks_of(3 * F)), dim3(kDn), 0, s, faces, V, F, slots,
+  hipLaunchKernelGGL(denoise_rows_kernel, dim3(mesh_row_blocks(3 * F)), dim3(kMeshRowThreads), 0, s, faces, V, F, slots,
                      reinterpret_cast<const double2*>(rec), reinterpret_cast<int4*>(rows), row_face);
   return hipGetLastError();
 }
 
 hipError_t launch_mesh_denoise_border(long long V, long long F, const long long* runs, const int* rows, unsigned char* border,
                                       hipStream_t s) {
-  hipLaunchKernelGGL(denoise_border_kernel, dim3(blocks_of(V)), dim3(kDn), 0, s, V, F, runs, reinterpret_cast<const int4*>(rows), border);
+  hipLaunchKernelGGL(mesh_border_kernel<int4>, dim3(mesh_row_blocks(V)), dim3(kMeshRowThreads), 0, s, V, F, runs,
+                     reinterpret_cast<const int4*>(rows), border);
   return hipGetLastError();
 }
 
 hipError_t launch_mesh_denoise_normals(const int* faces, long long V, long long F, const long long* runs, const int* row_face, double two_ss,
                                        double two_rr, const double* in, double* out, double* normals, hipStream_t s) {
-  hipLaunchKernelGGL(denoise_normal_kernel, dim3(blocks_of(F)), dim3(kDn), 0, s, faces, V, F, runs, row_face,
+  hipLaunchKernelGGL(denoise_normal_kernel, dim3(mesh_row_blocks(F)), dim3(kMeshRowThreads), 0, s, faces, V, F, runs, row_face,
                      two_ss, two_rr, reinterpret_cast<const double2*>(in), reinterpret_cast<double2*>(out), normals);
   return hipGetLastError();
 }
@@ -272,7 +212,7 @@ hipError_t launch_mesh_denoise_normals(const int* faces, long long V, long long 
 hipError_t launch_mesh_denoise_vertices(long long V, long long F, const long long* runs, const int* rows, const double* normals,
                                         const unsigned char* border, const unsigned char* pinned, const double* in, double* out,
                                         hipStream_t s) {
-  hipLaunchKernelGGL(denoise_vertex_kernel, dim3(blocks_of(V)), dim3(kDn), 0, s, V, F, runs, reinterpret_cast<const int4*>(rows), normals,
+  hipLaunchKernelGGL(denoise_vertex_kernel, dim3(mesh_row_blocks(V)), dim3(kMeshRowThreads), 0, s, V, F, runs, reinterpret_cast<const int4*>(rows), normals,
                      border, pinned, in, out);
   return hipGetLastError();
 }

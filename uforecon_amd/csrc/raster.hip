@@ -24,10 +24,8 @@
 //          iff 2r > s^2, or 2r == s^2 and q is odd (round half to even).
 //
 // Block shape: 256 threads throughout, no LDS.  Every index read from a caller's array is range-checked before it is used.
-#include "ufr_internal.h"
 #include "mesh_ray.h"
-
-#pragma clang fp contract(off)
+#include "mesh_rows.h"
 
 namespace ufr {
 namespace {
@@ -41,14 +39,12 @@ __global__ void __launch_bounds__(kRsThreads) vertex_normals_kernel(const double
                                                                      double* __restrict__ normals) {
   const long long v = (long long)blockIdx.x * kRsThreads + threadIdx.x;
   if (v >= V) return;
-  long long i0 = runs[v], i1 = runs[v + 1];
-  if (i0 < 0) i0 = 0;
-  if (i1 > 3 * F) i1 = 3 * F;
+  long long i0, i1;
+  run_of(runs, v, 3 * F, &i0, &i1);
   double sx = 0.0, sy = 0.0, sz = 0.0;
   for (long long i = i0; i < i1; ++i) {
     const long long slot = slots[i];
-    if (slot < 0 || slot >= 3 * F) continue;
-    if ((long long)faces[slot] != v) continue;
+    if (!slot_names(slot, faces, F, v)) continue;
     const long long f = slot / 3;
     const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
     if (ia < 0 || ib < 0 || ic < 0 || ia >= V || ib >= V || ic >= V) continue;

@@ -287,9 +287,7 @@ hipError_t launch_simplify_compact_vertices(const unsigned char* referenced, lon
                                             unsigned char* out_colors, unsigned char* out_placed, int* out_count,
                                             long long capacity, int* cluster_vertex, int* vertex_map, long long* block_tot,
                                             long long* block_off, long long* total, hipStream_t s);
-// mesh_smooth.hip: Laplacian and Taubin smoothing with uniform or cotangent weights (see the file header)
-constexpr int kSmoothThreads = 256;        // rows or vertices a block owns (ops.SMOOTH_BLOCK says the same to the tests)
-constexpr int kSmoothChunk = 1024;         // rows a block of the step stages in LDS at a time (ops.SMOOTH_CHUNK)
+// mesh_smooth.hip: Laplacian and Taubin smoothing with uniform or cotangent weights (see the file header; block and chunk sizes: mesh_rows.h)
 hipError_t launch_mesh_smooth_rows(const double* verts, const int* faces, long long V, long long F, const long long* slots,
                                    int cotangent, int* nbr, double* wgt, hipStream_t s);
 hipError_t launch_mesh_smooth_border(long long V, long long F, const long long* runs, const int* nbr, unsigned char* border,
@@ -298,8 +296,6 @@ hipError_t launch_mesh_smooth_step(long long V, long long F, const long long* ru
                                    const unsigned char* border, const unsigned char* pinned, double t, const double* in,
                                    double* out, hipStream_t s);
 // mesh_denoise.hip: bilateral normal filtering and the vertex update that follows the filtered normals (see the file header)
-constexpr int kDenoiseThreads = 256;       // faces, rows or vertices a block owns (ops.DENOISE_BLOCK says the same to the tests)
-constexpr int kDenoiseChunk = 1024;        // rows a block of the vertex step stages in LDS at a time (ops.DENOISE_CHUNK)
 hipError_t launch_mesh_denoise_faces(const double* verts, const int* faces, long long V, long long F, double* rec, double* normals,
                                      hipStream_t s);
 hipError_t launch_mesh_denoise_rows(const int* faces, long long V, long long F, const long long* slots, const double* rec, int* rows,

@@ -48,11 +48,16 @@ def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> int:
         raise UfrError(f"{name}: expected a tensor")
     if not t.is_cuda:
         raise UfrError(f"{name}: must live on the GPU (got {t.device}); the per-ray path has no CPU implementation")
+    _typed(t, name, dtype)
+    return t.data_ptr()
+
+
+def _typed(t: torch.Tensor, name: str, dtype) -> None:
+    """the checks of ``_dev`` that do not ask where the tensor lives"""
     if t.dtype != dtype:
         raise UfrError(f"{name}: dtype {t.dtype}, expected {dtype}")
     if not t.is_contiguous():
         raise UfrError(f"{name}: must be contiguous")
-    return t.data_ptr()
 
 
 def _opt(t: Optional[torch.Tensor], name: str) -> Optional[int]:
@@ -1313,16 +1318,53 @@ MASK_MAX_KERNEL = 127      # UFR_MASK_MAX_KERNEL of include/ufr.h
 MESH_MAX_VIEWS = 64        # UFR_MESH_MAX_VIEWS
 
 
-def _mesh(verts: torch.Tensor, faces: torch.Tensor, who: str):
-    """pointers and sizes of a mesh; raises on a face index outside 0..V-1 (one host synchronisation)"""
-    pv = _points64(verts, "verts")
-    pf = _dev(faces, "faces", torch.int32)
+def _faces(faces: torch.Tensor, V: int, who: str, rows: bool = False) -> int:
+    """F of an (F,3) int32 face array, on any device; raises on a wrong dtype or shape, on a face index outside 0..V-1 (one
+    host synchronisation) and, with ``rows`` (the caller hands the 3F corner slots to the library), on 3F >= 2^31"""
+    _typed(faces, "faces", torch.int32)
     if faces.dim() != 2 or faces.shape[1] != 3:
         raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
-    V, F = int(verts.shape[0]), int(faces.shape[0])
+    F = int(faces.shape[0])
+    if rows and 3 * F >= 2 ** 31:
+        raise UfrError(f"{who}: {F} faces: (2^31 - 1) / 3 or more")
     if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
         raise UfrError(f"{who}: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
-    return pv, pf, V, F
+    return F
+
+
+def _mesh(verts: torch.Tensor, faces: torch.Tensor, who: str, rows: bool = False):
+    """pointers and sizes of a mesh on the GPU, checked by ``_points64`` and ``_faces``"""
+    pv = _points64(verts, "verts")
+    pf = _dev(faces, "faces", torch.int32)
+    V = int(verts.shape[0])
+    return pv, pf, V, _faces(faces, V, who, rows)
+
+
+def _corner_runs(faces: torch.Tensor, V: int):
+    """The one order every per-vertex mesh stage walks: the 3F corner slots 3f + e sorted stably by the vertex they name,
+    ``slots`` (3F,) int64, and where each vertex's run starts, ``runs`` (V+1,) int64; both contiguous, on the device of
+    ``faces`` (any device).  A kernel that walks a run in ascending slot sums in one order, whatever the scheduling."""
+    svert, slots = torch.sort(faces.reshape(-1).to(torch.int64), stable=True)
+    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=faces.device))
+    return slots.contiguous(), runs.contiguous()
+
+
+def _ring_setup(verts: torch.Tensor, faces: torch.Tensor, pinned: Optional[torch.Tensor], who: str):
+    """What the stages that move vertices over their ring share: the checks of the mesh and of ``pinned``, a zeroed
+    ``border`` (V,) uint8 and ``pos_a``, a copy of ``verts`` -- the first of the two buffers the steps ping-pong.  Returns V, F,
+    border, pos_a and whether the mesh is empty (the input's positions are then the answer)."""
+    _, _, V, F = _mesh(verts, faces, who, rows=True)
+    if pinned is not None:
+        _dev(pinned, "pinned", torch.uint8)
+        if tuple(pinned.shape) != (V,):
+            raise UfrError(f"pinned: expected shape ({V},), got {tuple(pinned.shape)}")
+    border = torch.zeros(V, dtype=torch.uint8, device=verts.device)
+    return V, F, border, verts.clone(), V == 0 or F == 0
+
+
+def _ring_result(pos_a: torch.Tensor, pos_b: torch.Tensor, n_steps: int) -> torch.Tensor:
+    """the buffer that holds the positions after ``n_steps`` steps that began in ``pos_a``"""
+    return pos_a if n_steps % 2 == 0 else pos_b
 
 
 def mask_half_widths(k: int):
@@ -1448,17 +1490,12 @@ def raster_vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Ten
     faces that use the vertex, (0,0,0) for a vertex without faces or with a zero sum.  ``verts`` (V,3) CUDA float64, ``faces``
     (F,3) CUDA int32.  The corner slots are sorted by vertex here (stable), so the sums do not depend on scheduling.  A face
     index out of range raises.  One host synchronisation (the index check)."""
-    pv, pf, V, F = _mesh(verts, faces, "raster_vertex_normals")
-    dev = verts.device
-    normals = torch.zeros((V, 3), dtype=torch.float64, device=dev)
+    pv, pf, V, F = _mesh(verts, faces, "raster_vertex_normals", rows=True)
+    normals = torch.zeros((V, 3), dtype=torch.float64, device=verts.device)
     if V == 0 or F == 0:
         return normals
-    if 3 * F >= 2 ** 31:
-        raise UfrError(f"raster_vertex_normals: {F} faces: (2^31 - 1) / 3 or more")
-    corner = faces.reshape(-1).to(torch.int64)
-    svert, slots = torch.sort(corner, stable=True)
-    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=dev)).contiguous()
-    _lib.check(_lib.load().ufr_raster_vertex_normals(pv, pf, V, F, slots.contiguous().data_ptr(), runs.data_ptr(), normals.data_ptr(),
+    slots, runs = _corner_runs(faces, V)
+    _lib.check(_lib.load().ufr_raster_vertex_normals(pv, pf, V, F, slots.data_ptr(), runs.data_ptr(), normals.data_ptr(),
                                                      _stream()), "ufr_raster_vertex_normals")
     return normals
 
@@ -1680,30 +1717,21 @@ def mesh_color_fill(faces: torch.Tensor, colors: torch.Tensor, views_used: torch
     last, and is counted.  The corner slots are sorted by vertex here, once (stable).  A face index out of range raises.
     One host read per round, and one for the index check."""
     pf = _dev(faces, "faces", torch.int32)
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
     _dev(colors, "colors", torch.uint8)
     _dev(views_used, "views_used", torch.uint8)
-    V, F = int(views_used.shape[0]), int(faces.shape[0])
+    V = int(views_used.shape[0])
     if tuple(colors.shape) != (V, 3) or views_used.dim() != 1:
         raise UfrError(f"mesh_color_fill: colors {tuple(colors.shape)}, views_used {tuple(views_used.shape)}: expected (V, 3) and (V,)")
     rounds = int(rounds)
     if rounds < 0:
         raise UfrError(f"mesh_color_fill: rounds {rounds} (must be >= 0)")
-    if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
-        raise UfrError(f"mesh_color_fill: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
-    if 3 * F >= 2 ** 31:
-        raise UfrError(f"mesh_color_fill: {F} faces: (2^31 - 1) / 3 or more")
-    dev = colors.device
+    F = _faces(faces, V, "mesh_color_fill", rows=True)
     cur, state = colors.clone(), (views_used != 0).to(torch.uint8)
     if rounds == 0 or V == 0 or F == 0:
         return cur, state, 0
-    corner = faces.reshape(-1).to(torch.int64)
-    svert, slots = torch.sort(corner, stable=True)
-    slots = slots.contiguous()
-    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=dev)).contiguous()
+    slots, runs = _corner_runs(faces, V)
     nxt, nstate = torch.empty_like(cur), torch.empty_like(state)
-    filled = torch.zeros(1, dtype=torch.int32, device=dev)
+    filled = torch.zeros(1, dtype=torch.int32, device=colors.device)
     lib, run = _lib.load(), 0
     while run < rounds:
         filled.zero_()
@@ -2011,8 +2039,9 @@ def mesh_simplify(verts: torch.Tensor, faces: torch.Tensor, colors: Optional[tor
 
 
 # ---- mesh smoothing (csrc/mesh_smooth.hip; uforecon_amd/smooth_mesh.py is the caller)
-SMOOTH_BLOCK = 256                                  # kSmoothThreads of csrc/ufr_internal.h: the rows or vertices one block owns
-SMOOTH_CHUNK = 1024                                 # kSmoothChunk: the rows a block of the step stages in LDS at a time
+MESH_ROW_BLOCK = 256                                # kMeshRowThreads of csrc/mesh_rows.h: the rows, faces or vertices one block owns
+MESH_ROW_CHUNK = 1024                               # kMeshRowChunk: the rows a block of a staged walk holds in LDS at a time
+SMOOTH_BLOCK, SMOOTH_CHUNK = MESH_ROW_BLOCK, MESH_ROW_CHUNK
 SMOOTH_WEIGHTS = {"uniform": 0, "cotangent": 1}     # UFR_SMOOTH_UNIFORM / _COTANGENT
 SMOOTH_METHODS = ("taubin", "laplacian")
 SMOOTH_BOUNDARIES = ("fixed", "free")
@@ -2053,34 +2082,16 @@ def mesh_smooth(verts: torch.Tensor, faces: torch.Tensor, method: str = "taubin"
     if boundary not in SMOOTH_BOUNDARIES:
         raise UfrError(f"mesh_smooth: boundary {boundary!r} (one of {sorted(SMOOTH_BOUNDARIES)})")
     factors = smooth_factors(method, iterations, lam, mu)
-    _points64(verts, "verts")
-    _dev(faces, "faces", torch.int32)
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
-    V, F = int(verts.shape[0]), int(faces.shape[0])
-    if pinned is not None:
-        _dev(pinned, "pinned", torch.uint8)
-        if tuple(pinned.shape) != (V,):
-            raise UfrError(f"pinned: expected shape ({V},), got {tuple(pinned.shape)}")
-    if 3 * F >= 2 ** 31:
-        raise UfrError(f"mesh_smooth: {F} faces: (2^31 - 1) / 3 or more")
-    if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
-        raise UfrError(f"mesh_smooth: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
-    dev = verts.device
-    border = torch.zeros(V, dtype=torch.uint8, device=dev)
-    pos_a = verts.clone()
-    if V == 0 or F == 0:
+    V, F, border, pos_a, empty = _ring_setup(verts, faces, pinned, "mesh_smooth")
+    if empty:
         return dict(verts=pos_a, border=border)
     mode = SMOOTH_WEIGHTS[weights]
-    corner = faces.reshape(-1).to(torch.int64)
-    svert, slots = torch.sort(corner, stable=True)
-    slots = slots.contiguous()
-    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=dev)).contiguous()
+    slots, runs = _corner_runs(faces, V)
     lib = _lib.load()
     nbytes = lib.ufr_smooth_workspace_bytes(V, F, mode)
     if nbytes == 0:
         raise UfrError(f"mesh_smooth: V {V}, F {F} unsupported")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
     _lib.check(lib.ufr_smooth_rows(verts.data_ptr(), faces.data_ptr(), V, F, slots.data_ptr(), runs.data_ptr(), mode,
                                         border.data_ptr(), ws.data_ptr(), nbytes, _stream()), "ufr_smooth_rows")
     n = len(factors)
@@ -2091,12 +2102,11 @@ def mesh_smooth(verts: torch.Tensor, faces: torch.Tensor, method: str = "taubin"
                                          None if pinned is None else pinned.data_ptr(), (C.c_double * n)(*factors), n,
                                          pos_a.data_ptr(), pos_b.data_ptr(), ws.data_ptr(), nbytes, _stream()),
                "ufr_smooth_steps")
-    return dict(verts=pos_a if n % 2 == 0 else pos_b, border=border)
+    return dict(verts=_ring_result(pos_a, pos_b, n), border=border)
 
 
 # ---- mesh denoising (csrc/mesh_denoise.hip; uforecon_amd/denoise_mesh.py is the caller)
-DENOISE_BLOCK = 256                                 # kDenoiseThreads of csrc/ufr_internal.h: the faces, rows or vertices one block owns
-DENOISE_CHUNK = 1024                                # kDenoiseChunk: the rows a block of the vertex step stages in LDS at a time
+DENOISE_BLOCK, DENOISE_CHUNK = MESH_ROW_BLOCK, MESH_ROW_CHUNK
 DENOISE_SIGMA_R = 0.35                              # the chord of about 20 degrees: a neighbour turned that far weighs e^-1/2
 
 
@@ -2134,34 +2144,16 @@ def mesh_denoise(verts: torch.Tensor, faces: torch.Tensor, normal_iterations: in
     n_normal = _denoise_count("normal_iterations", normal_iterations)
     n_vertex = _denoise_count("vertex_iterations", vertex_iterations)
     two_ss, two_rr = _denoise_sigma("sigma_s", sigma_s), _denoise_sigma("sigma_r", sigma_r)
-    _points64(verts, "verts")
-    _dev(faces, "faces", torch.int32)
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise UfrError(f"faces: expected shape (F, 3), got {tuple(faces.shape)}")
-    V, F = int(verts.shape[0]), int(faces.shape[0])
-    if pinned is not None:
-        _dev(pinned, "pinned", torch.uint8)
-        if tuple(pinned.shape) != (V,):
-            raise UfrError(f"pinned: expected shape ({V},), got {tuple(pinned.shape)}")
-    if 3 * F >= 2 ** 31:
-        raise UfrError(f"mesh_denoise: {F} faces: (2^31 - 1) / 3 or more")
-    if F and (V == 0 or int(faces.min()) < 0 or int(faces.max()) >= V):
-        raise UfrError(f"mesh_denoise: face indices span {int(faces.min())}..{int(faces.max())}, the mesh has {V} vertices")
-    dev = verts.device
-    border = torch.zeros(V, dtype=torch.uint8, device=dev)
-    normals = torch.zeros((F, 3), dtype=torch.float64, device=dev)
-    pos_a = verts.clone()
-    if V == 0 or F == 0:
+    V, F, border, pos_a, empty = _ring_setup(verts, faces, pinned, "mesh_denoise")
+    normals = torch.zeros((F, 3), dtype=torch.float64, device=verts.device)
+    if empty:
         return dict(verts=pos_a, normals=normals, border=border)
-    corner = faces.reshape(-1).to(torch.int64)
-    svert, slots = torch.sort(corner, stable=True)
-    slots = slots.contiguous()
-    runs = torch.searchsorted(svert, torch.arange(V + 1, dtype=torch.int64, device=dev)).contiguous()
+    slots, runs = _corner_runs(faces, V)
     lib = _lib.load()
     nbytes = lib.ufr_denoise_workspace_bytes(V, F)
     if nbytes == 0:
         raise UfrError(f"mesh_denoise: V {V}, F {F} unsupported")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
     _lib.check(lib.ufr_denoise_faces(verts.data_ptr(), faces.data_ptr(), V, F, slots.data_ptr(), runs.data_ptr(), normals.data_ptr(),
                                      border.data_ptr(), ws.data_ptr(), nbytes, _stream()), "ufr_denoise_faces")
     if n_normal:
@@ -2173,7 +2165,7 @@ def mesh_denoise(verts: torch.Tensor, faces: torch.Tensor, normal_iterations: in
     _lib.check(lib.ufr_denoise_vertices(V, F, runs.data_ptr(), normals.data_ptr(), border.data_ptr() if boundary == "fixed" else None,
                                         None if pinned is None else pinned.data_ptr(), n_vertex, pos_a.data_ptr(), pos_b.data_ptr(),
                                         ws.data_ptr(), nbytes, _stream()), "ufr_denoise_vertices")
-    return dict(verts=pos_a if n_vertex % 2 == 0 else pos_b, normals=normals, border=border)
+    return dict(verts=_ring_result(pos_a, pos_b, n_vertex), normals=normals, border=border)
 
 
 # ---- a scan loader's per-pixel work (csrc/frame_input.hip; uforecon_amd/dtu_scan.py is the caller)
