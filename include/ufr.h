@@ -214,7 +214,12 @@ int ufr_sample_fixed(const float* near, const float* far, const float* U, float*
 
 /* ImportanceSampler.sample_ray (sampler.py:74-108) fused with the coarse+fine merge
  * (model.py:466-470).  weight,z: (RN,SN); U2: (PN,RN) as drawn by torch.rand(PN,RN);
- * z_fine: (RN,PN) sorted (may be NULL); z_all: (RN,SN+PN) sorted. */
+ * z_fine: (RN,PN) sorted (may be NULL); z_all: (RN,SN+PN) sorted.
+ * "Sorted" is the order of torch.sort(stable=True), a total order on every float: numbers ascending with -0 == +0, every
+ * NaN behind +inf, and equal values -- NaNs among themselves included -- in the order of their index in the list that is
+ * sorted (z_all: the SN coarse positions, then the new ones in their own sorted order).  So every slot of every output is
+ * written whatever a ray holds (a NaN or infinite weight, position or uniform; a weight sum that overflows): a ray that
+ * is not finite comes out not finite, in its own slots, and changes nothing of any other ray. */
 int ufr_sample_importance_merge(const float* weight, const float* z, const float* U2, float* z_fine,
                                 float* z_all, int32_t RN, int32_t SN, int32_t PN, ufr_stream stream);
 
@@ -249,7 +254,8 @@ int ufr_aggregate(const void* packed_weights, const float* x_tokens, const float
 /* VolumeRenderer.render (encoder_utils/renderer.py:7-48) with SingleVarianceNetwork
  * (single_variance_network.py:10-11).  z,srdf: (RN,SN); radiance: (RN,SN,3); variance: device scalar.
  * row (nullable, (RN,SN) int32): the colour of slot (ray, s) is radiance[row[ray][s]] -- the sample pool of the two-pass
- * step (ufr_sample_importance_pool); NULL = slot order.
+ * step (ufr_sample_importance_pool); NULL = slot order.  PRECONDITION: row is what ufr_sample_importance_pool writes, per
+ * ray a permutation of that ray's rows of the pool; it is not range-checked here or in ufr_composite_bwd.
  * Outputs: rgb (RN,3), depth (RN), opacity (RN), weight (RN,SN); any may be NULL except depth. */
 int ufr_composite(const float* z, const float* radiance, const int32_t* row, const float* srdf, const float* variance,
                   int32_t RN, int32_t SN, float* rgb, float* depth, float* opacity, float* weight,
@@ -337,7 +343,13 @@ int ufr_project_gather_bwd(const ufr_frame* frame, const ufr_raw_weights* raw, c
  * rows gives the same numbers (ufr_render_rays does that internally).  These entry points expose the pieces so that the
  * training step can do the same, forwards and backwards:
  *   ufr_sample_importance_pool = ufr_sample_importance_merge that also returns the new positions z_new (RN,PN), sorted
- *     along the ray, and for every merged slot its row in the pool [RN*SN coarse rows (ray-major) | RN*PN new rows]: row (RN,SN+PN) int32;
+ *     along the ray, and for every merged slot its row in the pool [RN*SN coarse rows (ray-major) | RN*PN new rows]: row (RN,SN+PN) int32.
+ *     z_all / z_new stand in the order stated at ufr_sample_importance_merge, and row[ray] is ALWAYS a permutation of the
+ *     ray's own rows { ray*SN + s } and { RN*SN + ray*PN + p } (row p of the new block holds z_new[ray][p]), also for a ray
+ *     whose weights, positions or uniforms are NaN or infinite: the producer is the one place that guarantees the table.
+ *     PRECONDITION of every `row` argument below and of ufr_composite / ufr_composite_bwd / ufr_project_gather_bwd: per ray
+ *     a permutation of that ray's pool rows, as this entry point writes it.  The kernels index the pool with it -- the
+ *     adjoints WRITE through it -- and check no range;
  *   ufr_view_transform / ufr_ray_transform = the view-transformer and ray-transformer halves of ufr_aggregate
  *     (token0 (P,80), radiance (P,3) | token0 rows of the RN*SN samples -> srdf (RN,SN)); `row` (nullable, (RN,SN) int32)
  *     maps slot (ray, s) to its row of token0 (NULL = slot order), so the fine pass reads the pool in place;

@@ -7,6 +7,9 @@ and tests/test_gpu_compositor_sampler.py compare the HIP kernels with the same f
 
 A bound of a GPU test is ``max(project bound, 2 x the float32 oracle's distance from float64 on that case)`` (``bound``),
 the rule of test_aggregate_rows_weight_magnitudes.
+
+The sampler's merge order on every float, NaNs included (merge_order), and the rays that are not finite (POISONS):
+tests/test_gpu_nonfinite_rays.py holds the sampler's tables and the kernels that index with them to these.
 """
 from __future__ import annotations
 
@@ -313,6 +316,77 @@ def sampler_ref(w, z, U2, dtype=torch.float64) -> torch.Tensor:
     RN = z.shape[0]
     with torch.no_grad():
         return O.importance_sample(torch.zeros(RN, 3, dtype=dtype), torch.ones(RN, 3, dtype=dtype), w.to(dtype), z.to(dtype), U2)[1]
+
+
+# ------------------------------------------------------------------ the merge order, and rays that are not finite
+def merge_order(v: torch.Tensor) -> torch.Tensor:
+    """The order in which the sampler emits the values of every row of v (..., n): index j stands before index k when
+    v[j] < v[k], or v[k] is a NaN and v[j] is a number (a NaN comes after every number, +inf included), or the two are
+    equal -- as floats, so -0.0 == +0.0, or both NaN -- and j < k.  This is the order of torch.sort(stable=True)
+    (tests/test_forward_refs.py keeps it so); it is stated by counting, without a sort.  -> (..., n) int64: the index of
+    the value that stands at every output position."""
+    o, w = v.unsqueeze(-1), v.unsqueeze(-2)                      # o[..., j, 0] against w[..., 0, k]
+    n = v.shape[-1]
+    j, k = torch.arange(n).unsqueeze(-1), torch.arange(n).unsqueeze(-2)
+    o_nan, w_nan = o.isnan(), w.isnan()
+    before = (o < w) | (~o_nan & w_nan) | (((o == w) | (o_nan & w_nan)) & (j < k))
+    rank = before.sum(-2)                                        # the values in front of index k
+    return torch.empty_like(rank).scatter_(-1, rank, torch.arange(n).expand(rank.shape))
+
+
+def same_values(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Elementwise: two NaNs count as equal, everything else compares by its bits (-0.0 is not +0.0)"""
+    return (a.isnan() & b.isnan()) | (a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32))
+
+
+POISONED_RAYS = (1, 4, 8)       # of SAMPLER_RN = 9: each shares its 4-ray workgroup with clean rays; 8 sits beside three idle waves
+OVERFLOWING_WEIGHT = 3e38       # finite, and already the sum of two exceeds float32
+POISONS = ("w_nan_first", "w_nan_mid", "w_nan_last", "w_nan_all", "w_pinf", "w_ninf", "w_sum_overflows",
+           "z_nan_first", "z_nan_mid", "z_nan_last", "z_nan_all", "z_pinf_last", "z_ninf_first", "u_nan", "w_nan_z_nan",
+           "unsorted_z_nan_first", "unsorted_z_nan_mid", "unsorted_z_nan_last", "unsorted_z_nan_all")
+
+
+@functools.lru_cache(maxsize=None)
+def poisoned_sampler_inputs(SN: int, PN: int, poison: str, RN: int = SAMPLER_RN):
+    """((weight, z, U2), (weight, z, U2) all clean): the 'bump' batch of sampler_inputs with ``poison`` applied to the rays
+    POISONED_RAYS, beside the same batch with nothing applied.  'unsorted_*': the coarse slots of EVERY ray are first
+    permuted with unsorting_permutation, so that the clean rays take the general rank path too (a NaN among sorted coarse
+    positions sends only its own ray there)."""
+    w, z, U2 = (t.clone() for t in sampler_inputs(SN, PN, "bump", RN))
+    what = poison
+    if poison.startswith("unsorted_"):
+        what = poison[len("unsorted_"):]
+        perm = unsorting_permutation(SN)
+        w, z = w[:, perm].contiguous(), z[:, perm].contiguous()
+    clean = (w.clone(), z.clone(), U2.clone())
+    rays = [r for r in POISONED_RAYS if r < RN]
+    nan, inf, mid = float("nan"), float("inf"), SN // 2
+    slot = dict(first=0, mid=mid, last=SN - 1)
+    if what in ("w_nan_first", "w_nan_mid", "w_nan_last"):
+        w[rays, slot[what[6:]]] = nan
+    elif what == "w_nan_all":
+        w[rays] = nan
+    elif what == "w_pinf":
+        w[rays, mid] = inf
+    elif what == "w_ninf":
+        w[rays, mid] = -inf
+    elif what == "w_sum_overflows":
+        w[rays] = OVERFLOWING_WEIGHT
+    elif what in ("z_nan_first", "z_nan_mid", "z_nan_last"):
+        z[rays, slot[what[6:]]] = nan
+    elif what == "z_nan_all":
+        z[rays] = nan
+    elif what == "z_pinf_last":
+        z[rays, SN - 1] = inf
+    elif what == "z_ninf_first":
+        z[rays, 0] = -inf
+    elif what == "u_nan":
+        U2[::2, rays] = nan             # every other uniform, the first included: NaN and finite draws side by side
+    else:
+        assert what == "w_nan_z_nan", poison
+        w[rays, 0] = nan
+        z[rays, mid] = nan
+    return (w.contiguous(), z.contiguous(), U2.contiguous()), clean
 
 
 def unsorting_permutation(SN: int, keep=()) -> torch.Tensor:

@@ -118,6 +118,55 @@ def test_float32_oracle_sampler_stays_near_float64(SN, PN):
         assert int((F.sampler_inputs(SN, PN, "zero_run")[0] == 0).sum()) >= F.SAMPLER_RN * (SN // 3)
 
 
+def _check_merge_order(label, v):
+    order = F.merge_order(v)
+    values, indices = torch.sort(v, dim=-1, stable=True)
+    assert torch.equal(order, indices), label
+    assert bool(F.same_values(torch.gather(v, -1, order), values).all()), label
+
+
+def test_merge_order_on_the_edges_of_the_float_order():
+    nan, inf = float("nan"), float("inf")
+    v = torch.tensor([[nan, 1.0, -0.0, inf, 0.0, nan, -inf, 1.0, 0.0, -0.0, inf, 3e38, -nan, 1.0],
+                      [2.0, 1.0, 1.0, 0.5, 0.5, 0.5, 0.25, 2.0, 9.0, 9.0, -9.0, 0.0, 1.0, 2.0],
+                      [nan] * 14])
+    order = F.merge_order(v)
+    # a NaN after every number, +inf included; NaNs, equal values and the two zeros in index order
+    assert order[0].tolist() == [6, 2, 4, 8, 9, 1, 7, 13, 11, 3, 10, 0, 5, 12]
+    assert order[2].tolist() == list(range(14))
+    _check_merge_order("edges", v)
+    assert bool(F.same_values(v, v).all()) and not bool(F.same_values(v[0, 2], v[0, 4]))      # -0.0 is not +0.0 by bits
+
+
+@pytest.mark.parametrize("SN,PN", F.SAMPLER_SHAPES)
+def test_merge_order_is_the_stable_sort_on_the_poisoned_patterns(SN, PN):
+    """The order the GPU tests hold the sampler to (forward_ref.merge_order) is torch.sort(stable=True), the sort of
+    model.py:466 and sampler.py:106, on what the poisoned rays put into it: the coarse positions followed by the fine
+    samples the float32 reference arithmetic draws from them, the latter in a shuffled order (the reference returns them
+    sorted).  The recipes are checked to poison the rays they claim and no other."""
+    g = torch.Generator().manual_seed(77 + SN + PN)
+    shuffle = torch.randperm(PN, generator=g)
+    clean_rays = [r for r in range(F.SAMPLER_RN) if r not in F.POISONED_RAYS]
+    assert len(F.POISONS) == len(set(F.POISONS)) == 19
+    for poison in F.POISONS:
+        (w, z, U2), (wc, zc, Uc) = F.poisoned_sampler_inputs(SN, PN, poison)
+        for t, c, dim in ((w, wc, 0), (z, zc, 0), (U2, Uc, 1)):
+            assert bool(torch.isfinite(c).all()), poison
+            assert torch.equal(t.index_select(dim, torch.tensor(clean_rays)), c.index_select(dim, torch.tensor(clean_rays))), poison
+        bad = ~(torch.isfinite(w).all(1) & torch.isfinite(z).all(1) & torch.isfinite(U2).all(0))
+        if poison == "w_sum_overflows":
+            bad = torch.isinf(w.sum(1))
+        assert bad.nonzero().flatten().tolist() == list(F.POISONED_RAYS), poison
+        if poison.startswith("unsorted_"):
+            assert not bool((zc[:, 1:] >= zc[:, :-1]).all(1).any()), poison       # every ray: the general path
+        zf = F.sampler_ref(w, z, U2, torch.float32)[:, shuffle]
+        _check_merge_order(f"SN={SN} PN={PN} {poison} fine", zf)
+        _check_merge_order(f"SN={SN} PN={PN} {poison} merged", torch.cat([z, zf], 1))
+    for pattern in F.PATTERNS:
+        w, z, U2 = F.sampler_inputs(SN, PN, pattern)
+        _check_merge_order(f"SN={SN} PN={PN} {pattern}", torch.cat([z, F.sampler_ref(w, z, U2, torch.float32)[:, shuffle]], 1))
+
+
 def test_unsorting_permutation_moves_what_it_may():
     for SN in (2, 3, 16, 255):
         p = F.unsorting_permutation(SN)

@@ -24,7 +24,10 @@ __global__ void __launch_bounds__(256) ray_setup_kernel(const int64_t* __restric
   if (i >= RN) return;
   int64_t p = ray_idx[i];
   // an index outside the H x W grid never becomes an out-of-bounds read: the ray is rendered from pixel 0 with NaN
-  // near / far, so its depth and colour come out NaN (the caller's bug stays visible)
+  // near / far, so every sample position of both passes is NaN and its depth and colour come out NaN (the caller's bug
+  // stays visible).  In the fine pass that rests on importance_merge_kernel below: it ranks NaNs like any other value,
+  // so the ray's slot -> row table is still a permutation of the ray's own pool rows and the kernels that index the
+  // pool through it (ray transformer, compositor, their adjoints -- none checks a range) stay inside this ray
   const bool in_range = p >= 0 && p < (int64_t)HW;
   p = in_range ? p : 0;
   rd_out[3 * i + 0] = ray_d[p];
@@ -108,6 +111,24 @@ __device__ __forceinline__ double wave_incl_scan(double v, int lane) {
   return v;
 }
 
+// The order of every list this kernel emits is the order of torch.sort(stable=True) (sampler.py:106, model.py:466):
+// numbers ascending with -0 == +0, every NaN behind +inf, equal values and NaNs among themselves in index order.  A rank
+// loop `o < v || (o == v && j < k)` is that order for every v that is a number (a NaN o is never in front of it); a NaN v
+// fails both comparisons, so its rank is counted here instead: every number, and the NaNs in front of index k, of a[lo, n).
+// Whatever a ray holds -- a NaN weight, an infinite position, an index outside the image upstream -- its ranks are then
+// a permutation: every slot of z_fine / z_all / z_new / src_row is written, with a row of the ray's own.
+// (Cold code beside hot rank loops: kept small -- not unrolled -- and entered only on `is_nan`, which says "unlikely".)
+__device__ __forceinline__ bool is_nan(float v) { return __builtin_expect(v != v, 0); }
+__device__ __forceinline__ int nan_rank(const float* a, int lo, int n, int k) {
+  int rank = 0;
+#pragma nounroll
+  for (int j = lo; j < n; ++j) {
+    const float o = a[j];
+    rank += (o == o || j < k) ? 1 : 0;
+  }
+  return rank;
+}
+
 __global__ void __launch_bounds__(256) importance_merge_kernel(const float* __restrict__ weight,
                                                                 const float* __restrict__ z,
                                                                 const float* __restrict__ U2, int u_stride,
@@ -187,6 +208,7 @@ __global__ void __launch_bounds__(256) importance_merge_kernel(const float* __re
         float o = zf[j];
         rank += (o < v || (o == v && j < k)) ? 1 : 0;
       }
+      if (is_nan(v)) rank = nan_rank(zf, 0, PN, k);
       z_fine[(size_t)ray * PN + rank] = v;
     }
   }
@@ -211,12 +233,15 @@ __global__ void __launch_bounds__(256) importance_merge_kernel(const float* __re
         const float o = zf[j];
         r += (o < v || (o == v && j < k)) ? 1 : 0;
       }
+      if (is_nan(v)) r = nan_rank(zf, 0, PN, k);
       fs[r] = v;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // coarse sample k: behind it come the new samples that are strictly smaller (an equal new sample has the larger index)
+    // (sorted coarse positions hold no NaN: it fails `<=` on either side.  The new samples may: they stand at the end of fs.)
+    // coarse sample k: behind it come the new samples that are strictly smaller (an equal new sample has the larger index;
+    // a NaN one is not smaller, and nothing but NaNs follows it)
     for (int k = lane; k < SN; k += 64) {
       const float v = all[k];
       int lo = 0, hi = PN;
@@ -226,11 +251,12 @@ __global__ void __launch_bounds__(256) importance_merge_kernel(const float* __re
       out[rank] = v;
       if (src_row) src_row[(size_t)ray * T + rank] = ray * SN + k;
     }
-    // new sample of sorted rank r: in front of it the r new ones before it and the coarse ones that are <= it
+    // new sample of sorted rank r: in front of it the r new ones before it and the coarse ones that are <= it -- written
+    // as "not greater", which for a NaN is all of them
     for (int r = lane; r < PN; r += 64) {
       const float v = fs[r];
       int lo = 0, hi = SN;
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (all[mid] <= v) lo = mid + 1; else hi = mid; }
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (!(all[mid] > v)) lo = mid + 1; else hi = mid; }
       const int rank = r + lo;
       out[rank] = v;
       if (src_row) src_row[(size_t)ray * T + rank] = RN * SN + ray * PN + r;
@@ -247,6 +273,7 @@ __global__ void __launch_bounds__(256) importance_merge_kernel(const float* __re
       rank += before;
       rank_new += j >= SN ? before : 0;
     }
+    if (is_nan(v)) { rank = nan_rank(all, 0, T, k); rank_new = nan_rank(all, SN, T, k); }
     out[rank] = v;
     // the new samples are emitted SORTED along the ray (their pool rows are only ever reached through src_row, so any order
     // is valid): neighbouring lanes of the gather kernels then hold neighbouring positions -- shared footprints in the
