@@ -924,6 +924,75 @@ int ufr_color_fill_round(const int32_t* faces, int64_t V, int64_t F, const int64
                               const uint8_t* colors_in, const uint8_t* state_in, uint8_t* colors_out, uint8_t* state_out,
                               int32_t* filled, ufr_stream stream);
 
+/* ---- mesh texturing (ABI 507, additive) -----------------------------------------------------------------------
+ * A per-face texture atlas baked from the photographs: what a thinned mesh needs to carry the pictures' detail, which one
+ * colour per vertex cannot.  The stage after simplify_mesh, beside mesh colouring; the reference has no such stage.
+ * uforecon_amd/texture_mesh.py is the caller, uforecon_amd/texture_ops.py holds the wrappers, tests/texture_ref.py is the
+ * numpy statement of every rule below.  Neither Open3D nor MVS-texturing was compared against: the rule written here is the
+ * rule.  Everything is fp64, every product and sum rounded on its own (no fused multiply-add), sums taken left to right;
+ * there is no floating-point atomic, so a rerun gives the same bits.  All arrays live on the device unless marked HOST.
+ *
+ * The atlas, in closed form: host and device agree by construction.  Patch size S, 1 <= S <= UFR_TEXTURE_MAX_PATCH, is the
+ *   number of texel steps along a triangle's legs; the cell side is C = S + 3.  Faces 2q and 2q + 1 share cell q; n_cells =
+ *   (F + 1) / 2, cols = ceil(sqrt(n_cells)) (exact, in integers), rows = ceil(n_cells / cols).  Cell q sits at column q % cols
+ *   and row q / cols; the atlas is Wt = cols * C by Ht = rows * C texels, each <= UFR_TEXTURE_MAX_SIDE.  Texel centres are the
+ *   integers, as pixel centres are everywhere in this header.  Local texel (i, j) of a cell (i along x) belongs to the even
+ *   face when i + j <= S + 2, otherwise to the odd face with (i, j) := (C-1-i, C-1-j): a half turn, so nothing is mirrored.
+ *   In those face-local indices corner a sits at (0, 0), b at (S, 0), c at (0, S) -- for the odd face the cell-local texels
+ *   (C-1, C-1), (C-1-S, C-1), (C-1, C-1-S) -- and a texel's weights are wb = i / S, wc = j / S, wa = (1 - wb) - wc.  wa goes
+ *   negative in the gutter, the diagonal band i + j > S past the hypotenuse (two texels deep for the even face, one for
+ *   the odd); the legs lie on the cell's border and need none.  The gutter is what keeps the bilinear footprint of any point of a face, edges and corners included, on that face's own
+ *   texels.  A texel whose face index is >= F belongs to no face.  Patch sizes are uniform: there are no charts and no sizes
+ *   by face area, which suits marching-cubes and clustered meshes, whose faces are of one size.
+ * ufr_texture_bake: one thread per texel.  verts (V,3) fp64; faces (F,3) int32; images, depth, k, w2c, centre, n_views, H, W,
+ *   z_min, depth_tol, min_cos, power, mode, fill: exactly as ufr_color_vertices takes them, with its ranges; S, Ht, Wt: the
+ *   atlas, which must equal the closed form for (F, S); fallback (V,3) uint8, nullable: vertex colours for the texels no view
+ *   saw.  Outputs: texture (Ht,Wt,3) uint8 and views_used (Ht,Wt) uint8.  For a texel of face f with corners a, b, c:
+ *     p = (wa * a + wb * b) + wc * c per component.
+ *     n = (b - a) x (c - a), each component two products and a difference, divided by len = sqrt((n.x*n.x + n.y*n.y) + n.z*n.z);
+ *       a len that is not > 0, or not finite, gives the zero normal, which no view sees.
+ *     The views are walked in ascending order by the per-view rule of ufr_color_vertices (projection, bounds, angle against
+ *       n, occlusion, weight, sample, accumulate), and the colour is formed as there; views_used = the views not skipped.
+ *     No view: to_byte((wa * Ca + wb * Cb) + wc * Cc) per channel of the face's fallback colours when fallback is given
+ *       (to_byte: rint, half to even, clamped to 0..255, not a number: 0), else fill; views_used = 0.
+ *   A texel of no face, and a texel of a face with an index outside 0..V-1, gets fill and 0.  workspace >=
+ *   ufr_color_vertices_workspace_bytes(n_views): the camera table.  Nothing synchronises.
+ * ufr_texture_fill_round: one Jacobi round in texel space, integers only.  colors_in (Ht,Wt,3) uint8, state_in (Ht,Wt) uint8,
+ *   0 = empty; S, Ht, Wt, F: the atlas as above.  A texel with state_in != 0, or of no face, is copied (colour and state).
+ *   An empty one visits (x-1, y), (x+1, y), (x, y-1), (x, y+1) in that order; a neighbour counts when it is inside the atlas,
+ *   belongs to the same face and has state_in != 0.  count > 0: each channel = sum / count rounded half to even in integers
+ *   (the rule of ufr_color_fill_round), state_out = 1 and *filled (device int32, the caller zeroes it) += 1 by an integer
+ *   atomic.  count = 0: copied.  Fallback colours sit in state-0 texels and are never read by a round.  colors_out /
+ *   state_out must not alias the inputs.  Two rounds reach the gutter's depth.  Does not synchronise.
+ * ufr_texture_frames: ufr_raster_frames with the colour taken from a texture: the same first hit, barycentrics, normals,
+ *   shading, depth, face-id and normal outputs, and workspace >= ufr_raster_frames_workspace_bytes(F, H, W).  corner_xy (F,3,2)
+ *   fp64: the texel coordinates (x, y) of every face's corners a, b, c; texture (Ht,Wt,3) uint8, Ht, Wt in 1 ..
+ *   UFR_TEXTURE_MAX_SIDE (any texture: the closed form is not asked for here).  With the shade kernel's own w_a, w_b, w_c:
+ *     tx = (w_a * xa + w_b * xb) + w_c * xc, ty likewise.  A tx or ty that is not finite gives the colour white (1, 1, 1).
+ *     x0 = floor(tx), fx = tx - x0; the indices x0 and x0 + 1 are each clamped to 0..Wt-1 after fx is formed (in double,
+ *       before the conversion); the same in y.
+ *     s = (1 - fy) * ((1 - fx) * T00 + fx * T01) + fy * ((1 - fx) * T10 + fx * T11) per channel, T the widened bytes;
+ *       colour = s / 255; pixel = rint((255 * colour) * I), as ufr_raster_frames.
+ *   There are no mipmaps: a texture seen from afar aliases, and rendering larger and averaging down (ufr_raster_downsample,
+ *   render_trajectory --supersample) is the antialiasing.
+ * Not done: per-face view selection and seam levelling (a texel is blended over all views that see it, like a vertex);
+ * exposure compensation; mipmaps; charts.  Every argument error (null pointer, S outside 1..125, an atlas that is not the
+ * closed form for (F, S), Ht or Wt above 16384, the ranges of ufr_color_vertices, a workspace that is too small, out buffers
+ * that alias in buffers) is UFR_ERR_ARG with the reason in the thread's last-error text; nothing is launched then.       */
+#define UFR_TEXTURE_MAX_PATCH 125
+#define UFR_TEXTURE_MAX_SIDE 16384
+int ufr_texture_bake(const double* verts, const int32_t* faces, int64_t V, int64_t F, const uint8_t* images, const float* depth,
+                     const double* k, const double* w2c, const double* centre, int32_t n_views, int32_t H, int32_t W, int32_t S,
+                     int32_t Ht, int32_t Wt, double z_min, double depth_tol, double min_cos, int32_t power, int32_t mode,
+                     const uint8_t* fill, const uint8_t* fallback, uint8_t* texture, uint8_t* views_used, void* workspace,
+                     size_t workspace_size, ufr_stream stream);
+int ufr_texture_fill_round(const uint8_t* colors_in, const uint8_t* state_in, int32_t S, int32_t Ht, int32_t Wt, int64_t F,
+                           uint8_t* colors_out, uint8_t* state_out, int32_t* filled, ufr_stream stream);
+int ufr_texture_frames(const double* verts, const int32_t* faces, int64_t V, int64_t F, const double* normals, const double* corner_xy,
+                       const uint8_t* texture, int32_t Ht, int32_t Wt, const float* k_inv, const float* c2w, int32_t n_frames,
+                       int32_t H, int32_t W, const uint8_t* background, double ambient, uint8_t* image, float* depth,
+                       int32_t* face_id, float* normal_map, void* workspace, size_t workspace_size, ufr_stream stream);
+
 /* ---- mesh smoothing (ABI 507, additive) ------------------------------------------------------------------------
  * Laplacian and Taubin smoothing with uniform or cotangent weights: the denoising stage of the mesh route, between cleaning
  * and simplification; the reference leaves it to Open3D and trimesh.  uforecon_amd/smooth_mesh.py is the caller,

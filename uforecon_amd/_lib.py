@@ -195,6 +195,12 @@ SIGNATURES = {
                                          i32, i32, C.c_double, C.c_double, C.c_double, i32, i32, C.POINTER(C.c_uint8), vp, vp, vp, sz,
                                          vp]),
     "ufr_color_fill_round": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ufr_texture_bake": (C.c_int, [vp, vp, i64, i64, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i32,
+                                   i32, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, i32, i32, C.POINTER(C.c_uint8), vp, vp,
+                                   vp, vp, sz, vp]),
+    "ufr_texture_fill_round": (C.c_int, [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp]),
+    "ufr_texture_frames": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i32,
+                                     C.POINTER(C.c_uint8), C.c_double, vp, vp, vp, vp, vp, sz, vp]),
     "ufr_simplify_workspace_bytes": (sz, [i64]),
     "ufr_simplify_clusters": (C.c_int, [vp, vp, i64, vp, vp, i64, vp, sz, C.POINTER(i64), vp]),
     "ufr_simplify_face_keys": (C.c_int, [vp, vp, i64, i64, vp, vp]),

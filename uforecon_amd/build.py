@@ -20,7 +20,7 @@ ARCH = "gfx950"
 
 SOURCES = ["api_core.hip", "api_weights_frame.hip", "api_ray.hip", "api_ray_bwd.hip", "api_encoder.hip", "api_geometry.hip", "api_mesh.hip", "api_validate.hip",
            "api_train.hip", "train_step.hip", "prep.hip", "sampler.hip", "gather.hip", "view_transformer.hip",
-           "ray_transformer.hip", "composite.hip", "render_loss.hip", "view_dgrad.hip", "wgrad_stream.hip", "ray_dgrad.hip", "presim_bwd.hip", "gather_bwd.hip", "frustum.hip", "tsdf.hip", "mcubes.hip", "similarity_field.hip", "chamfer.hip", "points_filter.hip", "poisson.hip", "depth_fusion.hip", "mesh_clean.hip", "raster.hip", "splat.hip", "mesh_color.hip", "mesh_simplify.hip", "mesh_smooth.hip", "mesh_denoise.hip", "frame_input.hip", "view_select.hip", "undistort.hip","frame_metrics.hip", "dcn.hip", "fmt.hip", "conv3d.hip", "conv3d_planes.hip", "conv3d_wgrad_planes.hip", "conv2d.hip"]
+           "ray_transformer.hip", "composite.hip", "render_loss.hip", "view_dgrad.hip", "wgrad_stream.hip", "ray_dgrad.hip", "presim_bwd.hip", "gather_bwd.hip", "frustum.hip", "tsdf.hip", "mcubes.hip", "similarity_field.hip", "chamfer.hip", "points_filter.hip", "poisson.hip", "depth_fusion.hip", "mesh_clean.hip", "raster.hip", "splat.hip", "mesh_color.hip", "mesh_texture.hip", "mesh_simplify.hip", "mesh_smooth.hip", "mesh_denoise.hip", "frame_input.hip", "view_select.hip", "undistort.hip","frame_metrics.hip", "dcn.hip", "fmt.hip", "conv3d.hip", "conv3d_planes.hip", "conv3d_wgrad_planes.hip", "conv2d.hip"]
 # -ffp-contract=on: fuse a*b+c only inside one expression.  hipcc's default (fast) also fuses across statements,
 # and did so differently in the two unrolled copies of the per-tile code of the view transformer: a point's result
 # then depended on which column tile it landed in (1 ulp), which breaks "rays are independent -> chunking and the

@@ -1,5 +1,5 @@
 // extern "C" surface of libufr.so (include/ufr.h), meshes: cleaning (mask votes, first hit, face components), rendering,
-// colouring, simplification, smoothing and denoising.  The rounds of the face components and the scans of the simplifier
+// colouring, texturing, simplification, smoothing and denoising.  The rounds of the face components and the scans of the simplifier
 // synchronise the stream to hand a flag or a count to the host; nothing else here waits.
 #include "api_geometry_common.h"
 
@@ -53,6 +53,66 @@ ComponentsWs carve_components(Carver& c, long long F) {
   return w;
 }
 
+// ---- mesh colouring and texturing
+// [camera table: one MeshColorCam per view]
+MeshColorCam* carve_mesh_colors(Carver& c, int n_views) { return c.take<MeshColorCam>((size_t)n_views); }
+
+// the ranges of what the per-view rule takes (ufr_color_vertices and ufr_texture_bake)
+int color_rule_check(const char* who, int32_t n_views, int32_t H, int32_t W, double z_min, double depth_tol, double min_cos,
+                     int32_t power, int32_t mode) {
+  UFR_REQUIRE(n_views >= 1 && n_views <= UFR_MESH_MAX_VIEWS, "%s: n_views %d (must be 1 .. %d)", who, n_views, UFR_MESH_MAX_VIEWS);
+  UFR_REQUIRE(H >= 2 && W >= 2, "%s: image %dx%d (H and W must be >= 2)", who, H, W);
+  UFR_CHECK(depth_image_check(who, H, W));
+  UFR_REQUIRE(z_min >= 0.0 && std::isfinite(z_min), "%s: z_min %g (must be >= 0 and finite)", who, z_min);
+  UFR_REQUIRE(depth_tol >= 0.0 && std::isfinite(depth_tol), "%s: depth_tol %g (must be >= 0 and finite)", who, depth_tol);
+  UFR_REQUIRE(min_cos >= 0.0 && min_cos <= 1.0, "%s: min_cos %g (must be 0 .. 1)", who, min_cos);
+  UFR_REQUIRE(power >= 0 && power <= UFR_MESH_COLOR_MAX_POWER, "%s: power %d (must be 0 .. %d)", who, power, UFR_MESH_COLOR_MAX_POWER);
+  UFR_REQUIRE(mode == UFR_MESH_COLOR_MEAN || mode == UFR_MESH_COLOR_BEST, "%s: unknown mode %d", who, mode);
+  return UFR_OK;
+}
+
+// the host cameras of n_views views as the records the kernels read; every view is checked
+int color_cameras(const char* who, const double* k, const double* w2c, const double* centre, int32_t n_views, MeshColorCam* cams) {
+  for (int32_t f = 0; f < n_views; ++f) {
+    const double *kk = k + 9 * (size_t)f, *m = w2c + 16 * (size_t)f, *cc = centre + 3 * (size_t)f;
+    for (int i = 0; i < 9; ++i) UFR_REQUIRE(std::isfinite(kk[i]), "%s: view %d: k is not finite", who, f);
+    for (int i = 0; i < 16; ++i) UFR_REQUIRE(std::isfinite(m[i]), "%s: view %d: w2c is not finite", who, f);
+    for (int i = 0; i < 3; ++i) UFR_REQUIRE(std::isfinite(cc[i]), "%s: view %d: the camera centre is not finite", who, f);
+    const double r3[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
+    double inv[9];
+    UFR_REQUIRE(invert3(r3, inv), "%s: view %d: w2c is singular", who, f);
+    for (int i = 0; i < 9; ++i) cams[f].k[i] = kk[i], cams[f].r[i] = r3[i];
+    for (int i = 0; i < 3; ++i) cams[f].t[i] = m[4 * i + 3], cams[f].c[i] = cc[i];
+  }
+  return UFR_OK;
+}
+
+// The atlas of F faces at patch size S in closed form (include/ufr.h, "mesh texturing"): cells of side S + 3, two faces a cell,
+// cols = ceil(sqrt(cells)) in integers.  False when S or F is out of range; the caller compares Ht and Wt with its own.
+bool texture_atlas(int64_t F, int32_t S, TextureAtlas* at) {
+  if (F < 1 || F > kChMax || S < 1 || S > UFR_TEXTURE_MAX_PATCH) return false;
+  const long long cells = ((long long)F + 1) / 2;
+  long long cols = (long long)std::sqrt((double)cells);
+  while (cols * cols < cells) ++cols;
+  while (cols > 1 && (cols - 1) * (cols - 1) >= cells) --cols;
+  const long long rows = (cells + cols - 1) / cols, C = S + 3;
+  if (cols * C > UFR_TEXTURE_MAX_SIDE || rows * C > UFR_TEXTURE_MAX_SIDE) return false;
+  at->S = S, at->cols = (int)cols, at->Wt = (int)(cols * C), at->Ht = (int)(rows * C), at->F = F;
+  return true;
+}
+
+int texture_atlas_check(const char* who, int64_t F, int32_t S, int32_t Ht, int32_t Wt, TextureAtlas* at) {
+  UFR_REQUIRE(S >= 1 && S <= UFR_TEXTURE_MAX_PATCH, "%s: S %d (must be 1 .. %d)", who, S, UFR_TEXTURE_MAX_PATCH);
+  UFR_REQUIRE(F >= 1 && F <= kChMax, "%s: F %lld (must be 1 .. 2^31 - 1)", who, (long long)F);
+  UFR_REQUIRE(Ht >= 1 && Wt >= 1 && Ht <= UFR_TEXTURE_MAX_SIDE && Wt <= UFR_TEXTURE_MAX_SIDE, "%s: atlas %dx%d (Ht and Wt must be 1 .. %d)",
+              who, Wt, Ht, UFR_TEXTURE_MAX_SIDE);
+  UFR_REQUIRE(texture_atlas(F, S, at), "%s: %lld faces at S %d need an atlas with a side above %d", who, (long long)F, S,
+              UFR_TEXTURE_MAX_SIDE);
+  UFR_REQUIRE(at->Ht == Ht && at->Wt == Wt, "%s: atlas %dx%d is not the closed form for F %lld, S %d: %dx%d", who, Wt, Ht, (long long)F, S,
+              at->Wt, at->Ht);
+  return UFR_OK;
+}
+
 // ---- mesh simplification
 // every scanning call: one scan workspace over its items
 ScanWs carve_simplify(Carver& c, long long n) { return carve_scan(c, (size_t)simplify_blocks(n)); }
@@ -89,6 +149,40 @@ DenoiseWs carve_mesh_denoise(Carver& c, long long F) {
   w.rows = c.take<int>((size_t)(12 * F));
   w.row_face = c.take<int>((size_t)(3 * F));
   return w;
+}
+
+// what ufr_raster_frames and ufr_texture_frames share: the checks, the workspace and the two launches a frame.  tex null: the
+// colour is the base colour or the vertex colours; given: the texture's (colors and base_color are then null)
+int raster_frames(const char* who, const double* verts, const int32_t* faces, int64_t V, int64_t F, const double* normals,
+                  const uint8_t* colors, const RasterTexture* tex, const float* k_inv, const float* c2w, int32_t n_frames, int32_t H,
+                  int32_t W, const float* base_color, const uint8_t* background, double ambient, uint8_t* image, float* depth,
+                  int32_t* face_id, float* normal_map, void* workspace, size_t workspace_bytes, ufr_stream stream) {
+  UFR_REQUIRE(verts && faces && k_inv && c2w && image && workspace, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax, "%s: V %lld, F %lld (each must be 1 .. 2^31 - 1)", who, (long long)V,
+              (long long)F);
+  UFR_REQUIRE(n_frames >= 1, "%s: n_frames %d (must be >= 1)", who, n_frames);
+  UFR_CHECK(depth_image_check(who, H, W));
+  UFR_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "%s: ambient %g (must be 0 .. 1)", who, ambient);
+  double base[3];
+  unsigned char bg[3];
+  UFR_CHECK(frame_colors(who, base_color, background, base, bg));
+  Carver c(workspace);
+  const RasterFramesWs w = carve_raster_frames(c, F, (long long)H * W);
+  UFR_REQUIRE(workspace_bytes >= c.off, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, c.off);
+  float rot[9], org[3];
+  double proj[12];
+  for (int32_t i = 0; i < n_frames; ++i) UFR_CHECK(hit_camera(who, k_inv, c2w + 16 * (size_t)i, rot, org, proj));   // all, before any launch
+  const size_t px = (size_t)H * W;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int32_t i = 0; i < n_frames; ++i) {   // launches only: the cameras travel as kernel arguments, nothing waits for a frame
+    UFR_CHECK(hit_camera(who, k_inv, c2w + 16 * (size_t)i, rot, org, proj));
+    UFR_TIMED("raster_first_hit", s, launch_first_hit(verts, faces, V, F, k_inv, rot, org, proj, nullptr, H, W, w.hit.keys,
+        w.hit.big_count, w.hit.big_list, w.face_img, nullptr, s));
+    UFR_TIMED("raster_shade", s, launch_raster_shade(verts, faces, V, F, normals, colors, k_inv, rot, org, proj, base, ambient, bg,
+        w.face_img, H, W, image + 3 * px * i, depth ? depth + px * i : nullptr, face_id ? face_id + px * i : nullptr,
+        normal_map ? normal_map + 3 * px * i : nullptr, s, tex));
+  }
+  return UFR_OK;
 }
 
 }  // namespace
@@ -222,33 +316,8 @@ int ufr_raster_frames(const double* verts, const int32_t* faces, int64_t V, int6
                       const float* k_inv, const float* c2w, int32_t n_frames, int32_t H, int32_t W, const float* base_color,
                       const uint8_t* background, double ambient, uint8_t* image, float* depth, int32_t* face_id, float* normal_map,
                       void* workspace, size_t workspace_bytes, ufr_stream stream) {
-  const char* who = "ufr_raster_frames";
-  UFR_REQUIRE(verts && faces && k_inv && c2w && image && workspace, "%s: null argument", who);
-  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax, "%s: V %lld, F %lld (each must be 1 .. 2^31 - 1)", who, (long long)V,
-              (long long)F);
-  UFR_REQUIRE(n_frames >= 1, "%s: n_frames %d (must be >= 1)", who, n_frames);
-  UFR_CHECK(depth_image_check(who, H, W));
-  UFR_REQUIRE(ambient >= 0.0 && ambient <= 1.0, "%s: ambient %g (must be 0 .. 1)", who, ambient);
-  double base[3];
-  unsigned char bg[3];
-  UFR_CHECK(frame_colors(who, base_color, background, base, bg));
-  Carver c(workspace);
-  const RasterFramesWs w = carve_raster_frames(c, F, (long long)H * W);
-  UFR_REQUIRE(workspace_bytes >= c.off, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, c.off);
-  float rot[9], org[3];
-  double proj[12];
-  for (int32_t i = 0; i < n_frames; ++i) UFR_CHECK(hit_camera(who, k_inv, c2w + 16 * (size_t)i, rot, org, proj));   // all, before any launch
-  const size_t px = (size_t)H * W;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int32_t i = 0; i < n_frames; ++i) {   // launches only: the cameras travel as kernel arguments, nothing waits for a frame
-    UFR_CHECK(hit_camera(who, k_inv, c2w + 16 * (size_t)i, rot, org, proj));
-    UFR_TIMED("raster_first_hit", s, launch_first_hit(verts, faces, V, F, k_inv, rot, org, proj, nullptr, H, W, w.hit.keys,
-        w.hit.big_count, w.hit.big_list, w.face_img, nullptr, s));
-    UFR_TIMED("raster_shade", s, launch_raster_shade(verts, faces, V, F, normals, colors, k_inv, rot, org, proj, base, ambient, bg,
-        w.face_img, H, W, image + 3 * px * i, depth ? depth + px * i : nullptr, face_id ? face_id + px * i : nullptr,
-        normal_map ? normal_map + 3 * px * i : nullptr, s));
-  }
-  return UFR_OK;
+  return raster_frames("ufr_raster_frames", verts, faces, V, F, normals, colors, nullptr, k_inv, c2w, n_frames, H, W, base_color,
+                       background, ambient, image, depth, face_id, normal_map, workspace, workspace_bytes, stream);
 }
 
 int ufr_raster_downsample(const uint8_t* src, int32_t n, int32_t H, int32_t W, int32_t s, uint8_t* dst, ufr_stream stream) {
@@ -265,9 +334,6 @@ int ufr_raster_downsample(const uint8_t* src, int32_t n, int32_t H, int32_t W, i
 }
 
 // ------------------------------------------------------------------ mesh colouring
-// [camera table: one MeshColorCam per view]
-MeshColorCam* carve_mesh_colors(Carver& c, int n_views) { return c.take<MeshColorCam>((size_t)n_views); }
-
 size_t ufr_color_vertices_workspace_bytes(int32_t n_views) {
   return (n_views >= 1 && n_views <= UFR_MESH_MAX_VIEWS) ? carved_bytes(carve_mesh_colors, (int)n_views) : 0;
 }
@@ -279,29 +345,12 @@ int ufr_color_vertices(const double* verts, const double* normals, int64_t V, co
   const char* who = "ufr_color_vertices";
   UFR_REQUIRE(verts && images && k && w2c && centre && fill && colors && views_used && workspace, "%s: null argument", who);
   UFR_REQUIRE(V >= 1 && V <= kChMax, "%s: V %lld (must be 1 .. 2^31 - 1)", who, (long long)V);
-  UFR_REQUIRE(n_views >= 1 && n_views <= UFR_MESH_MAX_VIEWS, "%s: n_views %d (must be 1 .. %d)", who, n_views, UFR_MESH_MAX_VIEWS);
-  UFR_REQUIRE(H >= 2 && W >= 2, "%s: image %dx%d (H and W must be >= 2)", who, H, W);
-  UFR_CHECK(depth_image_check(who, H, W));
-  UFR_REQUIRE(z_min >= 0.0 && std::isfinite(z_min), "%s: z_min %g (must be >= 0 and finite)", who, z_min);
-  UFR_REQUIRE(depth_tol >= 0.0 && std::isfinite(depth_tol), "%s: depth_tol %g (must be >= 0 and finite)", who, depth_tol);
-  UFR_REQUIRE(min_cos >= 0.0 && min_cos <= 1.0, "%s: min_cos %g (must be 0 .. 1)", who, min_cos);
-  UFR_REQUIRE(power >= 0 && power <= UFR_MESH_COLOR_MAX_POWER, "%s: power %d (must be 0 .. %d)", who, power, UFR_MESH_COLOR_MAX_POWER);
-  UFR_REQUIRE(mode == UFR_MESH_COLOR_MEAN || mode == UFR_MESH_COLOR_BEST, "%s: unknown mode %d", who, mode);
+  UFR_CHECK(color_rule_check(who, n_views, H, W, z_min, depth_tol, min_cos, power, mode));
   Carver cv(workspace);
   MeshColorCam* table = carve_mesh_colors(cv, n_views);
   UFR_REQUIRE(workspace_bytes >= cv.off, "%s: workspace too small: %zu < %zu bytes", who, workspace_bytes, cv.off);
   MeshColorCam cams[UFR_MESH_MAX_VIEWS];
-  for (int32_t f = 0; f < n_views; ++f) {   // all, before any launch
-    const double *kk = k + 9 * (size_t)f, *m = w2c + 16 * (size_t)f, *cc = centre + 3 * (size_t)f;
-    for (int i = 0; i < 9; ++i) UFR_REQUIRE(std::isfinite(kk[i]), "%s: view %d: k is not finite", who, f);
-    for (int i = 0; i < 16; ++i) UFR_REQUIRE(std::isfinite(m[i]), "%s: view %d: w2c is not finite", who, f);
-    for (int i = 0; i < 3; ++i) UFR_REQUIRE(std::isfinite(cc[i]), "%s: view %d: the camera centre is not finite", who, f);
-    const double r3[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
-    double inv[9];
-    UFR_REQUIRE(invert3(r3, inv), "%s: view %d: w2c is singular", who, f);
-    for (int i = 0; i < 9; ++i) cams[f].k[i] = kk[i], cams[f].r[i] = r3[i];
-    for (int i = 0; i < 3; ++i) cams[f].t[i] = m[4 * i + 3], cams[f].c[i] = cc[i];
-  }
+  UFR_CHECK(color_cameras(who, k, w2c, centre, n_views, cams));   // all, before any launch
   hipStream_t s = static_cast<hipStream_t>(stream);
   UFR_TIMED("mesh_color_cams", s, launch_mesh_color_cams(cams, n_views, table, s));
   UFR_TIMED("mesh_vertex_colors", s, launch_mesh_vertex_colors(verts, normals, V, images, depth, table, n_views, H, W, z_min, depth_tol,
@@ -320,6 +369,57 @@ int ufr_color_fill_round(const int32_t* faces, int64_t V, int64_t F, const int64
   UFR_TIMED("mesh_color_fill_round", s, launch_mesh_color_fill_round(faces, V, F, reinterpret_cast<const long long*>(sorted_slots),
       reinterpret_cast<const long long*>(run_starts), colors_in, state_in, colors_out, state_out, filled, s));
   return UFR_OK;
+}
+
+// ------------------------------------------------------------------ mesh texturing
+int ufr_texture_bake(const double* verts, const int32_t* faces, int64_t V, int64_t F, const uint8_t* images, const float* depth,
+                     const double* k, const double* w2c, const double* centre, int32_t n_views, int32_t H, int32_t W, int32_t S,
+                     int32_t Ht, int32_t Wt, double z_min, double depth_tol, double min_cos, int32_t power, int32_t mode,
+                     const uint8_t* fill, const uint8_t* fallback, uint8_t* texture, uint8_t* views_used, void* workspace,
+                     size_t workspace_size, ufr_stream stream) {
+  const char* who = "ufr_texture_bake";
+  UFR_REQUIRE(verts && faces && images && k && w2c && centre && fill && texture && views_used && workspace, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax, "%s: V %lld (must be 1 .. 2^31 - 1)", who, (long long)V);
+  TextureAtlas at;
+  UFR_CHECK(texture_atlas_check(who, F, S, Ht, Wt, &at));
+  UFR_CHECK(color_rule_check(who, n_views, H, W, z_min, depth_tol, min_cos, power, mode));
+  Carver cv(workspace);
+  MeshColorCam* table = carve_mesh_colors(cv, n_views);
+  UFR_REQUIRE(workspace_size >= cv.off, "%s: workspace too small: %zu < %zu bytes", who, workspace_size, cv.off);
+  MeshColorCam cams[UFR_MESH_MAX_VIEWS];
+  UFR_CHECK(color_cameras(who, k, w2c, centre, n_views, cams));   // all, before any launch
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_color_cams", s, launch_mesh_color_cams(cams, n_views, table, s));
+  UFR_TIMED("mesh_texture_bake", s, launch_texture_bake(verts, faces, V, at, images, depth, table, n_views, H, W, z_min, depth_tol,
+      min_cos, power, mode, fill, fallback, texture, views_used, s));
+  return UFR_OK;
+}
+
+int ufr_texture_fill_round(const uint8_t* colors_in, const uint8_t* state_in, int32_t S, int32_t Ht, int32_t Wt, int64_t F,
+                           uint8_t* colors_out, uint8_t* state_out, int32_t* filled, ufr_stream stream) {
+  const char* who = "ufr_texture_fill_round";
+  UFR_REQUIRE(colors_in && state_in && colors_out && state_out && filled, "%s: null argument", who);
+  TextureAtlas at;
+  UFR_CHECK(texture_atlas_check(who, F, S, Ht, Wt, &at));
+  UFR_REQUIRE(colors_out != colors_in && state_out != state_in, "%s: the round is double-buffered: out must not alias in", who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  UFR_TIMED("mesh_texture_fill_round", s, launch_texture_fill_round(at, colors_in, state_in, colors_out, state_out, filled, s));
+  return UFR_OK;
+}
+
+int ufr_texture_frames(const double* verts, const int32_t* faces, int64_t V, int64_t F, const double* normals, const double* corner_xy,
+                       const uint8_t* texture, int32_t Ht, int32_t Wt, const float* k_inv, const float* c2w, int32_t n_frames,
+                       int32_t H, int32_t W, const uint8_t* background, double ambient, uint8_t* image, float* depth,
+                       int32_t* face_id, float* normal_map, void* workspace, size_t workspace_size, ufr_stream stream) {
+  const char* who = "ufr_texture_frames";
+  UFR_REQUIRE(verts && faces && corner_xy && texture && k_inv && c2w && image && workspace, "%s: null argument", who);
+  UFR_REQUIRE(V >= 1 && V <= kChMax && F >= 1 && F <= kChMax, "%s: V %lld, F %lld (each must be 1 .. 2^31 - 1)", who, (long long)V,
+              (long long)F);
+  UFR_REQUIRE(Ht >= 1 && Wt >= 1 && Ht <= UFR_TEXTURE_MAX_SIDE && Wt <= UFR_TEXTURE_MAX_SIDE, "%s: texture %dx%d (Ht and Wt must be 1 .. %d)",
+              who, Wt, Ht, UFR_TEXTURE_MAX_SIDE);
+  const RasterTexture tex{corner_xy, texture, Ht, Wt};
+  return raster_frames(who, verts, faces, V, F, normals, nullptr, &tex, k_inv, c2w, n_frames, H, W, nullptr, background, ambient, image,
+                       depth, face_id, normal_map, workspace, workspace_size, stream);
 }
 
 // ------------------------------------------------------------------ mesh simplification

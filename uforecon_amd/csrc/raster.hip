@@ -17,7 +17,10 @@
 //            N       smooth: (w_a N_a + w_b N_b) + w_c N_c per component, divided by its length; flat (no vertex normals, or
 //                      that length is not > 0): n / |n|
 //            I       = ambient + (1 - ambient) * |N . d|: a headlight, two-sided, so winding does not matter
-//            colour  the base colour, or ((w_a C_a + w_b C_b) + w_c C_c) / 255 of the uint8 vertex colours
+//            colour  the base colour, or ((w_a C_a + w_b C_b) + w_c C_c) / 255 of the uint8 vertex colours, or (ufr_texture_frames,
+//                      the kernel's textured instance) s / 255 of a texture: tx = (w_a xa + w_b xb) + w_c xc and ty likewise from
+//                      the face's corner texels, x0 = floor(tx), fx = tx - x0, the indices x0 and x0 + 1 clamped to the texture
+//                      after fx is formed, s the bilinear expression of mesh colouring; tx or ty not finite: white.  No mipmaps
 //            pixel   = rint((255 * colour) * I) (round half to even) clamped to 0..255
 //            normal  = R^T N (camera coordinates; products summed in row order), negated when N . d > 0: it faces the camera
 //   downsample      one thread per output byte: the mean of an s x s block in integers, q = sum / s^2, r = sum % s^2, rounded up
@@ -72,10 +75,20 @@ struct ShadeArgs {
   unsigned char bg[3];
 };
 
+// the two texel indices of one axis of a bilinear footprint at t0 = floor(t): t0 and t0 + 1, each clamped to 0..n-1 in double
+// before the conversion (t is finite here, so both fit an int afterwards)
+__device__ inline void clamped_pair(double t0, int n, int* i0, int* i1) {
+  const double hi = (double)(n - 1), t1 = t0 + 1.0;
+  *i0 = (int)(t0 < 0.0 ? 0.0 : (t0 > hi ? hi : t0));
+  *i1 = (int)(t1 < 0.0 ? 0.0 : (t1 > hi ? hi : t1));
+}
+
+// kTextured false: ufr_raster_frames (tex is not looked at); true: ufr_texture_frames, the colour comes from tex
+template <bool kTextured>
 __global__ void __launch_bounds__(kRsThreads) shade_kernel(const double* __restrict__ verts, const int* __restrict__ faces, long long V,
                                                             long long F, const double* __restrict__ normals,
                                                             const unsigned char* __restrict__ colors, HitCam cam, ShadeArgs sh,
-                                                            const int* __restrict__ face_img, int H, int W,
+                                                            RasterTexture tex, const int* __restrict__ face_img, int H, int W,
                                                             unsigned char* __restrict__ image, float* __restrict__ depth,
                                                             int* __restrict__ face_out, float* __restrict__ normal_out) {
   const long long i = (long long)blockIdx.x * kRsThreads + threadIdx.x;
@@ -121,10 +134,32 @@ __global__ void __launch_bounds__(kRsThreads) shade_kernel(const double* __restr
     }
     const double c = dot3(N, d);
     const double I = sh.ambient + (1.0 - sh.ambient) * fabs(c);
+    double tcol[3] = {1.0, 1.0, 1.0};   // textured: white unless the texture coordinate is finite
+    if (kTextured) {
+      const double* xy = tex.corner_xy + 6 * f;   // (xa, ya, xb, yb, xc, yc) of face f
+      const double tx = (w0 * xy[0] + w1 * xy[2]) + w2 * xy[4];
+      const double ty = (w0 * xy[1] + w1 * xy[3]) + w2 * xy[5];
+      if (fabs(tx) <= 1.7976931348623157e308 && fabs(ty) <= 1.7976931348623157e308) {   // NaN fails too
+        const double xf = floor(tx), yf = floor(ty);
+        const double fx = tx - xf, fy = ty - yf;
+        int x0, x1, y0, y1;
+        clamped_pair(xf, tex.Wt, &x0, &x1);
+        clamped_pair(yf, tex.Ht, &y0, &y1);
+        const unsigned char* r0 = tex.texture + 3 * (long long)y0 * tex.Wt;
+        const unsigned char* r1 = tex.texture + 3 * (long long)y1 * tex.Wt;
+        const double gx = 1.0 - fx, gy = 1.0 - fy;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double s = gy * (gx * (double)r0[3 * x0 + k] + fx * (double)r0[3 * x1 + k]) +
+                           fy * (gx * (double)r1[3 * x0 + k] + fx * (double)r1[3 * x1 + k]);
+          tcol[k] = s / 255.0;
+        }
+      }
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      double col = sh.base[k];
-      if (colors) {
+      double col = kTextured ? tcol[k] : sh.base[k];
+      if (!kTextured && colors) {
         const double ca = (double)colors[3 * (long long)idx[0] + k], cb = (double)colors[3 * (long long)idx[1] + k],
                      cc = (double)colors[3 * (long long)idx[2] + k];
         col = ((w0 * ca + w1 * cb) + w2 * cc) / 255.0;
@@ -184,13 +219,19 @@ hipError_t launch_raster_vertex_normals(const double* verts, const int* faces, l
 hipError_t launch_raster_shade(const double* verts, const int* faces, long long V, long long F, const double* normals,
                                const unsigned char* colors, const float* kinv, const float* rot, const float* org,
                                const double* proj, const double* base, double ambient, const unsigned char* bg, const int* face_img,
-                               int H, int W, unsigned char* image, float* depth, int* face_out, float* normal_out, hipStream_t s) {
+                               int H, int W, unsigned char* image, float* depth, int* face_out, float* normal_out, hipStream_t s,
+                               const RasterTexture* tex) {
   const HitCam cam = make_hit_cam(kinv, rot, org, proj);
   ShadeArgs sh;
   for (int k = 0; k < 3; ++k) sh.base[k] = base[k], sh.bg[k] = bg[k];
   sh.ambient = ambient;
-  hipLaunchKernelGGL(shade_kernel, dim3(blocks_of((long long)H * W)), dim3(kRsThreads), 0, s, verts, faces, V, F, normals, colors, cam,
-                     sh, face_img, H, W, image, depth, face_out, normal_out);
+  const dim3 grid(blocks_of((long long)H * W)), block(kRsThreads);
+  if (tex)
+    hipLaunchKernelGGL(shade_kernel<true>, grid, block, 0, s, verts, faces, V, F, normals, colors, cam, sh, *tex, face_img, H, W, image,
+                       depth, face_out, normal_out);
+  else
+    hipLaunchKernelGGL(shade_kernel<false>, grid, block, 0, s, verts, faces, V, F, normals, colors, cam, sh, RasterTexture{}, face_img,
+                       H, W, image, depth, face_out, normal_out);
   return hipGetLastError();
 }
 

@@ -203,10 +203,18 @@ hipError_t launch_component_labels(const int* parent, const unsigned char* has_a
 // raster.hip: mesh rendering -- vertex normals, shading of a first-hit face image, box downsampling (see the file header)
 hipError_t launch_raster_vertex_normals(const double* verts, const int* faces, long long V, long long F, const long long* slots,
                                         const long long* runs, double* normals, hipStream_t s);
+// (tex given: the colour of a pixel is the bilinear sample of `texture` (Ht,Wt,3) at the barycentric mix of the face's three
+// texel coordinates corner_xy (F,3,2), ufr_texture_frames; colors and base are then not looked at)
+struct RasterTexture {
+  const double* corner_xy;
+  const unsigned char* texture;
+  int Ht, Wt;
+};
 hipError_t launch_raster_shade(const double* verts, const int* faces, long long V, long long F, const double* normals,
                                const unsigned char* colors, const float* kinv, const float* rot, const float* org,
                                const double* proj, const double* base, double ambient, const unsigned char* bg, const int* face_img,
-                               int H, int W, unsigned char* image, float* depth, int* face_out, float* normal_out, hipStream_t s);
+                               int H, int W, unsigned char* image, float* depth, int* face_out, float* normal_out, hipStream_t s,
+                               const RasterTexture* tex = nullptr);
 hipError_t launch_raster_downsample(const unsigned char* src, long long n, int H, int W, int sf, unsigned char* dst, hipStream_t s);
 // splat.hip: point-cloud rendering -- z-buffered splat into a key image, resolve with eye-dome lighting (see the file header)
 // (k 3x3 and w2c 4x4: host fp64; launch_splat presets the key image before its kernel)
@@ -261,6 +269,19 @@ hipError_t launch_mesh_vertex_colors(const double* verts, const double* normals,
 hipError_t launch_mesh_color_fill_round(const int* faces, long long V, long long F, const long long* slots, const long long* runs,
                                         const unsigned char* colors_in, const unsigned char* state_in, unsigned char* colors_out,
                                         unsigned char* state_out, int* filled, hipStream_t s);
+// mesh_texture.hip: a per-face texture atlas baked from the photographs and its texel-space fill (see the file header)
+constexpr int kTextureThreads = 256;       // texels a block owns (texture_ops.TEXTURE_BLOCK says the same to the tests)
+constexpr bool kTextureBakeCellMajor = true;   // the bake's thread order: profiles/mesh_texture_launch_shapes.md
+struct TextureAtlas {
+  int S, cols, Ht, Wt;                     // patch size, cells a row, the atlas: Wt = cols * (S + 3), Ht = rows * (S + 3)
+  long long F;                             // faces: cell q holds faces 2q and 2q + 1
+};
+hipError_t launch_texture_bake(const double* verts, const int* faces, long long V, const TextureAtlas& at, const unsigned char* images,
+                               const float* depth, const MeshColorCam* table, int n_views, int H, int W, double z_min,
+                               double depth_tol, double min_cos, int power, int mode, const unsigned char* fill,
+                               const unsigned char* fallback, unsigned char* texture, unsigned char* views_used, hipStream_t s);
+hipError_t launch_texture_fill_round(const TextureAtlas& at, const unsigned char* colors_in, const unsigned char* state_in,
+                                     unsigned char* colors_out, unsigned char* state_out, int* filled, hipStream_t s);
 // mesh_simplify.hip: vertex clustering with quadric placement (see the file header)
 constexpr int kSimplifyThreads = 256;      // items a block owns (ops.SIMPLIFY_BLOCK says the same to the tests)
 long long simplify_blocks(long long n);    // blocks of the scanning kernels: sizes the per-block workspace arrays

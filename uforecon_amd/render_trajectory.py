@@ -5,9 +5,11 @@ path is numpy float64; every pixel is HIP (csrc/mesh_clean.hip's first hit, then
 
     python -m uforecon_amd.render_trajectory --mesh_dir OUT/mesh/final --root_dir DTU_TEST --out_dir OUT/rendering
         [--scans ... --views 23 24 23 --num_views 240 --img_wh 800 640 --original_img_wh 1600 1200 --offset_dist 25
-         --supersample 2 --flat --color vertex|uniform --ambient A --format jpg|png --quality 90 --dump_poses DIR]
+         --supersample 2 --flat --color vertex|uniform|texture --ambient A --format jpg|png --quality 90 --dump_poses DIR]
 
 reads ``<mesh_dir>/scan<N>.ply`` and ``<root_dir>/cameras/<view>_cam.txt`` and writes ``<out_dir>/scan<N>/render_<i>.jpg``.
+``--color texture`` reads ``<mesh_dir>/scan<N>.obj`` with its material and PNG instead, as ``texture_mesh`` writes them, and
+takes every pixel's colour from the atlas (bilinear, no mipmaps: ``--supersample`` is the antialiasing).
 
 1. key poses as ``DtuFitSparse.load_scene`` builds ``all_render_w2cs_original``: ``c2w = inv(E)`` in float64, moved by
    ``offset_dist`` along its own x axis; the path is ``interpolate_trajectory`` of the reference (scipy's ``Slerp`` for the
@@ -201,10 +203,12 @@ def _frames_per_chunk(n, H, W, s, extra_bytes_per_pixel, device):
 
 def render_mesh(verts, faces, K, c2ws, H, W, colors=None, smooth=True, ambient=0.25, base_color=(1, 1, 1),
                 background=(255, 255, 255), supersample=1, return_depth=False, return_normals=False, return_face_ids=False,
-                device="cuda"):
+                device="cuda", texture=None, corner_xy=None):
     """Shaded views of a mesh: uint8 (n,H,W,3) images as a numpy array.  ``verts`` (V,3) any float dtype, ``faces`` (F,3)
     integers, ``K`` 3x3 intrinsics (normalised and inverted as ``clean_mesh.ray_camera`` does), ``c2ws`` (n,4,4) or (4,4)
-    camera-to-world matrices, ``colors`` (V,3) uint8 vertex colours or None (``base_color``, 0..1).  ``smooth``: area-weighted
+    camera-to-world matrices, ``colors`` (V,3) uint8 vertex colours or None (``base_color``, 0..1).  ``texture`` (Ht,Wt,3)
+    uint8 with ``corner_xy`` (F,3,2) texel coordinates of every face's corners, as ``texture_mesh.texture_mesh`` returns them:
+    the colour comes from the texture (``texture_ops.raster_frames_textured``; ``colors`` must then be None).  ``smooth``: area-weighted
     vertex normals, else the face normal.  ``supersample`` s in 1..4 renders at s x the size and box-filters down.  With
     ``return_depth`` / ``return_normals`` / ``return_face_ids`` a tuple: the images, then float32 (n,H,W) z-depth (0: no hit),
     float32 (n,H,W,3) camera-space normals facing the camera, int32 (n,H,W) face ids (-1: no hit), in that order -- at
@@ -237,19 +241,36 @@ def render_mesh(verts, faces, K, c2ws, H, W, colors=None, smooth=True, ambient=0
         colors = np.asarray(colors)
         if colors.shape != (V, 3) or colors.dtype != np.uint8:
             raise UfrError(f"render_mesh: colors {colors.shape} {colors.dtype}: expected ({V}, 3) uint8")
+    if (texture is None) != (corner_xy is None) or (texture is not None and colors is not None):
+        raise UfrError("render_mesh: texture and corner_xy come together, and without colors")
+    if texture is not None:
+        texture, corner_xy = np.asarray(texture), np.asarray(corner_xy, np.float64)
+        if texture.ndim != 3 or texture.shape[2] != 3 or texture.dtype != np.uint8 or corner_xy.shape != (F, 3, 2):
+            raise UfrError(f"render_mesh: texture {texture.shape} {texture.dtype}, corner_xy {corner_xy.shape}: expected (Ht, Wt, 3) "
+                           f"uint8 and ({F}, 3, 2)")
     dev = torch.device(device)
     tv = torch.from_numpy(np.ascontiguousarray(verts)).to(dev)
     tf = torch.from_numpy(np.ascontiguousarray(faces.astype(np.int32))).to(dev)
     tc = None if colors is None else torch.from_numpy(np.ascontiguousarray(colors)).to(dev)
+    tt = txy = None
+    if texture is not None:
+        from . import texture_ops
+
+        tt = torch.from_numpy(np.ascontiguousarray(texture)).to(dev)
+        txy = torch.from_numpy(np.ascontiguousarray(corner_xy)).to(dev)
     tn = ops.raster_vertex_normals(tv, tf) if smooth and F else None
     k_inv = ray_camera(supersampled_intrinsics(K, s).astype(np.float32), np.eye(4, dtype=np.float32))[0]
     n = len(c2ws)
     chunk = _frames_per_chunk(n, H, W, s, 4 * return_depth + 12 * return_normals + 4 * return_face_ids, dev)
     out = {k: [] for k in ["image"] + extras}
     for i in range(0, n, chunk):
-        r = ops.raster_frames(tv, tf, k_inv, c2ws[i:i + chunk], s * H, s * W, normals=tn, colors=tc, base_color=base_color,
-                              background=background, ambient=ambient, return_depth=return_depth,
-                              return_face_ids=return_face_ids, return_normals=return_normals, check_indices=False)
+        want = dict(background=background, ambient=ambient, return_depth=return_depth, return_face_ids=return_face_ids,
+                    return_normals=return_normals, check_indices=False)
+        if tt is not None:
+            r = texture_ops.raster_frames_textured(tv, tf, k_inv, c2ws[i:i + chunk], s * H, s * W, txy, tt, normals=tn, **want)
+        else:
+            r = ops.raster_frames(tv, tf, k_inv, c2ws[i:i + chunk], s * H, s * W, normals=tn, colors=tc, base_color=base_color,
+                                  **want)
         if s > 1:
             r["image"] = ops.raster_downsample(r["image"], s)
         for k in out:
@@ -347,7 +368,8 @@ def make_parser():
     parser.add_argument("--offset_dist", type=float, default=OFFSET_DIST, help="sideways shift of the key cameras (mm)")
     parser.add_argument("--supersample", type=int, default=1, choices=[1, 2, 3, 4])
     parser.add_argument("--flat", action="store_true", help="face normals instead of smooth vertex normals")
-    parser.add_argument("--color", choices=["vertex", "uniform"], default="uniform", help="vertex: the PLY's red/green/blue")
+    parser.add_argument("--color", choices=["vertex", "uniform", "texture"], default="uniform",
+                        help="vertex: the PLY's red/green/blue; texture: <mesh_dir>/scan<N>.obj with its PNG (texture_mesh)")
     parser.add_argument("--ambient", type=float, default=0.25)
     parser.add_argument("--format", choices=["jpg", "png"], default="jpg")
     parser.add_argument("--quality", type=int, default=90, help="JPEG quality")
@@ -394,13 +416,20 @@ def render_scan(mesh_path, root_dir, out_dir, views=VIEWS, num_views=NUM_VIEWS, 
                 offset_dist=OFFSET_DIST, supersample=1, flat=False, color="uniform", ambient=0.25, fmt="jpg", quality=90,
                 dump_poses=None):
     """One scan: the frames ``<out_dir>/render_<i>.<fmt>`` of ``mesh_path`` along the path through ``views``.  Returns the
-    (num_views,4,4) camera-to-world matrices."""
-    verts, faces, colors = read_ply(mesh_path, with_colors=True)
+    (num_views,4,4) camera-to-world matrices.  ``color="texture"``: ``mesh_path`` is an OBJ of ``texture_mesh.write_obj``."""
+    texture = corner_xy = None
+    if color == "texture":
+        from .texture_mesh import read_obj
+
+        verts, faces, corner_xy, texture = read_obj(mesh_path)
+        colors = None
+    else:
+        verts, faces, colors = read_ply(mesh_path, with_colors=True)
     if faces is None:
         faces = np.zeros((0, 3), np.int32)
     K, c2ws, H, W = _scan_cameras(root_dir, views, num_views, img_wh, original_img_wh, offset_dist, dump_poses)
     images = render_mesh(verts, faces, K, c2ws, H, W, colors=colors if color == "vertex" else None, smooth=not flat,
-                         ambient=ambient, supersample=supersample)
+                         ambient=ambient, supersample=supersample, texture=texture, corner_xy=corner_xy)
     _write_frames(images, out_dir, fmt, quality)
     return c2ws
 
@@ -436,7 +465,7 @@ def main(argv=None):
                          args.format, args.quality, args.dump_poses)
         return
     for scan in args.scans:
-        mesh = os.path.join(args.mesh_dir, "scan%d.ply" % scan)
+        mesh = os.path.join(args.mesh_dir, "scan%d.%s" % (scan, "obj" if args.color == "texture" else "ply"))
         if not os.path.exists(mesh):
             print("scan%d: no mesh at %s" % (scan, mesh))
             continue
